@@ -7,10 +7,15 @@
 A step = one pass of the hot path (guide binning, XOR/popcount scan, exact check of the noted candidates, hit grouping,
 ordered MIT/CFD replay) over one batch of synthetic guides; index, guides and scores are resident in HBM.
 
+A plain run sets up, warms up, times the K steps, writes the last step's scores if --dump-outputs is given, and prints
+the line.  Everything else it can measure runs only with --full: the per-stage breakdown (`kernel_ms`), the K steps again
+without the event pairs, `extras`, `cpu_baseline` and `per_rank` (--no-extras / --no-cpu-baseline / --no-cli drop parts
+of it).  The fields of the line that need those runs are null in a plain run.
+
 Workloads (BASELINE.json):
   N = 1   configs[2]: 100 000 guides per step vs a 300 M-line synthetic human-scale ISSL index (the configuration the
-          metric's target is quoted on).  north_star's 10 k-guide point and a 64-guide point (the HBM-bound regime of
-          the scan) are measured on the same index after the timed region and reported as extras.
+          metric's target is quoted on).  With --full, north_star's 10 k-guide point and a 64-guide point (the HBM-bound
+          regime of the scan) are measured on the same index after the timed region and reported as extras.
   N > 1   configs[3]: ONE batch of 1 000 000 guides per step, sharded over the N ranks in interleaved chunks
           (crackling_amd/sharding.py), same index replicated: built by rank 0, broadcast over RCCL/xGMI, scores gathered
           on rank 0 inside the timed region.  "scaling": "strong" -- the total work per step is fixed.
@@ -27,7 +32,10 @@ reuse or pruning) is kept as `algorithmic_over_hbm_peak`; `extras.whole_bucket_s
 off; `hbm_regime` is north_star's own point, 10 000 guides per step, where the pruned scan is bound by HBM (two guides
 per group: `hbm_pmc_frac` = PMC-measured bytes of a launch / its time / 8 TB/s).
 `cpu_baseline` times the CPU oracle (oracle/issl_oracle.c, the restatement of the reference's OpenMP scorer) on a
-bounded sample of the same workload -- baseline only, rank 0, N=1.
+bounded sample of the same workload -- baseline only, rank 0, N=1, --full.
+--dump-outputs DIR: rank 0 writes the MIT and CFD scores of the last timed step, in input order, as DIR/mit.npy and
+DIR/cfd.npy (float64; above DUMP_MAX_SCORES guides a fixed, seeded sample of them).  Inputs are seeded: the same
+arguments give the same inputs on every run, so two builds can be compared score for score.
 """
 import argparse
 import json
@@ -47,6 +55,7 @@ PEAK_CLOCK_HZ = 2.4e9       # peak engine clock; under the scan's load the chip 
 N_SIMD = 256 * 4
 VALU_CYCLES_PER_INSTR = 2   # SIMD-32: a wave64 VALU instruction holds the issue port for two cycles
 BROADCAST_LIMIT_S = 600.0   # N > 1: a rank whose image broadcast has not finished by then exits non-zero (watchdog below)
+DUMP_MAX_SCORES = 3_000_000  # --dump-outputs: at most this many guides' scores (2 x 8 B each: 48 MB)
 
 
 def valu_per_2048_cmp(pruned, max_dist):
@@ -234,6 +243,18 @@ def reference_baseline(issl_path, guides, gpu_scores, max_dist, thr, method, thr
         return None
 
 
+def dump_outputs(out_dir, mit, cfd):
+    """--dump-outputs: the scores a caller of the timed path receives for the last step, in input order, as float64
+    .npy files; a batch of more than DUMP_MAX_SCORES guides is represented by a fixed, seeded sample of them."""
+    mit, cfd = np.asarray(mit, dtype=np.float64), np.asarray(cfd, dtype=np.float64)
+    if len(mit) > DUMP_MAX_SCORES:
+        pick = np.sort(np.random.default_rng(20261016).choice(len(mit), DUMP_MAX_SCORES, replace=False))
+        mit, cfd = mit[pick], cfd[pick]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "mit.npy"), mit)
+    np.save(os.path.join(out_dir, "cfd.npy"), cfd)
+
+
 def main():
     # stdout carries exactly one JSON line: anything a library prints there (RCCL's version banner does) is sent
     # to stderr instead, and the line is written to the saved descriptor at the end.
@@ -256,14 +277,22 @@ def main():
     ap.add_argument("--dist", choices=["uniform", "markov"], default="uniform",
                     help="site distribution: iid uniform bases (BASELINE configs) or an AT-rich order-3 Markov chain")
     ap.add_argument("--chunk", type=int, default=4096, help="guides per interleaved shard chunk (N>1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beyond the headline figure: stage breakdown, the "
+                         "steps without event pairs, per-rank records, extras, CPU baseline, CLI leg (off: a plain run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--cpu-budget-s", type=float, default=16.0, help="CPU seconds for the port's thread sweep (the compiled reference takes ~10 s of scoring + two index loads on top)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the 10k-guide, 64-guide and host-pointer points")
-    ap.add_argument("--no-cli", action="store_true", help="skip extras.cli_end_to_end (bin/isslScoreOfftargets as Crackling runs it)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the 10k-guide, 64-guide and host-pointer points")
+    ap.add_argument("--no-cli", action="store_true", help="with --full: skip extras.cli_end_to_end (bin/isslScoreOfftargets as Crackling runs it)")
     ap.add_argument("--dump-scores", default=None,
                     help="rank 0 writes the scores of the last timed step, in input order, to this .npz (tests: the N>1 "
                          "path against the single-process result)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the scores of the last timed step, in input order, as DIR/mit.npy and DIR/cfd.npy "
+                         f"(float64; a fixed, seeded sample of {DUMP_MAX_SCORES} guides when the batch is larger)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -413,37 +442,44 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gather_s = time.perf_counter() - t_scored
-    if a.dump_scores and rank == 0:  # scores of the last timed step in input order
+    if (a.dump_scores or a.dump_outputs) and rank == 0:  # scores of the last timed step in input order
         last = (gathered[0][-1], gathered[1][-1]) if use_dist else (out_mit[-1], out_cfd[-1])
-        np.savez(a.dump_scores, guides=all_guides, mit=last[0].cpu().numpy(), cfd=last[1].cpu().numpy())
+        last = (last[0].cpu().numpy(), last[1].cpu().numpy())
+        if a.dump_scores:
+            np.savez(a.dump_scores, guides=all_guides, mit=last[0], cfd=last[1])
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, *last)
     st = index.stats()
     scan_ms = st["ms_scan"]
-    # Stage breakdown (bin / verify / group / replay) from a short UNTIMED pass: the timed region records only the event
-    # pair around the scan, because every further event record costs ~4 us of stream time.
-    # One lane for it: in the timed region consecutive batches alternate between two workspaces / streams, so that the
-    # short kernels of one batch run beside the scan of the next; a kernel's time is then not its own.
-    index.set_option("stage_timing", 1).set_option("lanes", 1)
-    for _ in range(3):
-        step()
-    index.finish(stream)
-    index.set_option("stage_timing", 0).set_option("lanes", lanes)
-    stages = index.stats()
-    # The same K steps once more as the library runs them when nobody asks for the event pairs (its default: one pair per burst):
-    # reported beside the line, never as `value`.
+    stages = None
     default_events_ms = None
-    if world == 1:
-        index.set_option("scan_events", 2)
-        t1 = time.perf_counter()
-        for i in range(a.steps):
-            index.score_device_async(d_guides, out_mit[i], out_cfd[i], a.max_dist, a.threshold, a.method, stream=None)
-        if index.finish(stream):
-            default_events_ms = (time.perf_counter() - t1) * 1e3 / a.steps
-        index.set_option("scan_events", 1)
+    if a.full:
+        # Stage breakdown (bin / verify / group / replay) from a short UNTIMED pass: the timed region records only the event
+        # pair around the scan, because every further event record costs ~4 us of stream time.
+        # One lane for it: in the timed region consecutive batches alternate between two workspaces / streams, so that the
+        # short kernels of one batch run beside the scan of the next; a kernel's time is then not its own.
+        index.set_option("stage_timing", 1).set_option("lanes", 1)
+        for _ in range(3):
+            step()
+        index.finish(stream)
+        index.set_option("stage_timing", 0).set_option("lanes", lanes)
+        stages = index.stats()
+        # The same K steps once more as the library runs them when nobody asks for the event pairs (its default: one pair per burst):
+        # reported beside the line, never as `value`.
+        if world == 1:
+            index.set_option("scan_events", 2)
+            t1 = time.perf_counter()
+            for i in range(a.steps):
+                index.score_device_async(d_guides, out_mit[i], out_cfd[i], a.max_dist, a.threshold, a.method, stream=None)
+            if index.finish(stream):
+                default_events_ms = (time.perf_counter() - t1) * 1e3 / a.steps
+            index.set_option("scan_events", 1)
     per_rank = None
     if use_dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if use_dist and a.full:
         mine_t = torch.tensor([scan_ms, stages["ms_total"], float(n_mine), float(st["candidates"]), timings.get("broadcast_s", 0.0),
                                float(image_bytes), float(dev_id), float(timings.get("hbm_used_peak_bytes_in_broadcast") or 0)],
                               dtype=torch.float64, device=cdev)
@@ -456,7 +492,7 @@ def main():
                         for r, x in enumerate(allr)]
 
     extras = {}
-    if world > 1 and not a.no_extras:
+    if a.full and world > 1 and not a.no_extras:
         # the weak-scaling companion of the strong figure above: every rank scores configs[2]'s per-GPU batch (100 000
         # guides, or its whole shard if that is smaller) for a few steps, no gather; max over ranks
         n_weak = min(100_000, n_mine)
@@ -479,7 +515,7 @@ def main():
             extras["weak_scaling_point"] = {"guides_per_gpu_per_step": n_weak, "steps": weak_steps, "ms_per_step": dt * 1e3 / weak_steps,
                                             "guides_per_s_all_gpus": world * n_weak * weak_steps / dt,
                                             "note": "every rank its own batch of this size per step, barrier + max over ranks, no gather"}
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         try:  # extra measurement points must never cost the line itself
             # north_star's point: 10 000 guides per step against the same index
             index.set_option("scan_events", 2)  # the library's default: no event pair inside a burst (the kernel's own stamps time the scan)
@@ -711,7 +747,7 @@ def main():
                             f"index image, guides and scores resident in HBM (host-pointer entry point: extras.host_pointer_entry)",
                 "guides_per_step_total": n_total, "guides_per_gpu": n_mine, "sites": a.sites, "distribution": a.dist,
                 "distinct_sites": hdr["n_sites"], "image_bytes": image_bytes, "max_dist": a.max_dist, "threshold": a.threshold,
-                "method": a.method, "spinup_ms": a.spinup_ms, "shard_chunk": a.chunk if world > 1 else None,
+                "method": a.method, "spinup_ms": a.spinup_ms, "shard_chunk": a.chunk if world > 1 else None, "full": a.full,
                 "parallelism": f"interleaved guide shards x{world}, replicated index (RCCL broadcast, gather of scores)" if world > 1 else "single GPU",
             },
             "roofline": {
@@ -733,8 +769,8 @@ def main():
                 "scan_units_per_launch": st["scan_tiles"],
                 "avg_launch_ms": scan_ms,
                 "avg_launch_ms_events": st["ms_scan_events"],
-                "avg_launch_ms_alone": stages["ms_scan"],
-                "frac_alone": useful_valu_cycles / (N_SIMD * PEAK_CLOCK_HZ * stages["ms_scan"] * 1e-3),
+                "avg_launch_ms_alone": stages["ms_scan"] if stages else None,
+                "frac_alone": useful_valu_cycles / (N_SIMD * PEAK_CLOCK_HZ * stages["ms_scan"] * 1e-3) if stages else None,
                 "lanes": lanes,
                 "pruned": st["pruned"],
                 "comparisons_per_launch": cmp_per_launch,
@@ -769,7 +805,7 @@ def main():
                         "same kernel at north_star's 10 000 guides per step, where it is HBM-bound (hbm_pmc_frac)",
             },
             "kernel_ms": {"bin": stages["ms_bin"], "scan": stages["ms_scan"], "verify": stages["ms_verify"], "group": stages["ms_group"],
-                          "replay": stages["ms_replay"], "pipeline": stages["ms_total"]},
+                          "replay": stages["ms_replay"], "pipeline": stages["ms_total"]} if stages else None,
             "hits_per_step": st["hits"],
             "setup_s": timings,
             "gather_s": gather_s if use_dist else None,
@@ -781,8 +817,8 @@ def main():
                              "broadcast_limit_s": BROADCAST_LIMIT_S} if use_dist else None),
             "extras": extras or None,
         }
-        want_cli = world == 1 and not a.no_cli and not a.no_extras
-        if world == 1 and (not a.no_cpu_baseline or want_cli):
+        want_cli = a.full and world == 1 and not a.no_cli and not a.no_extras
+        if a.full and world == 1 and (not a.no_cpu_baseline or want_cli):
             # neither leg must ever cost the line itself: on any failure it is reported inside the line
             t1 = time.perf_counter()
             issl_path = None

@@ -31,7 +31,7 @@ def test_two_ranks_on_one_gpu_through_bench(tmp_path):
     assert one.returncode == 0, one.stderr[-2000:]
     env2 = dict(env, ISSL_BENCH_DEVICE="0", ISSL_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "2", *args,
+                          "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "2", *args, "--full",
                           "--dump-scores", str(tmp_path / "two.npz")], capture_output=True, text=True, env=env2, timeout=600)
     assert two.returncode == 0, two.stderr[-3000:]
     line = json.loads([l for l in two.stdout.splitlines() if l.startswith("{")][-1])
@@ -60,7 +60,7 @@ def test_one_rank_over_rccl_equals_the_plain_run(tmp_path):
     plain = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     assert plain["collectives"] is None and plain["per_rank"] is None
     rccl = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                           "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "1", *args,
+                           "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "1", *args, "--full",
                            "--dump-scores", str(tmp_path / "rccl.npz")], capture_output=True, text=True, env=dict(env, MASTER_ADDR="127.0.0.1"), timeout=600)
     assert rccl.returncode == 0, rccl.stderr[-3000:]
     line = json.loads([l for l in rccl.stdout.splitlines() if l.startswith("{")][-1])

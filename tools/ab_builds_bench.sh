@@ -7,7 +7,7 @@ for dist in uniform markov; do
   for round in 1 2; do
     for which in prev cur; do
       cp tools/_build/libissl_hip_$which.so crackling_amd/libissl_hip.so
-      python3 bench.py --no-cpu-baseline --no-extras --dist $dist 2>/dev/null | python3 -c "
+      python3 bench.py --full --no-cpu-baseline --no-extras --dist $dist 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$dist $which', round(d['ms_per_step'],3), {k:round(x,3) for k,x in d['kernel_ms'].items()})"
     done
   done

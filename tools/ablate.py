@@ -117,7 +117,7 @@ def run(args):
             continue
         lib = OUT / f"libissl_hip_{name}.so"
         env = dict(os.environ, ISSL_HIP_LIBRARY=str(lib))
-        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--no-extras", "--no-cpu-baseline", "--steps", "5", "--warmup", "2"] + args,
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--no-extras", "--no-cpu-baseline", "--steps", "5", "--warmup", "2"] + args,
                            env=env, capture_output=True, text=True)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])

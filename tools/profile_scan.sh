@@ -7,7 +7,7 @@
 # baseline and without its extra measurement points, so that every k_scan launch of a pass has the same batch size.
 set -u
 OUT=gpurun_out/${1:-prof}; shift || true
-ARGS="bench.py --no-cpu-baseline --no-extras $*"
+ARGS="bench.py --full --no-cpu-baseline --no-extras $*"
 cd "$(dirname "$0")/.."
 mkdir -p "$OUT"
 export TMPDIR=/tmp

@@ -5,7 +5,7 @@
 # tracing), every run under its own timeout, a progress line after each.
 set -u
 OUT=gpurun_out/${1:-prof_tail}; shift || true
-ARGS="bench.py --no-cpu-baseline --no-extras --steps 10 --warmup 2 $*"
+ARGS="bench.py --full --no-cpu-baseline --no-extras --steps 10 --warmup 2 $*"
 cd "$(dirname "$0")/.."
 mkdir -p "$OUT"
 export TMPDIR=/tmp

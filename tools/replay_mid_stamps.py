@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Digest of k_replay_mid's phase clocks in an ISSL_SCAN_STAMPS dump (16 u64 per listed guide behind the scan's records;
 entries with [14] == 1 are k_replay_mid's):
-    ISSL_SCAN_STAMPS=/tmp/st.bin python bench.py --dist markov --no-extras --no-cpu-baseline --steps 3 --warmup 1
+    ISSL_SCAN_STAMPS=/tmp/st.bin python bench.py --full --dist markov --no-extras --no-cpu-baseline --steps 3 --warmup 1
     python tools/replay_mid_stamps.py /tmp/st.bin"""
 import numpy as np, sys
 a = np.fromfile(sys.argv[1], dtype=np.uint64)[524288:524288 + 16 * 4096].reshape(-1, 16).astype(np.int64)

@@ -2,7 +2,7 @@
 """Digest of the big-guide phase clocks in an ISSL_SCAN_STAMPS dump (k_replay_big writes 16 u64 per guide after the
 scan's records: start, hits, after partition, slice-0 start, its length, after its sort, after its terms, end, kept).
 
-    ISSL_SCAN_STAMPS=/tmp/st.bin python bench.py --dist markov --steps 5 --warmup 3 --no-cpu-baseline
+    ISSL_SCAN_STAMPS=/tmp/st.bin python bench.py --full --dist markov --steps 5 --warmup 3 --no-cpu-baseline
     python tools/replay_stamps.py /tmp/st.bin [1024]      (the 256-thread build's guides, or the 1024-thread build's)
 """
 import numpy as np, sys

@@ -67,5 +67,5 @@ if len(sys.argv) >= 6 and "scan_hbm_bytes_per_launch" in summary:
                    "trace_avg_launch_ms": summary.get("scan_avg_launch_ns", 0.0) * 1e-6 or None,
                    "trace_calls": summary.get("scan_calls"),
                    "source": f"{dst}_pmc.json (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes over `python3 bench.py "
-                             f"--no-cpu-baseline --no-extras`; FETCH_SIZE x2 per MI355X_MICROARCH.md, KiB->bytes)"})
+                             f"--full --no-cpu-baseline --no-extras`; FETCH_SIZE x2 per MI355X_MICROARCH.md, KiB->bytes)"})
     path.write_text(json.dumps({"points": points}, indent=1) + "\n")
