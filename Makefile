@@ -1,5 +1,5 @@
-# Build of the MI355X ISSL scorer: libissl_hip.so (C ABI, include/issl_hip.h) and the two
-# drop-in executables.  hipcc cross-compiles for gfx950 without a GPU present.
+# Build of the MI355X ISSL scorer: libissl_hip.so (C ABI, include/issl_hip.h; libissl_hip.map keeps every other symbol
+# out of its dynamic table) and the two drop-in executables.  hipcc cross-compiles for gfx950 without a GPU present.
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC     = crackling_amd/csrc
@@ -11,10 +11,13 @@ LIB      = crackling_amd/libissl_hip.so
 
 all: $(LIB) bin/isslScoreOfftargets bin/isslCreateIndex bin/extractOfftargets
 
-$(LIB): $(CSRC)/issl_kernels.hip $(CSRC)/issl_extract.hip $(CSRC)/issl_build.hip $(CSRC)/issl_capi.cpp $(CSRC)/issl_host.cpp $(CSRC)/issl_text.cpp \
-        $(CSRC)/issl_node.cpp $(CSRC)/issl_host.hpp $(CSRC)/issl_device.hpp $(CSRC)/issl_radix.hpp $(CSRC)/cfd_tables.inc include/issl_hip.h
+$(LIB): $(CSRC)/issl_kernels.hip $(CSRC)/issl_extract.hip $(CSRC)/issl_build.hip $(CSRC)/issl_capi.cpp $(CSRC)/issl_upload.cpp $(CSRC)/issl_pipeline.cpp \
+        $(CSRC)/issl_options.cpp $(CSRC)/issl_host.cpp $(CSRC)/issl_text.cpp $(CSRC)/issl_index.hpp \
+        $(CSRC)/issl_node.cpp $(CSRC)/issl_host.hpp $(CSRC)/issl_device.hpp $(CSRC)/issl_radix.hpp $(CSRC)/cfd_tables.inc include/issl_hip.h \
+        $(CSRC)/libissl_hip.map
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/issl_kernels.hip $(CSRC)/issl_extract.hip $(CSRC)/issl_build.hip $(CSRC)/issl_capi.cpp \
-	    $(CSRC)/issl_host.cpp $(CSRC)/issl_text.cpp $(CSRC)/issl_node.cpp -lpthread -ldl
+	    $(CSRC)/issl_upload.cpp $(CSRC)/issl_pipeline.cpp $(CSRC)/issl_options.cpp $(CSRC)/issl_host.cpp $(CSRC)/issl_text.cpp \
+	    $(CSRC)/issl_node.cpp -Wl,--version-script=$(CSRC)/libissl_hip.map -lpthread -ldl
 
 # host-only executable: libissl_hip.so is loaded with dlopen when the process has to score by itself, not when a resident
 # server answers (cli_score.cpp)

@@ -37,7 +37,7 @@ namespace issl {
 //
 // Hot and cold.  The scan reads ONLY `scan` (20 B per site); everything else is read for the ~2e-5 of the comparisons
 // that come within max_dist (k_verify, the replay kernels).  Sections may live in mapped, pinned HOST memory
-// (`cold_on_host`, layout_choices() in issl_capi.cpp): the slice lists of a compact sorted image -- which scoring never
+// (`cold_on_host`, layout_choices() in issl_upload.cpp): the slice lists of a compact sorted image -- which scoring never
 // reads: 52 B per site stay in HBM, so that every index the format can express (4.29 G sites) is scored from one GPU's
 // HBM --, or site table AND lists of a list-order image (25 B per site in HBM: there the candidate's signature is rebuilt
 // from its 32 bit planes in the scan stream, the count comes from `occ8`, and host memory is read only for counts >= 255
@@ -156,7 +156,7 @@ struct Tuning {
                             //                    per CU = 8 waves per SIMD; 768: 6 per SIMD) -- an occupancy experiment, not a tuning knob
     int upload_threads; // ISSL_UPLOAD_THREADS: readers of the ring below (1..32, default 8)
     size_t upload_chunk_kib, upload_ring_min_kib; // ISSL_UPLOAD_CHUNK_KIB / ISSL_UPLOAD_RING_MIN_KIB: the pinned ring a file-mapped index is uploaded through (FileUploader,
-                            //                    issl_capi.cpp): KiB per slot (default 16384) and the section size from which it is used (default 65536); tests
+                            //                    issl_upload.cpp): KiB per slot (default 16384) and the section size from which it is used (default 65536); tests
     uint32_t item_guides;   // ISSL_ITEM_GUIDES   guides per scan item (multiple of 8, <= kItemGuides)
     bool scan_generic;      // ISSL_SCAN_GENERIC  force the runtime-threshold build of the scan kernel
     int scan_events;        // ISSL_SCAN_EVENTS   HIP event pair around the scan: 1 every batch, 2 (default) the first batch after a finish, 0 never
@@ -189,10 +189,18 @@ struct Tuning {
     int keep_lists;         // ISSL_KEEP_LISTS    the slice lists of a compact sorted image: -1 dropped when the image with them
                             //                    does not fit the free HBM (ImageHeader::lists_absent), 0 always dropped, 1 always kept
     std::string stamps_path; // ISSL_SCAN_STAMPS  dump per-wave clocks of the scan here (diagnostics)
+    // The table of these options is issl_options.cpp.
     static Tuning from_env();
     // Returns false when the key is unknown or the value out of range.
     bool set(const char *key, const char *value);
+    // Returns false when the key is unknown or cannot be read (scan_stamps).
+    bool get(const char *key, long long *value) const;
+    // "key=value,key=value": ISSL_OK, or ISSL_E_ARG (message via set_error) at the first item set() refuses.
+    int set_list(const char *options);
 };
+// The read-only keys of issl_index_get_option (is_sorted, cold_on_host, ...) from the header of the handle's image, or -1
+// where it has none (h null).  Returns false when the key is not one of them.
+bool image_option(const ImageHeader *h, const char *key, long long *value);
 
 // Slice lists built on the device (issl_build.hip): d_entries[(s - slice_begin) * n_sites + k] for the slices
 // [slice_begin, slice_end), from the site signatures and their occurrence counts, both already in device memory.

@@ -202,12 +202,12 @@ void append_records(const char *fasta, size_t len, std::string &seq)
     }
     std::vector<std::string> piece(want);
     {
-        std::vector<std::thread> pool;
+        issl::ThreadGroup pool;
         for (size_t t = 1; t < want; ++t)
-            pool.emplace_back([&, t] { piece[t].reserve(cut[t + 1] - cut[t]); parse_fasta_lines(fasta, cut[t], cut[t + 1], piece[t]); });
+            pool.add([&, t] { piece[t].reserve(cut[t + 1] - cut[t]); parse_fasta_lines(fasta, cut[t], cut[t + 1], piece[t]); });
         piece[0].reserve(cut[1] - cut[0]);
         parse_fasta_lines(fasta, cut[0], cut[1], piece[0]);
-        for (auto &th : pool) th.join();
+        pool.join();
     }
     size_t total = seq.size() + 1;
     for (const auto &pc : piece) total += pc.size();
@@ -308,9 +308,11 @@ int issl_extract_from_memory(const char *const *files, const size_t *lens, int n
         issl::set_error("null argument");
         return ISSL_E_ARG;
     }
-    std::string seq;
-    for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], seq);
-    return issl::extract_sorted_text(seq, device, out_text, out_len, n_sites);
+    return issl::abi_call([&] {
+        std::string seq;
+        for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], seq);
+        return issl::extract_sorted_text(seq, device, out_text, out_len, n_sites);
+    });
 }
 
 int issl_extract_offtargets(const char *const *inputs, int n_inputs, const char *output_path, int device,
@@ -320,43 +322,45 @@ int issl_extract_offtargets(const char *const *inputs, int n_inputs, const char 
         issl::set_error("null argument");
         return ISSL_E_ARG;
     }
-    std::string seq;
-    for (int f = 0; f < n_inputs; ++f) {
-        FILE *fp = std::fopen(inputs[f], "rb");
-        if (!fp) {
-            issl::set_error(std::string("cannot open '") + inputs[f] + "'");
-            return ISSL_E_IO;
-        }
-        std::fseek(fp, 0, SEEK_END);
-        const long sz = std::ftell(fp);
-        std::fseek(fp, 0, SEEK_SET);
-        std::vector<char> buf(sz > 0 ? static_cast<size_t>(sz) : 0);
-        if (sz > 0 && std::fread(buf.data(), buf.size(), 1, fp) < 1) {
+    return issl::abi_call([&]() -> int {
+        std::string seq;
+        for (int f = 0; f < n_inputs; ++f) {
+            FILE *fp = std::fopen(inputs[f], "rb");
+            if (!fp) {
+                issl::set_error(std::string("cannot open '") + inputs[f] + "'");
+                return ISSL_E_IO;
+            }
+            std::fseek(fp, 0, SEEK_END);
+            const long sz = std::ftell(fp);
+            std::fseek(fp, 0, SEEK_SET);
+            std::vector<char> buf(sz > 0 ? static_cast<size_t>(sz) : 0);
+            if (sz > 0 && std::fread(buf.data(), buf.size(), 1, fp) < 1) {
+                std::fclose(fp);
+                issl::set_error(std::string("cannot read '") + inputs[f] + "'");
+                return ISSL_E_IO;
+            }
             std::fclose(fp);
-            issl::set_error(std::string("cannot read '") + inputs[f] + "'");
+            issl::append_records(buf.data(), buf.size(), seq);
+        }
+        char *text = nullptr;
+        size_t len = 0;
+        int rc = issl::extract_sorted_text(seq, device, &text, &len, n_sites);
+        if (rc) return rc;
+        FILE *out = std::fopen(output_path, "wb");
+        if (!out) {
+            std::free(text);
+            issl::set_error(std::string("cannot write '") + output_path + "'");
             return ISSL_E_IO;
         }
-        std::fclose(fp);
-        issl::append_records(buf.data(), buf.size(), seq);
-    }
-    char *text = nullptr;
-    size_t len = 0;
-    int rc = issl::extract_sorted_text(seq, device, &text, &len, n_sites);
-    if (rc) return rc;
-    FILE *out = std::fopen(output_path, "wb");
-    if (!out) {
+        const bool ok = (len == 0 || std::fwrite(text, 1, len, out) == len);
+        const bool closed = std::fclose(out) == 0;
         std::free(text);
-        issl::set_error(std::string("cannot write '") + output_path + "'");
-        return ISSL_E_IO;
-    }
-    const bool ok = (len == 0 || std::fwrite(text, 1, len, out) == len);
-    const bool closed = std::fclose(out) == 0;
-    std::free(text);
-    if (!ok || !closed) {
-        issl::set_error(std::string("short write to '") + output_path + "'");
-        return ISSL_E_IO;
-    }
-    return ISSL_OK;
+        if (!ok || !closed) {
+            issl::set_error(std::string("short write to '") + output_path + "'");
+            return ISSL_E_IO;
+        }
+        return ISSL_OK;
+    });
 }
 
 } // extern "C"

@@ -16,6 +16,19 @@ namespace issl {
 static thread_local std::string g_error;
 void set_error(const std::string &msg) { g_error = msg; }
 const char *get_error() { return g_error.c_str(); }
+void set_error(const char *msg) noexcept
+{
+    try {
+        g_error = msg;
+    } catch (...) { // (assigning within the capacity allocates nothing)
+        g_error.assign(msg, std::min(std::strlen(msg), g_error.capacity()));
+    }
+}
+int fail(int rc, const char *msg) noexcept
+{
+    set_error(msg);
+    return rc;
+}
 
 HostIndex::~HostIndex()
 {
@@ -215,9 +228,9 @@ int HostIndex::build_from_text(const char *text, size_t n_lines, size_t seq_len,
     std::vector<uint8_t> starts_run(n_lines);
     {
         const size_t n_threads = std::max<size_t>(1, std::min<size_t>(std::thread::hardware_concurrency(), 16));
-        std::vector<std::thread> pool;
+        ThreadGroup pool;
         for (size_t t = 0; t < n_threads; ++t) {
-            pool.emplace_back([&, t]() {
+            pool.add([&, t]() {
                 const size_t lo = n_lines * t / n_threads, hi = n_lines * (t + 1) / n_threads;
                 for (size_t i = lo; i < hi; ++i) {
                     const char *cur = text + i * stride;
@@ -226,7 +239,7 @@ int HostIndex::build_from_text(const char *text, size_t n_lines, size_t seq_len,
                 }
             });
         }
-        for (auto &th : pool) th.join();
+        pool.join();
     }
     std::vector<uint64_t> sigs;
     std::vector<uint32_t> occ;
@@ -294,9 +307,9 @@ int HostIndex::build_from_sites(const uint64_t *sigs, const uint32_t *occ, size_
             own_entries_[cursor[k]++] = (static_cast<uint64_t>(occ[id]) << 32) | static_cast<uint64_t>(id);
         }
     };
-    std::vector<std::thread> pool;
-    for (uint64_t s = 0; s < geo.n_slices; ++s) pool.emplace_back(do_slice, s);
-    for (auto &t : pool) t.join();
+    ThreadGroup pool;
+    for (uint64_t s = 0; s < geo.n_slices; ++s) pool.add(do_slice, s);
+    pool.join();
     sizes = own_sizes_.data();
     entries = own_entries_.data();
     return finish_build(slice_width);
@@ -332,10 +345,10 @@ int HostIndex::init_without_arrays(const uint64_t *sigs, size_t n_sites, size_t 
         for (size_t id = lo; id < hi; ++id)
             for (uint64_t s = 0; s < n_slices; ++s) ++cnt[s * per_slice + ((sigs[id] >> (slice_width * s)) & (per_slice - 1))];
     };
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < n_threads; ++t) pool.emplace_back(count, t);
+    ThreadGroup pool;
+    for (unsigned t = 1; t < n_threads; ++t) pool.add(count, t);
     count(0);
-    for (auto &t : pool) t.join();
+    pool.join();
     std::vector<uint64_t> total(nb, 0);
     for (const auto &p : part)
         for (uint64_t b = 0; b < nb; ++b) total[b] += p[b];

@@ -4,7 +4,12 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <new>
+#include <stdexcept>
 #include <string>
+#include <system_error>
+#include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/issl_hip.h"
@@ -13,7 +18,35 @@ namespace issl {
 
 // Thread-local error text behind issl_last_error().
 void set_error(const std::string &msg);
+void set_error(const char *msg) noexcept; // (a message there is no memory for is cut to the text's present capacity)
 const char *get_error();
+// set_error(msg), then rc.
+int fail(int rc, const char *msg) noexcept;
+
+// The guard of every extern "C" entry point that allocates or calls into the library: the C ABI never throws
+// (include/issl_hip.h), so what the C++ underneath throws comes back as an error code -- no memory, or no thread to be
+// had (std::system_error), as ISSL_E_NOMEM.
+template <class F> int abi_call(F &&f) noexcept
+{
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        return fail(ISSL_E_NOMEM, "out of memory");
+    } catch (const std::system_error &e) {
+        return fail(ISSL_E_NOMEM, e.what());
+    } catch (const std::exception &e) {
+        return fail(ISSL_E_DEVICE, e.what());
+    }
+}
+
+// Threads joined on every way out of their scope, an exception included (add() throws std::system_error when a thread
+// cannot be started; the ones already running are joined before it leaves the scope).
+struct ThreadGroup {
+    std::vector<std::thread> threads;
+    template <class... A> void add(A &&...a) { threads.emplace_back(std::forward<A>(a)...); }
+    void join() { for (auto &t : threads) if (t.joinable()) t.join(); }
+    ~ThreadGroup() { join(); }
+};
 
 // Geometry of an index (header fields + derived values).
 struct Geometry {

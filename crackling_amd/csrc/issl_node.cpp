@@ -155,118 +155,123 @@ int issl_node_close(issl_node *nd)
 int issl_node_create(issl_index *idx, const int *devices, int n_devices, issl_node **out)
 {
     if (!idx || !out) { set_error("null argument"); return ISSL_E_ARG; }
-    int visible = 0;
-    if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0) {
-        set_error("no HIP device available: the ISSL scorer has no CPU fallback");
-        return ISSL_E_DEVICE;
-    }
-    issl_node *nd = new (std::nothrow) issl_node();
-    if (!nd) { set_error("out of memory"); return ISSL_E_NOMEM; }
-    if (!devices || n_devices <= 0) {
-        for (int d = 0; d < visible; ++d) nd->devices.push_back(d);
-    } else {
-        for (int i = 0; i < n_devices; ++i) {
-            if (devices[i] < 0 || devices[i] >= visible) {
-                delete nd;
-                set_error("device " + std::to_string(devices[i]) + " out of range (" + std::to_string(visible) + " visible)");
-                return ISSL_E_ARG;
-            }
-            nd->devices.push_back(devices[i]);
-        }
-    }
-    const int n = static_cast<int>(nd->devices.size());
-    nd->root = idx;
-    nd->info.n_devices = n;
-    const char *force = std::getenv("ISSL_FORCE_RCCL"), *no = std::getenv("ISSL_NO_RCCL");
-    nd->force_rccl = force && force[0] == '1';
-    nd->no_rccl = no && no[0] == '1';
-    nd->busy_ms.assign(n, 0.0);
-    nd->guides_done.assign(n, 0);
-    double t0 = now_ms();
-    int rc = issl_index_upload(idx, nd->devices[0]);
-    if (rc) { delete nd; return rc; }
-    nd->info.ms_upload = now_ms() - t0;
-    void *img0 = nullptr;
-    size_t bytes = 0;
-    rc = issl_index_image(idx, &img0, &bytes);
-    if (rc) { delete nd; return rc; }
-    nd->images.assign(n, nullptr);
-    nd->replicas.assign(n, nullptr);
-    nd->images[0] = img0;
-    nd->replicas[0] = idx;
-    for (int i = 1; i < n; ++i) {
-        if (hipSetDevice(nd->devices[i]) != hipSuccess || hipMalloc(&nd->images[i], bytes) != hipSuccess) {
-            set_error("cannot allocate the index image on device " + std::to_string(nd->devices[i]));
-            issl_node_close(nd);
+    return abi_call([&]() -> int {
+        int visible = 0;
+        if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0) {
+            set_error("no HIP device available: the ISSL scorer has no CPU fallback");
             return ISSL_E_DEVICE;
         }
-    }
-    t0 = now_ms();
-    int used = 0;
-    rc = broadcast_image(nd, bytes, &used);
-    if (rc) { issl_node_close(nd); return rc; }
-    nd->info.ms_broadcast = now_ms() - t0;
-    nd->info.used_rccl = used;
-    // An image whose cold sections (site table, slice lists) live in pinned host memory is replicated hot part only:
-    // every device reads the ONE host copy (BASELINE configs[4]: index larger than the HBM).
-    void *cold = nullptr;
-    size_t cold_bytes = 0;
-    rc = issl_index_cold(idx, &cold, &cold_bytes);
-    if (rc) { issl_node_close(nd); return rc; }
-    for (int i = 1; i < n; ++i) {
-        rc = cold ? issl_index_attach_image_cold(nd->devices[i], nd->images[i], bytes, cold, cold_bytes, &nd->replicas[i])
-                  : issl_index_attach_image(nd->devices[i], nd->images[i], bytes, &nd->replicas[i]);
+        issl_node *nd = new (std::nothrow) issl_node();
+        if (!nd) { set_error("out of memory"); return ISSL_E_NOMEM; }
+        if (!devices || n_devices <= 0) {
+            for (int d = 0; d < visible; ++d) nd->devices.push_back(d);
+        } else {
+            for (int i = 0; i < n_devices; ++i) {
+                if (devices[i] < 0 || devices[i] >= visible) {
+                    delete nd;
+                    set_error("device " + std::to_string(devices[i]) + " out of range (" + std::to_string(visible) + " visible)");
+                    return ISSL_E_ARG;
+                }
+                nd->devices.push_back(devices[i]);
+            }
+        }
+        const int n = static_cast<int>(nd->devices.size());
+        nd->root = idx;
+        nd->info.n_devices = n;
+        const char *force = std::getenv("ISSL_FORCE_RCCL"), *no = std::getenv("ISSL_NO_RCCL");
+        nd->force_rccl = force && force[0] == '1';
+        nd->no_rccl = no && no[0] == '1';
+        nd->busy_ms.assign(n, 0.0);
+        nd->guides_done.assign(n, 0);
+        double t0 = now_ms();
+        int rc = issl_index_upload(idx, nd->devices[0]);
+        if (rc) { delete nd; return rc; }
+        nd->info.ms_upload = now_ms() - t0;
+        void *img0 = nullptr;
+        size_t bytes = 0;
+        rc = issl_index_image(idx, &img0, &bytes);
+        if (rc) { delete nd; return rc; }
+        nd->images.assign(n, nullptr);
+        nd->replicas.assign(n, nullptr);
+        nd->images[0] = img0;
+        nd->replicas[0] = idx;
+        for (int i = 1; i < n; ++i) {
+            if (hipSetDevice(nd->devices[i]) != hipSuccess || hipMalloc(&nd->images[i], bytes) != hipSuccess) {
+                set_error("cannot allocate the index image on device " + std::to_string(nd->devices[i]));
+                issl_node_close(nd);
+                return ISSL_E_DEVICE;
+            }
+        }
+        t0 = now_ms();
+        int used = 0;
+        rc = broadcast_image(nd, bytes, &used);
         if (rc) { issl_node_close(nd); return rc; }
-    }
-    *out = nd;
-    return ISSL_OK;
+        nd->info.ms_broadcast = now_ms() - t0;
+        nd->info.used_rccl = used;
+        // An image whose cold sections (site table, slice lists) live in pinned host memory is replicated hot part only:
+        // every device reads the ONE host copy (BASELINE configs[4]: index larger than the HBM).
+        void *cold = nullptr;
+        size_t cold_bytes = 0;
+        rc = issl_index_cold(idx, &cold, &cold_bytes);
+        if (rc) { issl_node_close(nd); return rc; }
+        for (int i = 1; i < n; ++i) {
+            rc = cold ? issl_index_attach_image_cold(nd->devices[i], nd->images[i], bytes, cold, cold_bytes, &nd->replicas[i])
+                      : issl_index_attach_image(nd->devices[i], nd->images[i], bytes, &nd->replicas[i]);
+            if (rc) { issl_node_close(nd); return rc; }
+        }
+        *out = nd;
+        return ISSL_OK;
+    });
 }
 
 int issl_node_score(issl_node *nd, const uint64_t *guides, size_t n, int max_dist, double threshold, int method,
                     double *mit, double *cfd)
 {
     if (!nd || (n && (!guides || !mit || !cfd))) { set_error("null argument"); return ISSL_E_ARG; }
-    const size_t world = nd->replicas.size();
-    const double t0 = now_ms();
-    std::vector<int> rcs(world, ISSL_OK);
-    std::vector<std::string> errs(world);
-    // The reference cuts its guide loop statically (OpenMP, isslScoreOfftargets.cpp:316); Crackling emits guides in
-    // genome order, so contiguous eighths would give the GPU with the repeat-dense region the longest shard.  The
-    // batch is a queue of chunks instead: every device thread takes the next one when it is done with its last
-    // (scores land at the chunk's place in the caller's arrays, so input order is kept).
-    const size_t chunk = std::min<size_t>(262144, std::max<size_t>(16384, (n + world * 8 - 1) / (world * 8)));
-    std::atomic<size_t> next{0};
-    std::atomic<bool> failed{false};
-    auto work = [&](size_t r) {
-        nd->busy_ms[r] = 0.0;
-        nd->guides_done[r] = 0;
-        while (!failed.load(std::memory_order_relaxed)) {
-            const size_t lo = next.fetch_add(chunk);
-            if (lo >= n) break;
-            const size_t cnt = std::min(chunk, n - lo);
-            const double t1 = now_ms();
-            rcs[r] = issl_score(nd->replicas[r], guides + lo, cnt, max_dist, threshold, method, mit + lo, cfd + lo);
-            nd->busy_ms[r] += now_ms() - t1;
-            nd->guides_done[r] += cnt;
+    return abi_call([&]() -> int {
+        const size_t world = nd->replicas.size();
+        const double t0 = now_ms();
+        std::vector<int> rcs(world, ISSL_OK);
+        std::vector<std::string> errs(world);
+        // The reference cuts its guide loop statically (OpenMP, isslScoreOfftargets.cpp:316); Crackling emits guides in
+        // genome order, so contiguous eighths would give the GPU with the repeat-dense region the longest shard.  The
+        // batch is a queue of chunks instead: every device thread takes the next one when it is done with its last
+        // (scores land at the chunk's place in the caller's arrays, so input order is kept).
+        const size_t chunk = std::min<size_t>(262144, std::max<size_t>(16384, (n + world * 8 - 1) / (world * 8)));
+        std::atomic<size_t> next{0};
+        std::atomic<bool> failed{false};
+        auto work = [&](size_t r) {
+            nd->busy_ms[r] = 0.0;
+            nd->guides_done[r] = 0;
+            while (!failed.load(std::memory_order_relaxed)) {
+                const size_t lo = next.fetch_add(chunk);
+                if (lo >= n) break;
+                const size_t cnt = std::min(chunk, n - lo);
+                const double t1 = now_ms();
+                rcs[r] = issl_score(nd->replicas[r], guides + lo, cnt, max_dist, threshold, method, mit + lo, cfd + lo);
+                nd->busy_ms[r] += now_ms() - t1;
+                nd->guides_done[r] += cnt;
+                if (rcs[r]) {
+                    errs[r] = issl_last_error();
+                    failed.store(true);
+                    break;
+                }
+            }
+        };
+        {
+            ThreadGroup pool;
+            for (size_t r = 1; r < world; ++r) pool.add(work, r);
+            work(0);
+        }
+        nd->info.ms_last_score = now_ms() - t0;
+        for (size_t r = 0; r < world; ++r) {
             if (rcs[r]) {
-                errs[r] = issl_last_error();
-                failed.store(true);
-                break;
+                set_error("device " + std::to_string(nd->devices[r]) + ": " + errs[r]);
+                return rcs[r];
             }
         }
-    };
-    std::vector<std::thread> pool;
-    for (size_t r = 1; r < world; ++r) pool.emplace_back(work, r);
-    work(0);
-    for (auto &t : pool) t.join();
-    nd->info.ms_last_score = now_ms() - t0;
-    for (size_t r = 0; r < world; ++r) {
-        if (rcs[r]) {
-            set_error("device " + std::to_string(nd->devices[r]) + ": " + errs[r]);
-            return rcs[r];
-        }
-    }
-    return ISSL_OK;
+        return ISSL_OK;
+    });
 }
 
 int issl_node_shard_times(const issl_node *nd, double *busy_ms, uint64_t *guides, int n)

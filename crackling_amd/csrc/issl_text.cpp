@@ -2,8 +2,11 @@
 // (:514-527).  Host code only.  At a million guides per page both are as long as the scoring itself when done the
 // obvious way (one thread, printf("%f") twice per line), so both run on several threads and the "%f" is a formatter of
 // its own -- exact, digit for digit what glibc prints.
+// Also the guide codec's entry points and issl_verdicts, which reads the scores the way Crackling reads that text.
 #include <algorithm>
+#include <cctype>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -179,10 +182,10 @@ int issl_format_scores(const uint64_t *guides, const double *mit, const double *
         out[t].len = static_cast<size_t>(p - buf);
     };
     {
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < nt; ++t) pool.emplace_back(work, t);
+        ThreadGroup pool;
+        for (size_t t = 1; t < nt; ++t) pool.add(work, t);
         work(0);
-        for (auto &th : pool) th.join();
+        pool.join();
     }
     for (size_t t = 0; t < nt; ++t)
         if (failed[t]) {
@@ -249,10 +252,10 @@ int issl_read_query_file(const char *path, size_t seq_len, uint64_t **out, size_
         }
     };
     {
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < nt; ++t) pool.emplace_back(work, t);
+        ThreadGroup pool;
+        for (size_t t = 1; t < nt; ++t) pool.add(work, t);
         work(0);
-        for (auto &th : pool) th.join();
+        pool.join();
     }
     ::close(fd);
     for (size_t t = 0; t < nt; ++t)
@@ -264,6 +267,67 @@ int issl_read_query_file(const char *path, size_t seq_len, uint64_t **out, size_
     *out = g;
     *n = count;
     return ISSL_OK;
+}
+
+int issl_encode_guides(const char *text, size_t n, size_t seq_len, size_t stride, uint64_t *out)
+{
+    if ((!text && n) || !out || seq_len == 0 || seq_len > 32 || stride < seq_len) {
+        set_error("bad argument to issl_encode_guides");
+        return ISSL_E_ARG;
+    }
+    for (size_t i = 0; i < n; ++i) out[i] = encode_guide(text + i * stride, seq_len);
+    return ISSL_OK;
+}
+
+int issl_decode_guide(uint64_t sig, size_t seq_len, char *out)
+{
+    if (!out || seq_len == 0 || seq_len > 32) { set_error("bad argument to issl_decode_guide"); return ISSL_E_ARG; }
+    decode_guide(sig, seq_len, out);
+    return ISSL_OK;
+}
+
+int issl_method_from_string(const char *s) { return method_from_string(s); }
+
+// Crackling.py:780-835.  The caller compares float(<"%f" text>) with the threshold, so a score within 1e-6 of the
+// threshold is sent through the same text round trip; everything else compares the same way without it.
+int issl_verdicts(const double *mit, const double *cfd, size_t n, double threshold, const char *method,
+                  uint8_t *accepted)
+{
+    if (!method || (n && (!mit || !cfd || !accepted))) { set_error("null argument"); return ISSL_E_ARG; }
+    return abi_call([&] {
+        const int printed = method_from_string(method); // exact match, :121-143
+        const bool has_mit = printed == ISSL_METHOD_MIT || printed == ISSL_METHOD_AND || printed == ISSL_METHOD_OR ||
+                             printed == ISSL_METHOD_AVG;
+        const bool has_cfd = printed == ISSL_METHOD_CFD || printed == ISSL_METHOD_AND || printed == ISSL_METHOD_OR ||
+                             printed == ISSL_METHOD_AVG;
+        std::string m(method); // str(...).strip().lower()
+        const char *ws = " \t\n\r\f\v";
+        const size_t b = m.find_first_not_of(ws);
+        m = b == std::string::npos ? std::string() : m.substr(b, m.find_last_not_of(ws) - b + 1);
+        for (char &c : m) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+        const int rule = method_from_string(m.c_str());
+        auto as_read = [&](double x, bool present) {
+            if (!present) return -1.0;
+            if (std::fabs(x - threshold) > 1e-5 && rule != ISSL_METHOD_AVG) return x; // text rounding cannot flip it
+            char buf[400];
+            std::snprintf(buf, sizeof buf, "%f", x);
+            return std::strtod(buf, nullptr);
+        };
+        for (size_t i = 0; i < n; ++i) {
+            const double a = as_read(mit[i], has_mit), c = as_read(cfd[i], has_cfd);
+            bool reject;
+            switch (rule) {
+            case ISSL_METHOD_MIT: reject = a < threshold; break;
+            case ISSL_METHOD_CFD: reject = c < threshold; break;
+            case ISSL_METHOD_AND: reject = a < threshold && c < threshold; break;
+            case ISSL_METHOD_OR: reject = a < threshold || c < threshold; break;
+            case ISSL_METHOD_AVG: reject = (a + c) / 2 < threshold; break;
+            default: accepted[i] = ISSL_VERDICT_NONE; continue;
+            }
+            accepted[i] = reject ? ISSL_VERDICT_REJECTED : ISSL_VERDICT_ACCEPTED;
+        }
+        return ISSL_OK;
+    });
 }
 
 } // extern "C"

@@ -9,8 +9,8 @@
  * bin/isslScoreOfftargets (crackling_amd/csrc/cli_score.cpp) is the shipped caller.
  *
  * Conventions: plain C types only; every function returns 0 on success or a negative
- * ISSL_E_* code, never throws and never calls exit(); issl_last_error() holds the message of the
- * last failure on the calling thread.  One issl_index is used by one thread at a time.
+ * ISSL_E_* code, never throws and never calls exit() (memory or a thread that cannot be had is ISSL_E_NOMEM);
+ * issl_last_error() holds the message of the last failure on the calling thread.  One issl_index is used by one thread at a time.
  * Scoring needs a HIP device: there is NO CPU fallback, calls fail with ISSL_E_DEVICE.
  */
 #ifndef ISSL_HIP_H
@@ -256,9 +256,8 @@ int issl_index_attach_image_cold(int device, void *dev_buf, size_t bytes, void *
  *     ISSL_UPLOAD_THREADS): the ring of pinned chunks a file-mapped index is uploaded through (eight threads pread the
  *     file into two slots each, every slot leaves with its own asynchronous copy: the PCIe link's rate, where hipMemcpy
  *     from the fresh mapping moves a fifth of it; the sections are queued one behind the other, every reader pins its
- *     slots when it first needs them, and the ring goes back on a thread of its own after the handle's first scoring
- *     call -- or at issl_index_close): KiB per slot (default 16384), the section size from which the ring is used
- *     (default 65536), readers (1..32, default 8)
+ *     slots when it first needs them, and the ring is given back at the end of the upload, before it returns): KiB per
+ *     slot (default 16384), the section size from which the ring is used (default 65536), readers (1..32, default 8)
  *   scan_threads (ISSL_SCAN_THREADS) 64..1024: threads per scan workgroup (default 1024 = 8 waves per SIMD; an occupancy
  *     experiment)
  *   prune (ISSL_PRUNE) -1|0|1: scan only the successor-byte groups of a bucket that can hold a site within max_dist (13

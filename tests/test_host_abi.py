@@ -1,9 +1,12 @@
 """CPU: host logic of the product library and its C ABI (no compute calls: there is no GPU here)."""
 import ctypes as C
+import json
 import os
 import pathlib
 import re
+import resource
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -316,31 +319,122 @@ def _has_gpu():
         return False
 
 
+def _option_table():
+    """(key, environment name) of every settable option: the rows of the library's option table."""
+    src = (ROOT / "crackling_amd" / "csrc" / "issl_options.cpp").read_text()
+    rows = re.findall(r'\{"([a-z_0-9]+)", "(ISSL_[A-Z_0-9]+)"', src)
+    assert len(rows) >= 24, rows
+    return rows
+
+
+# (a value inside the option's range, one outside it) for every settable option that can be read back
+OPTION_CASES = {"prune": (1, 2), "lanes": (3, 4), "hit_slots": (2, 3), "lean_tail": (0, 2), "small_bin": (0, 2), "scan_events": (1, 3),
+                "scan_threads": (768, 63), "scan_blocks": (512, 0), "upload_threads": (3, 33), "upload_chunk_kib": (64, 3),
+                "upload_ring_min_kib": (0, -1), "fine_items": (16, -1), "expect_guides": (1000, -1), "scan_generic": (1, 2),
+                "stage_timing": (1, 2), "tail_shapes": (0, 2), "item_guides": (64, 7), "raw_chunks": (1000, -1),
+                "inline_sigs": (0, 2), "host_cold": (1, -2), "sorted_layout": (0, 2), "compact": (1, -2), "keep_lists": (0, 2)}
+
+
 def test_every_documented_option_can_be_set_and_read_back(golden_uniform):
-    """The options `include/issl_hip.h` lists for issl_index_set_option (their environment names in brackets there): each
-    takes a value of its range and gives it back through issl_index_get_option; a value outside the range is refused and
-    leaves the option as it was.  No device needed: options live on the handle."""
-    import re
+    """Every settable option (scan_stamps, a file name, can be set but not read): the header lists it with its environment
+    name; it takes a value of its range and gives it back through issl_index_get_option; a value outside the range, or
+    one that is not a number, is refused and leaves the option as it was.  No device needed: options live on the handle."""
     header = (ROOT / "include" / "issl_hip.h").read_text()
-    named = {n for n in re.findall(r"\b([a-z][a-z_0-9]+)\b", header) if ("ISSL_" + n.upper()) in header}  # name and environment name both there
-    # (name, a value inside its range, a value outside it or None)
-    cases = {"prune": (1, 2), "lanes": (3, 4), "hit_slots": (2, 3), "lean_tail": (0, 2), "small_bin": (0, 2), "scan_events": (1, 3),
-             "scan_threads": (768, 63), "scan_blocks": (512, None), "upload_threads": (3, 33), "upload_chunk_kib": (64, 3),
-             "upload_ring_min_kib": (0, None), "fine_items": (16, None), "expect_guides": (1000, None), "scan_generic": (1, 2),
-             "stage_timing": (1, 2), "tail_shapes": (0, None), "item_guides": (64, None), "raw_chunks": (1000, None)}
-    missing = sorted(n for n in ("small_bin", "scan_events", "upload_threads", "fine_items", "expect_guides", "lean_tail", "lanes", "hit_slots")
-                     if n not in named)
-    assert not missing, f"options this round added or changed are not in the header's list: {missing}"
+    rows = _option_table()
+    missing = sorted(k for k, env in rows if k not in header or env not in header)
+    assert not missing, f"options of the library that the header does not list: {missing}"
+    assert set(OPTION_CASES) == {k for k, _ in rows} - {"scan_stamps"}
     ix = ca.IsslIndex.open(golden_uniform.issl)
     try:
-        for name, (good, bad) in cases.items():
+        for name, (good, bad) in OPTION_CASES.items():
             before = ix.get_option(name)
             ix.set_option(name, good)
             assert ix.get_option(name) == good, name
-            if bad is not None:
+            for refused in (bad, "x", "", "99999999999999999999999"):
+                if name in ("upload_ring_min_kib", "raw_chunks", "expect_guides", "fine_items") and refused == "99999999999999999999999":
+                    continue  # (no upper bound: strtoll's clamp is a value of the range)
                 with pytest.raises(ca.IsslError):
-                    ix.set_option(name, bad)
-                assert ix.get_option(name) == good, name
+                    ix.set_option(name, refused)
+                assert ix.get_option(name) == good, (name, refused)
             ix.set_option(name, before)
+        ix.set_option("scan_stamps", "")
+        with pytest.raises(ca.IsslError):
+            ix.get_option("scan_stamps")
     finally:
         ix.close()
+
+
+_ENV_CHILD = """
+import json, sys
+sys.path.insert(0, sys.argv[1])
+import crackling_amd as ca
+ix = ca.IsslIndex.open(sys.argv[2])
+print(json.dumps({k: ix.get_option(k) for k in sys.argv[3:]}))
+ix.close()
+"""
+
+
+def test_every_option_is_read_from_its_environment_variable(golden_uniform):
+    """A handle reads every option from its environment variable (ISSL_FORCE_HOST_COLD for host_cold); a value out of
+    range there leaves the default in place.  One child process per environment."""
+    rows = [(k, env) for k, env in _option_table() if k in OPTION_CASES]
+    base = {k: v for k, v in os.environ.items() if not k.startswith("ISSL_")}
+
+    def read(extra):
+        run = subprocess.run([sys.executable, "-c", _ENV_CHILD, str(ROOT), str(golden_uniform.issl)] + [k for k, _ in rows],
+                             env={**base, **extra}, capture_output=True, text=True, timeout=120)
+        assert run.returncode == 0, run.stderr
+        return json.loads(run.stdout.strip().splitlines()[-1])
+
+    defaults = read({})
+    good = read({env: str(OPTION_CASES[k][0]) for k, env in rows})
+    assert good == {k: OPTION_CASES[k][0] for k, _ in rows}
+    assert all(good[k] != defaults[k] for k, _ in rows if OPTION_CASES[k][0] != defaults[k])
+    assert read({env: str(OPTION_CASES[k][1]) for k, env in rows}) == defaults
+    assert read({env: "x" for _, env in rows}) == defaults
+
+
+def test_dynamic_symbol_table_is_the_header(tmp_path):
+    """libissl_hip.so defines exactly the functions include/issl_hip.h declares in its dynamic symbol table: no internal
+    C++ symbol another library in the caller's process could interpose."""
+    header = (ROOT / "include" / "issl_hip.h").read_text()
+    declared = set(re.findall(r"\b(issl_[a-z_0-9]+)\s*\(", header))
+    run = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True)
+    assert run.returncode == 0, f"cannot read the dynamic symbol table: {run.stderr}"
+    defined = {line.split()[-1] for line in run.stdout.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtWwiDdBbRrVv"}
+    defined = {name.split("@")[0] for name in defined}
+    assert declared, "no declarations found in the header"
+    assert defined == declared, f"exported but not declared: {sorted(defined - declared)[:20]}; declared but missing: {sorted(declared - defined)}"
+
+
+_NOMEM_CHILD = r"""
+import ctypes as C, resource, sys
+lib = C.CDLL(sys.argv[1])
+lib.issl_last_error.restype = C.c_char_p
+n = 8 << 20
+big = b"ACGTACGTACGTACGTACGT\n" * n                      # made before the limit: 176 MB of text
+small = b"".join((a + b + c + "A" * 17 + "\n").encode() for a in "ACGT" for b in "ACGT" for c in "ACGT")  # 64 sorted lines
+with open("/proc/self/statm") as f:
+    vm = int(f.read().split()[0]) * resource.getpagesize()
+resource.setrlimit(resource.RLIMIT_AS, (vm + (64 << 20), resource.getrlimit(resource.RLIMIT_AS)[1]))
+h = C.c_void_p()
+rc = lib.issl_index_build_from_text(big, C.c_size_t(n), C.c_size_t(20), C.c_size_t(8), C.byref(h))
+print(rc, lib.issl_last_error().decode(), flush=True)
+assert rc == -6 and lib.issl_last_error(), rc                   # ISSL_E_NOMEM, with a message
+rc = lib.issl_index_build_from_text(small, C.c_size_t(64), C.c_size_t(20), C.c_size_t(8), C.byref(h))
+assert rc == 0, (rc, lib.issl_last_error())
+lib.issl_index_close(h)
+print("ok", flush=True)
+"""
+
+
+def test_allocation_failure_comes_back_as_an_error_code():
+    """The C ABI never throws: an index the process has no memory for is ISSL_E_NOMEM with a message, and the library goes
+    on working -- not std::terminate inside the caller's process.  Host-side entry points only (no device is opened); the
+    address space is capped after the library has loaded, the threads' stacks at 1 MiB so that a small build still fits."""
+    def limits():
+        resource.setrlimit(resource.RLIMIT_STACK, (1 << 20, resource.getrlimit(resource.RLIMIT_STACK)[1]))
+    run = subprocess.run([sys.executable, "-c", _NOMEM_CHILD, _lib.LIB_PATH], capture_output=True, text=True, timeout=120,
+                         preexec_fn=limits)
+    assert run.returncode == 0, f"exit {run.returncode}\n{run.stdout}\n{run.stderr[-2000:]}"
+    assert run.stdout.startswith("-6 ") and run.stdout.rstrip().endswith("ok"), run.stdout

@@ -20,3 +20,18 @@ def test_parser_and_builder_are_clean_under_asan_and_ubsan(golden, tmp_path):
                          env={"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
     assert run.returncode == 0, run.stdout + run.stderr
     assert run.stdout.startswith("ok:") and "ERROR" not in run.stderr, run.stdout + run.stderr
+
+
+def test_option_parser_is_clean_under_asan_and_ubsan(tmp_path):
+    """The option table's parser (crackling_amd/csrc/issl_options.cpp, tools/options_sanitize.cpp): empty, non-numeric,
+    overflowing and negative values are refused without a sanitizer report and without changing an option."""
+    exe = tmp_path / "options_sanitize"
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                            str(ROOT / "tools" / "options_sanitize.cpp"), str(ROOT / "crackling_amd" / "csrc" / "issl_options.cpp"),
+                            str(ROOT / "crackling_amd" / "csrc" / "issl_host.cpp"), "-lpthread", "-o", str(exe)],
+                           capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True,
+                         env={"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert run.stdout.startswith("ok:") and "ERROR" not in run.stderr, run.stdout + run.stderr

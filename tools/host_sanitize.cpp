@@ -16,7 +16,7 @@
 
 #include "../crackling_amd/csrc/issl_host.hpp"
 
-extern "C" void issl_free(void *p) { std::free(p); } // (lives in issl_capi.cpp, which needs the HIP runtime)
+extern "C" void issl_free(void *p) { std::free(p); } // (lives in issl_capi.cpp, built with the HIP runtime)
 
 static std::vector<uint8_t> slurp(const char *path)
 {
