@@ -1,5 +1,5 @@
 # Build of the MI355X ISSL scorer: libissl_hip.so (C ABI, include/issl_hip.h; libissl_hip.map keeps every other symbol
-# out of its dynamic table) and the two drop-in executables.  hipcc cross-compiles for gfx950 without a GPU present.
+# out of its dynamic table), the three drop-in executables and isslIndexFromFasta.  hipcc cross-compiles for gfx950 without a GPU present.
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC     = crackling_amd/csrc
@@ -9,7 +9,7 @@ CXXFLAGS = -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result
 HIPFLAGS = $(CXXFLAGS) --offload-arch=$(ARCH)
 LIB      = crackling_amd/libissl_hip.so
 
-all: $(LIB) bin/isslScoreOfftargets bin/isslCreateIndex bin/extractOfftargets
+all: $(LIB) bin/isslScoreOfftargets bin/isslCreateIndex bin/extractOfftargets bin/isslIndexFromFasta
 
 $(LIB): $(CSRC)/issl_kernels.hip $(CSRC)/issl_extract.hip $(CSRC)/issl_build.hip $(CSRC)/issl_capi.cpp $(CSRC)/issl_upload.cpp $(CSRC)/issl_pipeline.cpp \
         $(CSRC)/issl_options.cpp $(CSRC)/issl_host.cpp $(CSRC)/issl_text.cpp $(CSRC)/issl_index.hpp \
@@ -25,7 +25,11 @@ bin/isslScoreOfftargets: $(CSRC)/cli_score.cpp include/issl_hip.h $(LIB)
 	@mkdir -p bin
 	g++ $(CXXFLAGS) -o $@ $< -lpthread -ldl
 
-bin/extractOfftargets: $(CSRC)/cli_extract.cpp $(LIB)
+bin/extractOfftargets: $(CSRC)/cli_extract.cpp $(CSRC)/cli_inputs.hpp $(LIB)
+	@mkdir -p bin
+	$(HIPCC) $(CXXFLAGS) -o $@ $< -Lcrackling_amd -lissl_hip -Wl,-rpath,'$$ORIGIN/../crackling_amd'
+
+bin/isslIndexFromFasta: $(CSRC)/cli_index_fasta.cpp $(CSRC)/cli_inputs.hpp include/issl_hip.h $(LIB)
 	@mkdir -p bin
 	$(HIPCC) $(CXXFLAGS) -o $@ $< -Lcrackling_amd -lissl_hip -Wl,-rpath,'$$ORIGIN/../crackling_amd'
 

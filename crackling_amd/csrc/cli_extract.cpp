@@ -6,16 +6,14 @@
 // Writes every N20 site next to a PAM (both strands, the reference's two patterns), one per line, sorted, duplicates
 // kept -- the input of isslCreateIndex.  The two options of the reference are accepted and ignored (there are no
 // intermediate files and no process pool).  ISSL_DEVICE selects the GPU.
-#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <dirent.h>
 #include <string>
-#include <sys/stat.h>
 #include <vector>
 
 #include "../../include/issl_hip.h"
+#include "cli_inputs.hpp"
 
 int main(int argc, char **argv)
 {
@@ -32,20 +30,7 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "usage: %s output inputs [inputs ...] [--maxOpenFiles N] [--threads N]\n", argv[0]);
         return 2; // argparse's exit status for a usage error
     }
-    std::vector<std::string> inputs(pos.begin() + 1, pos.end());
-    struct stat st;
-    if (inputs.size() == 1 && ::stat(inputs[0].c_str(), &st) == 0 && S_ISDIR(st.st_mode)) { // :204-210
-        const std::string dir = inputs[0];
-        inputs.clear();
-        if (DIR *d = ::opendir(dir.c_str())) {
-            while (dirent *e = ::readdir(d)) {
-                if (e->d_name[0] == '.') continue;
-                inputs.push_back(dir + "/" + e->d_name);
-            }
-            ::closedir(d);
-        }
-        std::sort(inputs.begin(), inputs.end());
-    }
+    const std::vector<std::string> inputs = expand_fasta_inputs(std::vector<std::string>(pos.begin() + 1, pos.end()));
     std::vector<const char *> ptrs;
     for (auto &s : inputs) ptrs.push_back(s.c_str());
     const char *dev = std::getenv("ISSL_DEVICE");

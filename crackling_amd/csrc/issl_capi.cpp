@@ -11,6 +11,25 @@
 
 using namespace issl;
 
+namespace issl {
+
+int build_from_device_sites(const uint64_t *d_sigs, const uint32_t *d_occ, size_t n_sites, size_t n_lines, size_t seq_len,
+                            size_t slice_width, int device, const char *options, issl_index **out)
+{
+    int rc = select_device(device);
+    if (rc) return rc;
+    const uint32_t n_slices = static_cast<uint32_t>((seq_len * 2) / slice_width);
+    std::vector<uint64_t> sizes(size_t(n_slices) << slice_width);
+    rc = launch_bucket_sizes(d_sigs, n_sites, static_cast<uint32_t>(slice_width), n_slices, sizes.data());
+    if (rc) return rc;
+    std::unique_ptr<HostIndex> h(new HostIndex());
+    rc = h->init_from_bucket_sizes(sizes.data(), n_sites, n_lines, seq_len, slice_width);
+    if (rc) return rc;
+    return build_on_device(std::move(h), d_sigs, d_occ, true, device, options, out);
+}
+
+} // namespace issl
+
 extern "C" {
 
 const char *issl_last_error(void) { return get_error(); }
@@ -210,18 +229,7 @@ int issl_index_build_from_device_sites(const uint64_t *d_sigs, const uint32_t *d
         set_error("bad sequence length or slice width");
         return ISSL_E_ARG;
     }
-    return abi_call([&]() -> int {
-        int rc = select_device(device);
-        if (rc) return rc;
-        const uint32_t n_slices = static_cast<uint32_t>((seq_len * 2) / slice_width);
-        std::vector<uint64_t> sizes(size_t(n_slices) << slice_width);
-        rc = launch_bucket_sizes(d_sigs, n_sites, static_cast<uint32_t>(slice_width), n_slices, sizes.data());
-        if (rc) return rc;
-        std::unique_ptr<HostIndex> h(new HostIndex());
-        rc = h->init_from_bucket_sizes(sizes.data(), n_sites, n_lines, seq_len, slice_width);
-        if (rc) return rc;
-        return build_on_device(std::move(h), d_sigs, d_occ, true, device, options, out);
-    });
+    return abi_call([&] { return build_from_device_sites(d_sigs, d_occ, n_sites, n_lines, seq_len, slice_width, device, options, out); });
 }
 
 int issl_index_build_on_device(const uint64_t *sigs, const uint32_t *occ, size_t n_sites, size_t n_lines,

@@ -10,10 +10,17 @@
 // Device: k_match_count / k_match_emit find the matches and write each site as a 40-bit key whose numeric order is
 // the text order (base 0 in the two most significant bits); an LSD radix sort (5 passes of 8 bits) orders the keys;
 // k_keys_to_text expands them to "<20 chars>\n".
+//
+// Genome -> index (issl_index_build_from_fasta): the sorted keys never leave the device.  k_run_heads counts the heads of
+// the runs of equal keys per 4096-key block, launch_scan turns the counts into the rank of every block's first head, and
+// k_run_sites writes, per run, the site's ISSL signature (isslCreateIndex.cpp:39-47,183-200: the 20 two-bit groups of the
+// key in reverse order, base 0 in the least significant bits) and its occurrence count.  Those two arrays go to the
+// device-side builder (issl_index_build_from_device_sites) as they are.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cctype>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +29,7 @@
 #include <vector>
 
 #include "issl_host.hpp"
+#include "issl_index.hpp"
 #include "issl_radix.hpp"
 
 namespace issl {
@@ -141,6 +149,64 @@ __global__ __launch_bounds__(256) void k_keys_to_text(const uint64_t *__restrict
     dst[20] = '\n';
 }
 
+// ---- collapse of the sorted keys into the site table (runs of equal keys -> one site each) -------------------------
+// No thread walks a run: a repeat gives 10^5 identical keys and more.  Every key is looked at by one thread, which
+// compares it with its two neighbours; a run's count is its tail's index + 1 minus its head's index.
+constexpr uint32_t kRunRounds = 16;                 // keys per thread in the collapse kernels
+constexpr uint32_t kRunBlockKeys = 256 * kRunRounds; // keys per 256-thread workgroup
+
+__global__ __launch_bounds__(256) void k_run_heads(const uint64_t *__restrict__ keys, uint64_t n, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t wave_cnt[4];
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kRunBlockKeys;
+    uint32_t c = 0;
+    for (uint32_t r = 0; r < kRunRounds; ++r) {
+        const uint64_t i = base + r * 256 + threadIdx.x;
+        if (i < n && (i == 0 || keys[i] != keys[i - 1])) ++c;
+    }
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// first[b]: heads before block b (exclusive scan of k_run_heads' counts).  occ[] is zeroed before the launch: the head
+// and the tail of a run of two keys or more add -head and tail + 1 to the run's count, in whichever order they come.
+__global__ __launch_bounds__(256) void k_run_sites(const uint64_t *__restrict__ keys, uint64_t n, const uint32_t *__restrict__ first,
+                                                   uint64_t *__restrict__ sigs, uint32_t *__restrict__ occ)
+{
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kRunBlockKeys;
+    uint32_t before = first[blockIdx.x]; // heads ahead of this round
+    for (uint32_t r = 0; r < kRunRounds; ++r) {
+        const uint64_t i = base + r * 256 + threadIdx.x;
+        const bool valid = i < n;
+        const uint64_t key = valid ? keys[i] : 0ull;
+        const bool head = valid && (i == 0 || keys[i - 1] != key);
+        const bool tail = valid && (i + 1 == n || keys[i + 1] != key);
+        const uint64_t heads = __ballot(head);
+        if (lane == 0) wave_cnt[wave] = static_cast<uint32_t>(__builtin_popcountll(heads));
+        __syncthreads();
+        uint32_t rank = before + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(heads >> 32),
+                                                           __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(heads), 0u));
+        for (uint32_t w = 0; w < wave; ++w) rank += wave_cnt[w];
+        // rank: heads before i, i.e. the id of the site i opens, or one past the id of the site i belongs to
+        if (head) {
+            uint64_t sig = 0;
+#pragma unroll
+            for (int p = 0; p < 20; ++p) sig |= ((key >> (2 * (19 - p))) & 3ull) << (2 * p);
+            sigs[rank] = sig;
+        }
+        const uint32_t at = static_cast<uint32_t>(i); // n <= 2^32 - 1: exact, and the sums below are exact mod 2^32
+        if (head && tail) occ[rank] = 1u;
+        else if (head) atomicAdd(&occ[rank], 0u - at);
+        else if (tail) atomicAdd(&occ[rank - 1], at + 1u);
+        before += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+    }
+}
+
 // Sort d_keys[0..n) ascending on the low `bits` bits; d_tmp has the same size.  Result in d_keys.
 int radix_sort(uint64_t *d_keys, uint64_t *d_tmp, uint64_t n, uint32_t bits)
 {
@@ -220,8 +286,37 @@ void append_records(const char *fasta, size_t len, std::string &seq)
     if (!seq.empty() && seq.back() != '\n') seq.push_back('\n');
 }
 
-// seq (host) -> sorted site text (host, malloc'd).
-int extract_sorted_text(const std::string &seq, int device, char **out_text, size_t *out_len, uint64_t *n_sites)
+// Device buffers are released on every path out of the functions that hold them.
+struct DevBuf {
+    void *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
+};
+
+// ISSL_UPLOAD_TIMING=1: one stderr line per stage of the genome -> index path, the device synchronised at each boundary.
+struct StageClock {
+    bool on = false;
+    double t0 = 0;
+    static double now_ms()
+    {
+        using namespace std::chrono;
+        return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+    }
+    void start() { if (on) t0 = now_ms(); }
+    void note(const char *stage)
+    {
+        if (!on) return;
+        (void)hipDeviceSynchronize();
+        const double t = now_ms();
+        std::fprintf(stderr, "[issl genome] %s %.1f ms\n", stage, t - t0);
+        t0 = t;
+    }
+};
+
+int use_device(int device)
 {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
@@ -233,26 +328,24 @@ int extract_sorted_text(const std::string &seq, int device, char **out_text, siz
         return ISSL_E_ARG;
     }
     EX_HIP_TRY(hipSetDevice(device));
-    *out_text = nullptr;
-    *out_len = 0;
+    return ISSL_OK;
+}
+
+// seq (host) -> sorted site keys in the memory of the current device: keys.p holds *n_sites of them (null when there
+// are none).  Peak: the sequence, then 16 B per site (keys + sort scratch).
+int extract_sorted_keys(const std::string &seq, DevBuf &keys, uint64_t *n_sites, StageClock *clock)
+{
     *n_sites = 0;
     const uint64_t len = seq.size();
-    if (len < 23) {
-        *out_text = static_cast<char *>(std::malloc(1));
-        return ISSL_OK;
-    }
-    // device buffers are released on every path out of this function
-    struct DevBuf {
-        void *p = nullptr;
-        ~DevBuf() { release(); }
-        void release() { if (p) (void)hipFree(p); p = nullptr; }
-    } seq_buf, ctr_buf, keys_buf, tmp_buf, text_buf;
+    if (len < 23) return ISSL_OK;
+    DevBuf seq_buf, ctr_buf, tmp_buf;
     EX_HIP_TRY(hipMalloc(&seq_buf.p, len));
     EX_HIP_TRY(hipMalloc(&ctr_buf.p, 16));
     uint8_t *d_seq = static_cast<uint8_t *>(seq_buf.p);
     unsigned long long *d_ctr = static_cast<unsigned long long *>(ctr_buf.p);
     EX_HIP_TRY(hipMemcpy(d_seq, seq.data(), len, hipMemcpyHostToDevice));
     EX_HIP_TRY(hipMemset(d_ctr, 0, 16));
+    if (clock) clock->note("upload");
     const uint32_t blocks = static_cast<uint32_t>((len + kPosPerBlock - 1) / kPosPerBlock);
     hipLaunchKernelGGL(k_match_count, dim3(blocks), dim3(256), 0, nullptr, d_seq, len, d_ctr);
     unsigned long long total = 0;
@@ -261,19 +354,37 @@ int extract_sorted_text(const std::string &seq, int device, char **out_text, siz
         set_error("more than 2^32 - 1 sites in one extraction (" + std::to_string(total) + "): split the input");
         return ISSL_E_UNSUPPORTED;
     }
+    if (total == 0) return ISSL_OK;
+    EX_HIP_TRY(hipMalloc(&keys.p, 8 * total));
+    EX_HIP_TRY(hipMalloc(&tmp_buf.p, 8 * total));
+    uint64_t *d_keys = static_cast<uint64_t *>(keys.p), *d_tmp = static_cast<uint64_t *>(tmp_buf.p);
+    hipLaunchKernelGGL(k_match_emit, dim3(blocks), dim3(256), 0, nullptr, d_seq, len, d_ctr + 1, d_keys, total);
+    EX_HIP_TRY(hipDeviceSynchronize());
+    seq_buf.release();
+    if (clock) clock->note("match");
+    int rc = radix_sort(d_keys, d_tmp, total, 40);
+    tmp_buf.release();
+    if (rc) return rc;
+    if (clock) clock->note("sort");
+    *n_sites = total;
+    return ISSL_OK;
+}
+
+// seq (host) -> sorted site text (host, malloc'd).
+int extract_sorted_text(const std::string &seq, int device, char **out_text, size_t *out_len, uint64_t *n_sites)
+{
+    if (int rc = use_device(device)) return rc;
+    *out_text = nullptr;
+    *out_len = 0;
+    *n_sites = 0;
+    DevBuf keys_buf, text_buf;
+    uint64_t total = 0;
+    if (int rc = extract_sorted_keys(seq, keys_buf, &total, nullptr)) return rc;
     if (total == 0) {
         *out_text = static_cast<char *>(std::malloc(1));
         return ISSL_OK;
     }
-    EX_HIP_TRY(hipMalloc(&keys_buf.p, 8 * total));
-    EX_HIP_TRY(hipMalloc(&tmp_buf.p, 8 * total));
-    uint64_t *d_keys = static_cast<uint64_t *>(keys_buf.p), *d_tmp = static_cast<uint64_t *>(tmp_buf.p);
-    hipLaunchKernelGGL(k_match_emit, dim3(blocks), dim3(256), 0, nullptr, d_seq, len, d_ctr + 1, d_keys, total);
-    EX_HIP_TRY(hipDeviceSynchronize());
-    seq_buf.release();
-    int rc = radix_sort(d_keys, d_tmp, total, 40);
-    tmp_buf.release();
-    if (rc) return rc;
+    const uint64_t *d_keys = static_cast<const uint64_t *>(keys_buf.p);
     EX_HIP_TRY(hipMalloc(&text_buf.p, 21 * total));
     char *d_text = static_cast<char *>(text_buf.p);
     hipLaunchKernelGGL(k_keys_to_text, dim3(static_cast<uint32_t>((total + 255) / 256)), dim3(256), 0, nullptr, d_keys,
@@ -293,6 +404,86 @@ int extract_sorted_text(const std::string &seq, int device, char **out_text, siz
     *out_len = 21 * total;
     *n_sites = total;
     return ISSL_OK;
+}
+
+// seq (host) -> uploaded index, the site table built and handed over in HBM.  Same result and same errors as
+// extract_sorted_text followed by HostIndex::build_from_text(text, n_sites, 20, slice_width) (the text is sorted, so
+// its runs of equal lines are the runs of equal keys), for the widths the device builder takes (checked by the caller).
+// Peak of the collapse: 8 B per raw site (keys) + 12 B per distinct site; keys are gone before the image build starts.
+int build_index_from_seq(const std::string &seq, size_t slice_width, int device, const char *options, StageClock &clock,
+                         issl_index **out)
+{
+    if (int rc = use_device(device)) return rc;
+    {
+        Tuning probe = Tuning::from_env(); // a typo in the options fails here, not after the extraction
+        if (int rc = probe.set_list(options)) return rc;
+    }
+    DevBuf keys_buf, first_buf, sigs_buf, occ_buf;
+    uint64_t n = 0;
+    if (int rc = extract_sorted_keys(seq, keys_buf, &n, &clock)) return rc;
+    if (n == 0) {
+        set_error("site list is empty");
+        return ISSL_E_ARG;
+    }
+    const uint64_t *d_keys = static_cast<const uint64_t *>(keys_buf.p);
+    const uint32_t n_blocks = static_cast<uint32_t>((n + kRunBlockKeys - 1) / kRunBlockKeys);
+    EX_HIP_TRY(hipMalloc(&first_buf.p, 4 * scan_words(n_blocks + 1ull)));
+    uint32_t *d_first = static_cast<uint32_t *>(first_buf.p);
+    EX_HIP_TRY(hipMemset(d_first + n_blocks, 0, 4));
+    hipLaunchKernelGGL(k_run_heads, dim3(n_blocks), dim3(256), 0, nullptr, d_keys, n, d_first);
+    launch_scan(d_first, n_blocks + 1ull, nullptr);
+    uint32_t n_distinct = 0;
+    EX_HIP_TRY(hipMemcpy(&n_distinct, d_first + n_blocks, 4, hipMemcpyDeviceToHost));
+    if (n_distinct == 0 || n_distinct > n) {
+        set_error("site collapse on the device: " + std::to_string(n_distinct) + " distinct of " + std::to_string(n) + " sites");
+        return ISSL_E_DEVICE;
+    }
+    EX_HIP_TRY(hipMalloc(&sigs_buf.p, 8ull * n_distinct));
+    EX_HIP_TRY(hipMalloc(&occ_buf.p, 4ull * n_distinct));
+    uint64_t *d_sigs = static_cast<uint64_t *>(sigs_buf.p);
+    uint32_t *d_occ = static_cast<uint32_t *>(occ_buf.p);
+    EX_HIP_TRY(hipMemset(d_occ, 0, 4ull * n_distinct));
+    hipLaunchKernelGGL(k_run_sites, dim3(n_blocks), dim3(256), 0, nullptr, d_keys, n, d_first, d_sigs, d_occ);
+    EX_HIP_TRY(hipDeviceSynchronize());
+    keys_buf.release();
+    first_buf.release();
+    clock.note("collapse");
+    issl_index *ix = nullptr;
+    if (int rc = build_from_device_sites(d_sigs, d_occ, n_distinct, n, 20, slice_width, device, options, &ix)) return rc;
+    clock.note("build");
+    *out = ix;
+    return ISSL_OK;
+}
+
+// The FASTA files at paths[0..n) -> seq (extractOfftargets.py:72-88 over every input in turn).
+int read_fasta_files(const char *const *paths, int n, std::string &seq)
+{
+    for (int f = 0; f < n; ++f) {
+        FILE *fp = std::fopen(paths[f], "rb");
+        if (!fp) {
+            set_error(std::string("cannot open '") + paths[f] + "'");
+            return ISSL_E_IO;
+        }
+        std::fseek(fp, 0, SEEK_END);
+        const long sz = std::ftell(fp);
+        std::fseek(fp, 0, SEEK_SET);
+        std::vector<char> buf(sz > 0 ? static_cast<size_t>(sz) : 0);
+        if (sz > 0 && std::fread(buf.data(), buf.size(), 1, fp) < 1) {
+            std::fclose(fp);
+            set_error(std::string("cannot read '") + paths[f] + "'");
+            return ISSL_E_IO;
+        }
+        std::fclose(fp);
+        append_records(buf.data(), buf.size(), seq);
+    }
+    return ISSL_OK;
+}
+
+bool fasta_index_width(size_t slice_width)
+{
+    if (slice_width == 8 || slice_width == 4 || slice_width == 2) return true;
+    set_error("slice width " + std::to_string(slice_width) + " for an index built from FASTA: 8, 4 or 2 bits (the scorer's geometries)");
+    return false;
 }
 
 } // namespace
@@ -324,24 +515,7 @@ int issl_extract_offtargets(const char *const *inputs, int n_inputs, const char 
     }
     return issl::abi_call([&]() -> int {
         std::string seq;
-        for (int f = 0; f < n_inputs; ++f) {
-            FILE *fp = std::fopen(inputs[f], "rb");
-            if (!fp) {
-                issl::set_error(std::string("cannot open '") + inputs[f] + "'");
-                return ISSL_E_IO;
-            }
-            std::fseek(fp, 0, SEEK_END);
-            const long sz = std::ftell(fp);
-            std::fseek(fp, 0, SEEK_SET);
-            std::vector<char> buf(sz > 0 ? static_cast<size_t>(sz) : 0);
-            if (sz > 0 && std::fread(buf.data(), buf.size(), 1, fp) < 1) {
-                std::fclose(fp);
-                issl::set_error(std::string("cannot read '") + inputs[f] + "'");
-                return ISSL_E_IO;
-            }
-            std::fclose(fp);
-            issl::append_records(buf.data(), buf.size(), seq);
-        }
+        if (int rc = issl::read_fasta_files(inputs, n_inputs, seq)) return rc;
         char *text = nullptr;
         size_t len = 0;
         int rc = issl::extract_sorted_text(seq, device, &text, &len, n_sites);
@@ -360,6 +534,42 @@ int issl_extract_offtargets(const char *const *inputs, int n_inputs, const char 
             return ISSL_E_IO;
         }
         return ISSL_OK;
+    });
+}
+
+int issl_index_build_from_fasta(const char *const *files, const size_t *lens, int n_files, size_t slice_width, int device,
+                                const char *options, issl_index **out)
+{
+    if (!issl::fasta_index_width(slice_width)) return ISSL_E_ARG;
+    if (!files || !lens || n_files <= 0 || !out) {
+        issl::set_error("null argument");
+        return ISSL_E_ARG;
+    }
+    return issl::abi_call([&] {
+        issl::StageClock clock{issl::Tuning::from_env().upload_timing};
+        clock.start();
+        std::string seq;
+        for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], seq);
+        clock.note("parse");
+        return issl::build_index_from_seq(seq, slice_width, device, options, clock, out);
+    });
+}
+
+int issl_index_build_from_fasta_files(const char *const *paths, int n_paths, size_t slice_width, int device,
+                                      const char *options, issl_index **out)
+{
+    if (!issl::fasta_index_width(slice_width)) return ISSL_E_ARG;
+    if (!paths || n_paths <= 0 || !out) {
+        issl::set_error("null argument");
+        return ISSL_E_ARG;
+    }
+    return issl::abi_call([&]() -> int {
+        issl::StageClock clock{issl::Tuning::from_env().upload_timing};
+        clock.start();
+        std::string seq;
+        if (int rc = issl::read_fasta_files(paths, n_paths, seq)) return rc;
+        clock.note("parse");
+        return issl::build_index_from_seq(seq, slice_width, device, options, clock, out);
     });
 }
 

@@ -95,6 +95,9 @@ template <class Init> int new_index(Init &&init, issl_index **out)
 // issl_index_build_on_device_opt / _from_device_sites: upload of an index whose slice lists are built on the device.
 int build_on_device(std::unique_ptr<HostIndex> h, const uint64_t *sigs, const uint32_t *occ, bool on_device, int device,
                     const char *options, issl_index **out);
+// issl_index_build_from_device_sites after its argument checks (geometry: seq_len 1..32, slices of 2..8 bits)
+int build_from_device_sites(const uint64_t *d_sigs, const uint32_t *d_occ, size_t n_sites, size_t n_lines, size_t seq_len,
+                            size_t slice_width, int device, const char *options, issl_index **out);
 int upload_common(issl_index *idx, int device, void *buf, size_t bytes);
 int attach_common(int device, void *dev_buf, size_t bytes, void *cold_host, size_t cold_bytes, issl_index **out);
 int planned_image_bytes(const issl_index *idx, size_t *out); // the image the next upload tries first

@@ -1,5 +1,6 @@
 // One stable radix pass of up to 8 bits (digit = key >> shift & mask) over 64-bit keys, shared by the off-target extraction (LSD sort of the site keys,
-// issl_extract.hip) and the device-side index builder (one pass per slice, issl_build.hip).  Included by both; the
+// issl_extract.hip) and the device-side index builder (one pass per slice, issl_build.hip); its exclusive scan also ranks
+// the runs of equal keys when the extraction's keys are collapsed into a site table (issl_extract.hip).  Included by both; the
 // kernels live in an anonymous namespace, one copy per translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -98,23 +99,24 @@ __global__ __launch_bounds__(1024) void k_radix_scan_apply(uint32_t *__restrict_
     }
 }
 
-// Words a histogram buffer needs for n_blocks key blocks: the counters + the chunk sums of their scan.
-inline uint64_t radix_hist_words(uint32_t n_blocks)
-{
-    const uint64_t m = 256ull * n_blocks;
-    return m + (m + kScanChunkWords - 1) / kScanChunkWords + 1;
-}
+// Words a buffer needs for an in-place exclusive scan of m counters: the counters + the chunk sums.
+inline uint64_t scan_words(uint64_t m) { return m + (m + kScanChunkWords - 1) / kScanChunkWords + 1; }
 
-inline void launch_radix_scan(uint32_t *hist, uint32_t n_blocks, hipStream_t stream)
+// Words a histogram buffer needs for n_blocks key blocks.
+inline uint64_t radix_hist_words(uint32_t n_blocks) { return scan_words(256ull * n_blocks); }
+
+// Exclusive scan of data[0..m) in place; data has scan_words(m) words.
+inline void launch_scan(uint32_t *data, uint64_t m, hipStream_t stream)
 {
-    const uint64_t m = 256ull * n_blocks;
     if (m == 0) return;
     const uint32_t chunks = static_cast<uint32_t>((m + kScanChunkWords - 1) / kScanChunkWords);
-    uint32_t *sums = hist + m;
-    hipLaunchKernelGGL(k_radix_scan_sums, dim3(chunks), dim3(1024), 0, stream, hist, m, sums);
+    uint32_t *sums = data + m;
+    hipLaunchKernelGGL(k_radix_scan_sums, dim3(chunks), dim3(1024), 0, stream, data, m, sums);
     hipLaunchKernelGGL(k_radix_scan_top, dim3(1), dim3(1024), 0, stream, sums, chunks);
-    hipLaunchKernelGGL(k_radix_scan_apply, dim3(chunks), dim3(1024), 0, stream, hist, m, sums);
+    hipLaunchKernelGGL(k_radix_scan_apply, dim3(chunks), dim3(1024), 0, stream, data, m, sums);
 }
+
+inline void launch_radix_scan(uint32_t *hist, uint32_t n_blocks, hipStream_t stream) { launch_scan(hist, 256ull * n_blocks, stream); }
 
 // What a pass writes for the key at index i: the key itself (sorting) ...
 struct KeyItself {

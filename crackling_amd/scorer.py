@@ -143,6 +143,28 @@ class IsslIndex:
         return cls(h)
 
     @classmethod
+    def build_from_fasta(cls, inputs, slice_width=8, device=0, options=None):
+        """Genome FASTA -> uploaded index, the site table built on `device` and never in host memory: the handle of
+        build_from_text(extract_offtargets(inputs), 20, slice_width), same bytes, scores and errors.  inputs: a list of
+        bytes blobs (FASTA contents) or of paths (str / os.PathLike).  slice_width: 8, 4 or 2.  options: layout options
+        of the image, e.g. {"compact": 1}."""
+        inputs = list(inputs)
+        h = C.c_void_p()
+        opts = ",".join(f"{k}={v}" for k, v in (options or {}).items()).encode() or None
+        if inputs and all(isinstance(x, (bytes, bytearray, memoryview)) for x in inputs):
+            blobs = [bytes(x) for x in inputs]
+            files = (C.c_char_p * len(blobs))(*blobs)
+            lens = (C.c_size_t * len(blobs))(*[len(b) for b in blobs])
+            check(lib.issl_index_build_from_fasta(files, lens, len(blobs), slice_width, device, opts, C.byref(h)))
+        elif inputs and all(isinstance(x, (str, os.PathLike)) for x in inputs):
+            paths = [os.fsencode(x) for x in inputs]
+            arr = (C.c_char_p * len(paths))(*paths)
+            check(lib.issl_index_build_from_fasta_files(arr, len(paths), slice_width, device, opts, C.byref(h)))
+        else:
+            raise TypeError("inputs: a non-empty list of bytes blobs or of paths")
+        return cls(h)
+
+    @classmethod
     def attach_tensor(cls, tensor):
         """Adopt an HBM image that arrived in a torch uint8 CUDA tensor (e.g. by RCCL broadcast)."""
         h = C.c_void_p()

@@ -144,7 +144,7 @@ int issl_index_build_on_device_opt(const uint64_t *sigs, const uint32_t *occ, si
                                    const char *options, issl_index **out);
 
 /* The same for a site table that is ALREADY in the memory of `device` (d_sigs, d_occ: device pointers; e.g. the sorted,
- * de-duplicated keys issl_extract_* leaves there, or sites generated on the GPU): bucket lengths are counted on the
+ * de-duplicated sites issl_index_build_from_fasta collapses there, or sites generated on the GPU): bucket lengths are counted on the
  * device, nothing of the size of the index ever exists in host memory.  The inputs are copied into the image and may be
  * freed when the call returns.  isslCreateIndex.cpp:199-234 from its state after the counting loop on.  (ABI 5)
  * Checked on the device: no signature carries bits above 2 * seq_len (ISSL_E_ARG).  NOT checked, as in the host-side
@@ -154,6 +154,22 @@ int issl_index_build_on_device_opt(const uint64_t *sigs, const uint32_t *occ, si
 int issl_index_build_from_device_sites(const uint64_t *d_sigs, const uint32_t *d_occ, size_t n_sites,
                                        size_t n_lines, size_t seq_len, size_t slice_width, int device,
                                        const char *options, issl_index **out);
+
+/* Genome FASTA in, uploaded index out, the site table never in host memory: the extraction below (issl_extract_*) sorts
+ * the sites on `device`, the runs of equal sites are collapsed there into signatures and occurrence counts (ids in text
+ * order, n_lines = the raw site count), and those go to issl_index_build_from_device_sites with `options`.  The handle and
+ * its issl_index_write bytes, scores and errors are those of issl_extract_from_memory(files) followed by
+ * issl_index_build_from_text(text, n_lines, 20, slice_width): "site list is empty" (ISSL_E_ARG) for a genome without a
+ * site, ISSL_E_UNSUPPORTED above 2^32 - 1 raw sites, ISSL_E_DEVICE without a device (no CPU fallback).  slice_width must be
+ * 8, 4 or 2 (ISSL_E_ARG before any work otherwise); an unknown option fails once the device is selected, before the
+ * extraction.  Peak HBM: the extraction's 16 B per raw site, then 8 B per raw site + 12 B per distinct site for the
+ * collapse, then the image build with its 12 B per distinct site of inputs.  ISSL_UPLOAD_TIMING=1 prints one stderr line
+ * per stage.  files[i]/lens[i]: the bytes of FASTA / multi-FASTA files. */
+int issl_index_build_from_fasta(const char *const *files, const size_t *lens, int n_files, size_t slice_width,
+                                int device, const char *options, issl_index **out);
+/* Same from files on disk (what bin/isslIndexFromFasta calls). */
+int issl_index_build_from_fasta_files(const char *const *paths, int n_paths, size_t slice_width,
+                                      int device, const char *options, issl_index **out);
 
 /* Write the .issl bytes (isslCreateIndex.cpp:256-289). */
 int issl_index_write(const issl_index *idx, const char *path);

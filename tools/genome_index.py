@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""Genome FASTA -> ready-to-score index on one MI355X, stage by stage, against the two-program chain.
+
+A seeded synthetic genome (generated here, nothing downloaded) of --mbp million bases:
+  uniform  i.i.d. bases;
+  repeat   i.i.d. bases with 10 % of the genome made of mutated copies of 64 interspersed 300-bp elements and one
+           23-mer (N20 + NGG) repeated 200 000 times.
+The fused path (IsslIndex.build_from_fasta, in this process) is timed per stage with ISSL_UPLOAD_TIMING=1, which
+synchronises the device at every boundary: parse (host FASTA pass), upload, match, sort, collapse, build (image), then
+the file write (up to --write-max-mbp); free HBM is sampled every 5 ms for the high-water mark.  The chain (bin/extractOfftargets sites.txt,
+then bin/isslCreateIndex sites.txt 20 W) runs as the two processes a user runs, on the same file, up to --chain-max-mbp;
+its .issl must be byte-identical.  Prints one JSON object per genome size (and writes them to --out)."""
+import argparse
+import filecmp
+import json
+import os
+import pathlib
+import re
+import subprocess
+import sys
+import tempfile
+import threading
+import time
+
+import numpy as np
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def genome(path, mbp, kind, seed, records=24):
+    """Write the FASTA; returns its size in bytes.  Generated 64 Mbp at a time (bounded host memory at any size)."""
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    elements = [acgt[rng.integers(0, 4, size=300, dtype=np.uint8)] for _ in range(64)]
+    unit = np.frombuffer(b"GATTACAGATTACAGATTACCGG", dtype=np.uint8)
+    total = int(mbp * 1e6)
+    per = total // records
+    with open(path, "wb") as fh:
+        for r in range(records):
+            fh.write(b">chr%d synthetic %s seed %d\n" % (r, kind.encode(), seed))
+            left = per
+            while left:
+                n = min(left, 64 << 20)
+                s = acgt[rng.integers(0, 4, size=n, dtype=np.uint8)]
+                if kind == "repeat":
+                    for at in rng.integers(0, max(n - 300, 1), size=n // 3000):   # 10 % of the bases
+                        e = elements[int(rng.integers(0, 64))].copy()
+                        mut = rng.random(300) < 0.02
+                        e[mut] = acgt[rng.integers(0, 4, size=int(mut.sum()), dtype=np.uint8)]
+                        s[at:at + 300] = e[: n - at]
+                    if r == 0 and left == per:
+                        rep = np.tile(unit, min(200_000, n // 23 // 2))
+                        s[: len(rep)] = rep
+                left -= n
+                line = s[: n - n % 60].reshape(-1, 60)
+                fh.write(np.hstack([line, np.full((len(line), 1), 10, np.uint8)]).tobytes())
+                if n % 60:
+                    fh.write(s[n - n % 60:].tobytes() + b"\n")
+    return os.path.getsize(path)
+
+
+class HbmWatch:
+    def __init__(self, torch):
+        self.torch = torch
+
+    def __enter__(self):
+        self.torch.cuda.synchronize()
+        self.before = self.torch.cuda.mem_get_info(0)[0]
+        self.low = self.before
+        self.stop = threading.Event()
+
+        def watch():
+            while not self.stop.is_set():
+                self.low = min(self.low, self.torch.cuda.mem_get_info(0)[0])
+                self.stop.wait(0.005)
+        self.t = threading.Thread(target=watch, daemon=True)
+        self.t.start()
+        return self
+
+    def __exit__(self, *exc):
+        self.stop.set()
+        self.t.join()
+
+    @property
+    def peak(self):
+        return self.before - self.low
+
+
+def stderr_of(fn):
+    """Run fn() with fd 2 redirected to a file; returns (result, captured text)."""
+    with tempfile.TemporaryFile() as tmp:
+        sys.stderr.flush()
+        saved = os.dup(2)
+        os.dup2(tmp.fileno(), 2)
+        try:
+            out = fn()
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        return out, tmp.read().decode(errors="replace")
+
+
+def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout):
+    import torch
+    import crackling_amd as ca
+    fa = work / f"genome_{kind}_{mbp:g}.fa"
+    t = time.perf_counter()
+    fa_bytes = genome(fa, mbp, kind, seed)
+    res = {"genome_mbp": mbp, "kind": kind, "seed": seed, "slice_width": width, "fasta_bytes": fa_bytes,
+           "generate_s": time.perf_counter() - t}
+    os.environ["ISSL_UPLOAD_TIMING"] = "1"   # read when the call starts (Tuning::from_env)
+    with HbmWatch(torch) as hbm:
+        t = time.perf_counter()
+        ix, err = stderr_of(lambda: ca.IsslIndex.build_from_fasta([str(fa)], slice_width=width))
+        fused_s = time.perf_counter() - t
+    os.environ.pop("ISSL_UPLOAD_TIMING")
+    stages = {m.group(1): float(m.group(2)) / 1e3 for m in re.finditer(r"\[issl genome\] (\w+) ([0-9.]+) ms", err)}
+    out = work / "fused.issl"
+    if mbp <= max(write_max_mbp, chain_max_mbp):
+        t = time.perf_counter()
+        ix.write(out)
+        stages["write"] = time.perf_counter() - t
+    hd = ix.header
+    res.update({"raw_sites": hd["n_lines"], "distinct_sites": hd["n_sites"], "image_bytes": ix.device_bytes(),
+                "fused": {"stages_s": stages, "to_resident_handle_s": fused_s, "hbm_high_water_bytes": hbm.peak,
+                          "hbm_high_water_per_raw_site": hbm.peak / max(hd["n_lines"], 1),
+                          "upload_notes": [ln for ln in err.splitlines() if ln.startswith("[issl upload]")]}})
+    ix.close()
+    if mbp <= chain_max_mbp:
+        sites = work / "sites.txt"
+        chain_issl = work / "chain.issl"
+        t = time.perf_counter()
+        subprocess.run([str(ROOT / "bin" / "extractOfftargets"), str(sites), str(fa)], check=True, capture_output=True,
+                       timeout=timeout)
+        t_extract = time.perf_counter() - t
+        t = time.perf_counter()
+        subprocess.run([str(ROOT / "bin" / "isslCreateIndex"), str(sites), "20", str(width), str(chain_issl)], check=True,
+                       capture_output=True, timeout=timeout)
+        t_create = time.perf_counter() - t
+        res["chain"] = {"extractOfftargets_s": t_extract, "isslCreateIndex_s": t_create, "text_bytes": sites.stat().st_size,
+                        "total_s": t_extract + t_create,
+                        "identical_issl": filecmp.cmp(chain_issl, out, shallow=False)}
+        sites.unlink()
+        chain_issl.unlink()
+    else:
+        res["chain"] = f"not run above {chain_max_mbp:g} Mbp (--chain-max-mbp)"
+    out.unlink(missing_ok=True)
+    fa.unlink()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--mbp", type=float, nargs="+", default=[200.0])
+    ap.add_argument("--kind", choices=["uniform", "repeat"], default="repeat")
+    ap.add_argument("--seed", type=int, default=20261016)
+    ap.add_argument("--width", type=int, default=8)
+    ap.add_argument("--chain-max-mbp", type=float, default=1000.0)
+    ap.add_argument("--write-max-mbp", type=float, default=1000.0, help="time the .issl write up to this size (~48 B per site on disk)")
+    ap.add_argument("--timeout", type=float, default=900.0, help="time limit of each chain process (s)")
+    ap.add_argument("--workdir", default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    import crackling_amd as ca
+    torch.cuda.init()
+    torch.zeros(1, device="cuda:0")
+    ca.IsslIndex.build_from_fasta([b">w\n" + b"ACGTTGCAGGTACCAGTAGGCAGG" * 100 + b"\n"]).close()   # runtime + code objects
+    results = []
+    with tempfile.TemporaryDirectory(dir=a.workdir) as tmp:
+        for mbp in a.mbp:
+            r = run(mbp, a.kind, a.seed, a.width, pathlib.Path(tmp), a.chain_max_mbp, a.write_max_mbp, a.timeout)
+            print(json.dumps(r), flush=True)
+            results.append(r)
+    if a.out:
+        pathlib.Path(a.out).write_text(json.dumps({"device": torch.cuda.get_device_name(0), "results": results}, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
