@@ -1,5 +1,5 @@
 # Build of the MI355X ISSL scorer: libissl_hip.so (C ABI, include/issl_hip.h; libissl_hip.map keeps every other symbol
-# out of its dynamic table), the three drop-in executables and isslIndexFromFasta.  hipcc cross-compiles for gfx950 without a GPU present.
+# out of its dynamic table), the three drop-in executables, isslReportOfftargets and isslIndexFromFasta.  hipcc cross-compiles for gfx950 without a GPU present.
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC     = crackling_amd/csrc
@@ -9,7 +9,7 @@ CXXFLAGS = -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result
 HIPFLAGS = $(CXXFLAGS) --offload-arch=$(ARCH)
 LIB      = crackling_amd/libissl_hip.so
 
-all: $(LIB) bin/isslScoreOfftargets bin/isslCreateIndex bin/extractOfftargets bin/isslIndexFromFasta
+all: $(LIB) bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslCreateIndex bin/extractOfftargets bin/isslIndexFromFasta
 
 $(LIB): $(CSRC)/issl_kernels.hip $(CSRC)/issl_extract.hip $(CSRC)/issl_build.hip $(CSRC)/issl_capi.cpp $(CSRC)/issl_upload.cpp $(CSRC)/issl_pipeline.cpp \
         $(CSRC)/issl_options.cpp $(CSRC)/issl_host.cpp $(CSRC)/issl_text.cpp $(CSRC)/issl_index.hpp \
@@ -24,6 +24,11 @@ $(LIB): $(CSRC)/issl_kernels.hip $(CSRC)/issl_extract.hip $(CSRC)/issl_build.hip
 bin/isslScoreOfftargets: $(CSRC)/cli_score.cpp include/issl_hip.h $(LIB)
 	@mkdir -p bin
 	g++ $(CXXFLAGS) -o $@ $< -lpthread -ldl
+
+# the off-target report (records or --profile per guide): host-only as well, the library through dlopen
+bin/isslReportOfftargets: $(CSRC)/cli_report.cpp include/issl_hip.h $(LIB)
+	@mkdir -p bin
+	g++ $(CXXFLAGS) -o $@ $< -ldl
 
 bin/extractOfftargets: $(CSRC)/cli_extract.cpp $(CSRC)/cli_inputs.hpp $(LIB)
 	@mkdir -p bin

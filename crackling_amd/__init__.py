@@ -12,6 +12,8 @@ from .scorer import (  # noqa: F401
     IsslIndex,
     IsslNode,
     METHODS,
+    OFFTARGET_DTYPE,
+    PROFILE_DTYPE,
     encode_guides,
     extract_offtargets,
     decode_guides,
@@ -23,6 +25,6 @@ from .scorer import (  # noqa: F401
 )
 
 __all__ = [
-    "IsslIndex", "IsslNode", "IsslError", "METHODS", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
+    "IsslIndex", "IsslNode", "IsslError", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH",
 ]

@@ -52,6 +52,20 @@ class Hit(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("guide", "slice", "pos", "id", "dist", "occ")]
 
 
+PROFILE_BINS = 7
+
+
+class Offtarget(C.Structure):
+    """issl_offtarget: 40 bytes, no padding."""
+    _fields_ = [("site", C.c_uint64), ("mit", C.c_double), ("cfd", C.c_double), ("guide", C.c_uint32), ("id", C.c_uint32),
+                ("occ", C.c_uint32), ("dist", C.c_uint16), ("slice", C.c_uint16)]
+
+
+class Profile(C.Structure):
+    """issl_profile: 88 bytes."""
+    _fields_ = [("sites", C.c_uint32 * PROFILE_BINS), ("pad", C.c_uint32), ("occurrences", C.c_uint64 * PROFILE_BINS)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_guides", C.c_uint64), ("candidates", C.c_uint64), ("hits", C.c_uint64), ("scan_tiles", C.c_uint64),
@@ -117,6 +131,10 @@ _protos = {
     "issl_score_wait": (C.c_int, [_P, _P]),
     "issl_score_finish": (C.c_int, [_P, _P]),
     "issl_dump_hits": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_offtarget_profile": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
+    "issl_offtarget_profile_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
+    "issl_offtargets": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_offtargets_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "issl_last_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "issl_count_candidates": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "issl_verdicts": (C.c_int, [_P, _P, C.c_size_t, C.c_double, C.c_char_p, _P]),

@@ -364,6 +364,45 @@ int issl_dump_hits(issl_index *idx, const uint64_t *guides, size_t n, int max_di
     return abi_call([&] { return dump_hits(idx, guides, n, max_dist, threshold, method, hits, cap, n_hits); });
 }
 
+// Off-target report: arguments first (without a device), then the state of the handle.
+static int report_args(const issl_index *idx, bool pointers, int max_dist)
+{
+    if (!idx || !pointers) { set_error("null argument"); return ISSL_E_ARG; }
+    if (max_dist < 0 || max_dist >= ISSL_PROFILE_BINS) { set_error("max_dist must lie in 0..6 for the off-target report"); return ISSL_E_ARG; }
+    if (!idx->d_image) { set_error("index has no device image: call issl_index_upload first"); return ISSL_E_STATE; }
+    return ISSL_OK;
+}
+
+int issl_offtarget_profile(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, issl_profile *out)
+{
+    if (int rc = report_args(idx, !n || (guides && out), max_dist)) return rc;
+    if (n == 0) return ISSL_OK;
+    return abi_call([&] { return profile_host(idx, guides, n, max_dist, out); });
+}
+
+int issl_offtarget_profile_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, issl_profile *d_out,
+                                  void *stream)
+{
+    if (int rc = report_args(idx, !n || (d_guides && d_out), max_dist)) return rc;
+    return abi_call([&] { return profile_device(idx, d_guides, n, max_dist, d_out, static_cast<hipStream_t>(stream)); });
+}
+
+int issl_offtargets(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, uint64_t *offsets, issl_offtarget *recs,
+                    size_t cap, size_t *n_total)
+{
+    if (int rc = report_args(idx, offsets && n_total && (!n || guides) && (!cap || recs), max_dist)) return rc;
+    return abi_call([&] { return offtargets_host(idx, guides, n, max_dist, offsets, recs, recs ? cap : 0, n_total); });
+}
+
+int issl_offtargets_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, uint64_t *d_offsets,
+                           issl_offtarget *d_recs, size_t cap, size_t *n_total, void *stream)
+{
+    if (int rc = report_args(idx, d_offsets && n_total && (!n || d_guides) && (!cap || d_recs), max_dist)) return rc;
+    return abi_call([&] {
+        return offtargets_device(idx, d_guides, n, max_dist, d_offsets, d_recs, d_recs ? cap : 0, n_total, static_cast<hipStream_t>(stream));
+    });
+}
+
 int issl_last_stats(const issl_index *idx, issl_stats *out)
 {
     if (!idx || !out) { set_error("null argument"); return ISSL_E_ARG; }

@@ -344,8 +344,12 @@ constexpr uint32_t kSlotHitsWide = 2048; // = kMidHits: what a workspace grows i
 // fills a whole 32-byte sector goes out as it is, where an 8- and a 16-byte piece of two arrays cost two partial ones.
 struct alignas(32) SlotRec {
     double mit, cfd;
-    uint64_t key, pad;
+    uint64_t key, pad; // pad: occurrences | mismatches << 32 (slot_pad) -- what the off-target profile bins
 };
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint64_t slot_pad(uint32_t occ, uint32_t dist) { return static_cast<uint64_t>(occ) | (static_cast<uint64_t>(dist) << 32); }
 constexpr uint32_t kFineWays = 13;      // successor bytes within one mismatch of a guide's: itself + 4 positions x 3 bases
 constexpr uint32_t kFineWays2 = 67;     // ... within two (max_dist 5): + 6 pairs of positions x 9 base pairs
 constexpr uint32_t kFetchPairs = 8;     // time of fetching one 8 KiB tile, in (guide, tile) comparisons of the chip: measured 7
@@ -462,5 +466,14 @@ void launch_group_hits(const Workspace &ws, uint32_t n, void *stream);
 void launch_replay(const ImageView &v, const Workspace &ws, const uint64_t *d_guides, uint32_t n,
                    const ScoreParams &p, double *d_mit, double *d_cfd, uint32_t *d_kept, issl_hit *d_hitrec,
                    void *stream);
+// Off-target report.  launch_profile stands in the replay's place behind launch_group_hits: one issl_profile per guide
+// from its hit slots and, beyond them, its segment of the grouped keys.  launch_report_offsets / _emit follow a batch
+// that ran the replay with d_hitrec (every hit grouped and expanded in scoring order, threshold 0: no early exit):
+// d_offsets[i] = base + goff[i] for i <= n; one issl_offtarget per expanded record, `guide` counted from guide_base.
+void launch_profile(const ImageView &v, const Workspace &ws, const uint64_t *d_guides, uint32_t n, issl_profile *d_out,
+                    void *stream);
+void launch_report_offsets(const Workspace &ws, uint32_t n, uint64_t base, uint64_t *d_offsets, void *stream);
+void launch_report_emit(const ImageView &v, const Workspace &ws, const uint64_t *d_guides, uint32_t n_records,
+                        uint32_t guide_base, issl_offtarget *d_out, void *stream);
 
 } // namespace issl

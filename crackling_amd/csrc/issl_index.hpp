@@ -112,7 +112,7 @@ int ensure_workspace(issl_index *ix, size_t n, Lane &lane, uint32_t fine_ways = 
 int ensure_raw_capacity(Workspace &w, size_t chunks);
 int finish_batches(issl_index *ix, hipStream_t stream);
 int score_core(issl_index *ix, const uint64_t *d_guides, size_t n, int max_dist, double threshold, int method,
-               double *d_mit, double *d_cfd, hipStream_t stream, bool dump);
+               double *d_mit, double *d_cfd, hipStream_t stream, bool dump, issl_profile *d_profile = nullptr);
 int score_async(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, double threshold, int method,
                 double *d_mit, double *d_cfd, hipStream_t stream);
 int wait_batches(issl_index *idx, hipStream_t stream);
@@ -120,5 +120,12 @@ int score_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, 
                double *mit, double *cfd);
 int dump_hits(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, double threshold, int method,
               issl_hit *hits, size_t cap, size_t *n_hits);
+// Off-target report (issl_offtarget_profile*, issl_offtargets*): host batches of any size in issl_score's pieces.
+int profile_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, issl_profile *out);
+int profile_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, issl_profile *d_out, hipStream_t stream);
+int offtargets_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, uint64_t *offsets, issl_offtarget *recs,
+                    size_t cap, size_t *n_total);
+int offtargets_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, uint64_t *d_offsets,
+                      issl_offtarget *d_recs, size_t cap, size_t *n_total, hipStream_t stream);
 
 } // namespace issl

@@ -256,7 +256,7 @@ int ensure_workspace(issl_index *ix, size_t n, Lane &lane, uint32_t fine_ways)
 // bound tail of batch i runs beside the scan of batch i + 1 -- a step then costs max(bin + scan, tail) instead of their sum.
 static int enqueue_batch(issl_index *ix, Lane &lane, hipStream_t stream, const uint64_t *d_guides, size_t n, int max_dist,
                          double threshold, int method, double *d_mit, double *d_cfd, bool dump, bool staged,
-                         int lanes_mode = 1)
+                         int lanes_mode = 1, issl_profile *d_profile = nullptr)
 {
     // lanes_mode 2: the software pipeline described above.  3 ("binning ahead"): two workspaces as well, but only the BINNING
     // of a batch -- seven short, latency-bound launches, 0.19 ms at 100 k guides -- runs beside the batch before it; its scan
@@ -327,8 +327,10 @@ static int enqueue_batch(issl_index *ix, Lane &lane, hipStream_t stream, const u
     if (staged) HIP_TRY(hipEventRecord(lane.ev[3], tail));
     launch_group_hits(ws, n32, tail);
     if (staged) HIP_TRY(hipEventRecord(lane.ev[4], tail));
-    launch_replay(ix->view, ws, d_guides, n32, p, d_mit, d_cfd, dump ? ws.d_kept : nullptr,
-                  dump ? ws.d_hitrec : nullptr, tail);
+    // (the off-target profile: the same batch up to here, its hits binned by distance instead of added up)
+    if (d_profile) launch_profile(ix->view, ws, d_guides, n32, d_profile, tail);
+    else launch_replay(ix->view, ws, d_guides, n32, p, d_mit, d_cfd, dump ? ws.d_kept : nullptr,
+                       dump ? ws.d_hitrec : nullptr, tail);
     if (staged) HIP_TRY(hipEventRecord(lane.ev[5], tail));
     if (pipelined || bin_ahead) HIP_TRY(hipEventRecord(lane.done, tail)); // (what the other lane's batches wait for)
     lane.done_recorded = pipelined || bin_ahead; // (one lane: issl_score_wait records it when somebody asks)
@@ -484,7 +486,7 @@ int finish_batches(issl_index *ix, hipStream_t stream)
 
 // Synchronous batch on the caller's stream.
 int score_core(issl_index *ix, const uint64_t *d_guides, size_t n, int max_dist, double threshold, int method,
-               double *d_mit, double *d_cfd, hipStream_t stream, bool dump)
+               double *d_mit, double *d_cfd, hipStream_t stream, bool dump, issl_profile *d_profile)
 {
     int rc = finish_batches(ix, stream); // anything enqueued asynchronously before
     if (rc) return rc;
@@ -492,7 +494,7 @@ int score_core(issl_index *ix, const uint64_t *d_guides, size_t n, int max_dist,
     ix->stats.n_guides = n;
     if (n == 0) return ISSL_OK;
     for (int attempt = 0;; ++attempt) {
-        rc = enqueue_batch(ix, ix->lane, stream, d_guides, n, max_dist, threshold, method, d_mit, d_cfd, dump, true);
+        rc = enqueue_batch(ix, ix->lane, stream, d_guides, n, max_dist, threshold, method, d_mit, d_cfd, dump, true, 1, d_profile);
         if (rc) return rc;
         rc = finish_batches(ix, stream);
         if (rc == ISSL_OK) {
@@ -507,9 +509,11 @@ int score_core(issl_index *ix, const uint64_t *d_guides, size_t n, int max_dist,
     }
 }
 
-// issl_score: a batch of guides in host memory, in pieces.
-int score_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, double threshold, int method,
-               double *mit, double *cfd)
+// A batch of guides in host memory, in pieces (issl_score, the off-target report): run_piece(at, cnt) puts guides[at, at + cnt)
+// through score_core on the lane's workspace, which is sized for them when it is called; the handle's statistics are
+// the pieces' totals afterwards.
+template <class RunPiece>
+static int for_each_piece(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, RunPiece &&run_piece)
 {
     HIP_TRY(hipSetDevice(idx->device));
     // Crackling hands over pages of up to 5 M guides (config.ini:112); larger batches go through in pieces of at most
@@ -587,25 +591,8 @@ int score_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, 
             rc = ensure_raw_capacity(ws, want_chunks);
             if (rc) return rc;
         }
-        if (ensure_stage(ws, 24 * cnt)) { // guides in, scores out through pinned memory: one DMA each, one synchronisation
-            uint64_t *sg = static_cast<uint64_t *>(ws.h_stage);
-            double *sm = reinterpret_cast<double *>(sg + cnt), *sc = sm + cnt;
-            std::memcpy(sg, guides + at, 8 * cnt);
-            HIP_TRY(hipMemcpyAsync(ws.d_guides, sg, 8 * cnt, hipMemcpyHostToDevice, nullptr));
-            rc = score_core(idx, ws.d_guides, cnt, max_dist, threshold, method, ws.d_mit, ws.d_cfd, nullptr, false);
-            if (rc) return rc;
-            HIP_TRY(hipMemcpyAsync(sm, ws.d_mit, 8 * cnt, hipMemcpyDeviceToHost, nullptr));
-            HIP_TRY(hipMemcpyAsync(sc, ws.d_cfd, 8 * cnt, hipMemcpyDeviceToHost, nullptr));
-            HIP_TRY(hipStreamSynchronize(nullptr));
-            std::memcpy(mit + at, sm, 8 * cnt);
-            std::memcpy(cfd + at, sc, 8 * cnt);
-        } else {
-            HIP_TRY(hipMemcpy(ws.d_guides, guides + at, 8 * cnt, hipMemcpyHostToDevice));
-            rc = score_core(idx, ws.d_guides, cnt, max_dist, threshold, method, ws.d_mit, ws.d_cfd, nullptr, false);
-            if (rc) return rc;
-            HIP_TRY(hipMemcpy(mit + at, ws.d_mit, 8 * cnt, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(cfd + at, ws.d_cfd, 8 * cnt, hipMemcpyDeviceToHost));
-        }
+        rc = run_piece(at, cnt);
+        if (rc) return rc;
         const issl_stats &s = idx->stats;
         // (a piece that went through at once: the next ones within its size and distance need no estimate; denser guides than
         // these still take the grow-and-rerun round)
@@ -626,6 +613,36 @@ int score_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, 
     }
     idx->stats = total;
     return ISSL_OK;
+}
+
+// issl_score: a batch of guides in host memory, in pieces.
+int score_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, double threshold, int method,
+               double *mit, double *cfd)
+{
+    return for_each_piece(idx, guides, n, max_dist, [&](size_t at, size_t cnt) -> int {
+        Workspace &ws = idx->lane.ws;
+        int rc;
+        if (ensure_stage(ws, 24 * cnt)) { // guides in, scores out through pinned memory: one DMA each, one synchronisation
+            uint64_t *sg = static_cast<uint64_t *>(ws.h_stage);
+            double *sm = reinterpret_cast<double *>(sg + cnt), *sc = sm + cnt;
+            std::memcpy(sg, guides + at, 8 * cnt);
+            HIP_TRY(hipMemcpyAsync(ws.d_guides, sg, 8 * cnt, hipMemcpyHostToDevice, nullptr));
+            rc = score_core(idx, ws.d_guides, cnt, max_dist, threshold, method, ws.d_mit, ws.d_cfd, nullptr, false);
+            if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(sm, ws.d_mit, 8 * cnt, hipMemcpyDeviceToHost, nullptr));
+            HIP_TRY(hipMemcpyAsync(sc, ws.d_cfd, 8 * cnt, hipMemcpyDeviceToHost, nullptr));
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            std::memcpy(mit + at, sm, 8 * cnt);
+            std::memcpy(cfd + at, sc, 8 * cnt);
+        } else {
+            HIP_TRY(hipMemcpy(ws.d_guides, guides + at, 8 * cnt, hipMemcpyHostToDevice));
+            rc = score_core(idx, ws.d_guides, cnt, max_dist, threshold, method, ws.d_mit, ws.d_cfd, nullptr, false);
+            if (rc) return rc;
+            HIP_TRY(hipMemcpy(mit + at, ws.d_mit, 8 * cnt, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(cfd + at, ws.d_cfd, 8 * cnt, hipMemcpyDeviceToHost));
+        }
+        return ISSL_OK;
+    });
 }
 
 // issl_dump_hits: every hit of at most 2^22 guides, in guide order.
@@ -654,6 +671,145 @@ int dump_hits(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, d
         }
     }
     *n_hits = total;
+    return ISSL_OK;
+}
+
+// ---- off-target report ------------------------------------------------------------------------
+// A device buffer of the call (the piece's profiles, the piece's records): grown, never shrunk, freed at the end.
+namespace {
+struct CallBuffer {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t want)
+    {
+        if (want <= bytes) return ISSL_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+        HIP_TRY(hipMalloc(&p, want));
+        bytes = want;
+        return ISSL_OK;
+    }
+    ~CallBuffer() { if (p) (void)hipFree(p); }
+};
+} // namespace
+
+// issl_offtarget_profile_device: the scoring pipeline with the profile kernels in the replay's place.  Neither score is
+// asked of k_verify (ISSL_METHOD_UNKNOWN): the distance and the count are all the profile reads.
+int profile_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, issl_profile *d_out, hipStream_t stream)
+{
+    return score_core(idx, d_guides, n, max_dist, 0.0, ISSL_METHOD_UNKNOWN, nullptr, nullptr, stream, false, d_out);
+}
+
+int profile_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, issl_profile *out)
+{
+    CallBuffer prof;
+    return for_each_piece(idx, guides, n, max_dist, [&](size_t at, size_t cnt) -> int {
+        Workspace &ws = idx->lane.ws;
+        int rc = prof.reserve(sizeof(issl_profile) * cnt);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(ws.d_guides, guides + at, 8 * cnt, hipMemcpyHostToDevice));
+        rc = profile_device(idx, ws.d_guides, cnt, max_dist, static_cast<issl_profile *>(prof.p), nullptr);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(out + at, prof.p, sizeof(issl_profile) * cnt, hipMemcpyDeviceToHost));
+        return ISSL_OK;
+    });
+}
+
+// One batch of the record list: every hit grouped and expanded in scoring order by the replay (as issl_dump_hits has
+// them; threshold 0: maximum_sum = +inf, no exit), offsets from the grouping pass's prefix, then -- when the caller has
+// room for them -- the records.  Leaves the batch's number of records in *n_records; synchronises `stream`.
+static int offtargets_batch(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, uint64_t base, size_t guide_base,
+                            uint64_t *d_offsets, issl_offtarget *d_recs, size_t room, uint32_t *n_records, hipStream_t stream)
+{
+    Workspace &ws = idx->lane.ws;
+    int rc = score_core(idx, d_guides, n, max_dist, 0.0, ISSL_METHOD_AND, ws.d_mit, ws.d_cfd, stream, true);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(n_records, ws.goff + n, 4, hipMemcpyDeviceToHost, stream));
+    if (d_offsets) launch_report_offsets(ws, static_cast<uint32_t>(n), base, d_offsets, stream);
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (d_recs && *n_records <= room) {
+        launch_report_emit(idx->view, ws, d_guides, *n_records, static_cast<uint32_t>(guide_base), d_recs, stream);
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    HIP_TRY(hipGetLastError());
+    return ISSL_OK;
+}
+
+int offtargets_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, uint64_t *d_offsets,
+                      issl_offtarget *d_recs, size_t cap, size_t *n_total, hipStream_t stream)
+{
+    HIP_TRY(hipSetDevice(idx->device));
+    *n_total = 0;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return ISSL_OK;
+    }
+    int rc = finish_batches(idx, stream);
+    if (rc) return rc;
+    rc = ensure_workspace(idx, std::min(n, kMaxBatch), idx->lane); // (the replay's score outputs: the workspace's; a batch too large is refused by enqueue_batch)
+    if (rc) return rc;
+    uint32_t records = 0;
+    rc = offtargets_batch(idx, d_guides, n, max_dist, 0, 0, d_offsets, d_recs, cap, &records, stream);
+    if (rc) return rc;
+    *n_total = records;
+    return ISSL_OK;
+}
+
+// issl_offtargets.  The records reach the caller's array only when all of them fit, and that is known once every piece
+// has been counted: a batch of several pieces is counted first (the scoring pipeline, no score asked for: k_verify's
+// per-guide counts are the answer) and listed in a second pass.  Below 2^15 guides for_each_piece never cuts, and the
+// one piece is listed at once.
+int offtargets_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, uint64_t *offsets, issl_offtarget *recs,
+                    size_t cap, size_t *n_total)
+{
+    HIP_TRY(hipSetDevice(idx->device));
+    offsets[0] = 0;
+    *n_total = 0;
+    if (n == 0) return ISSL_OK;
+    const bool one_piece = n < (size_t(1) << 15);
+    uint64_t run = 0;
+    if (!recs || !one_piece) {
+        std::vector<uint32_t> counts;
+        int rc = for_each_piece(idx, guides, n, max_dist, [&](size_t at, size_t cnt) -> int {
+            Workspace &ws = idx->lane.ws;
+            HIP_TRY(hipMemcpy(ws.d_guides, guides + at, 8 * cnt, hipMemcpyHostToDevice));
+            int prc = score_core(idx, ws.d_guides, cnt, max_dist, 0.0, ISSL_METHOD_UNKNOWN, ws.d_mit, ws.d_cfd, nullptr, false);
+            if (prc) return prc;
+            counts.resize(cnt);
+            HIP_TRY(hipMemcpy(counts.data(), ws.gcount, 4 * cnt, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < cnt; ++i) { run += counts[i]; offsets[at + i + 1] = run; }
+            return ISSL_OK;
+        });
+        if (rc) return rc;
+        *n_total = run;
+        if (!recs || run > cap) return ISSL_OK;
+    }
+    CallBuffer out;
+    std::vector<uint32_t> goff;
+    run = 0;
+    bool fits = true;
+    int rc = for_each_piece(idx, guides, n, max_dist, [&](size_t at, size_t cnt) -> int {
+        Workspace &ws = idx->lane.ws;
+        HIP_TRY(hipMemcpy(ws.d_guides, guides + at, 8 * cnt, hipMemcpyHostToDevice));
+        uint32_t records = 0;
+        int prc = offtargets_batch(idx, ws.d_guides, cnt, max_dist, 0, 0, nullptr, nullptr, 0, &records, nullptr);
+        if (prc) return prc;
+        goff.resize(cnt + 1);
+        HIP_TRY(hipMemcpy(goff.data(), ws.goff, 4 * (cnt + 1), hipMemcpyDeviceToHost));
+        for (size_t i = 1; i <= cnt; ++i) offsets[at + i] = run + goff[i];
+        if (run + records > cap) fits = false; // (one piece, not counted before: nothing is written)
+        if (fits && records) {
+            if ((prc = out.reserve(sizeof(issl_offtarget) * size_t(records)))) return prc;
+            launch_report_emit(idx->view, ws, ws.d_guides, records, static_cast<uint32_t>(at), static_cast<issl_offtarget *>(out.p), nullptr);
+            HIP_TRY(hipMemcpy(recs + run, out.p, sizeof(issl_offtarget) * size_t(records), hipMemcpyDeviceToHost));
+        }
+        run += records;
+        return ISSL_OK;
+    });
+    if (rc) return rc;
+    *n_total = run;
     return ISSL_OK;
 }
 

@@ -16,6 +16,10 @@ from . import _lib
 from ._lib import lib, check, IsslError
 
 METHODS = {"unknown": 0, "mit": 1, "cfd": 2, "and": 3, "or": 4, "avg": 5}
+# issl_offtarget (40 bytes) and issl_profile (88 bytes) of include/issl_hip.h
+OFFTARGET_DTYPE = np.dtype([("site", "<u8"), ("mit", "<f8"), ("cfd", "<f8"), ("guide", "<u4"), ("id", "<u4"), ("occ", "<u4"),
+                            ("dist", "<u2"), ("slice", "<u2")])
+PROFILE_DTYPE = np.dtype([("sites", "<u4", (_lib.PROFILE_BINS,)), ("pad", "<u4"), ("occurrences", "<u8", (_lib.PROFILE_BINS,))])
 
 
 def _method_code(method):
@@ -287,6 +291,44 @@ class IsslIndex:
             check(lib.issl_dump_hits(self._h, sigs.ctypes.data, len(sigs), int(max_dist), float(threshold),
                                      _method_code(method), out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    # -- off-target report ---------------------------------------------------------------------
+    def offtarget_profile(self, guides, max_dist=4):
+        """-> (sites uint32[n, 7], occurrences uint64[n, 7]): per guide and distance, the number of off-target sites and
+        the sum of their occurrences (every site within max_dist, no early exit; bins above max_dist are zero)."""
+        sigs = self._sigs(guides)
+        out = np.zeros(len(sigs), dtype=PROFILE_DTYPE)
+        check(lib.issl_offtarget_profile(self._h, sigs.ctypes.data, len(sigs), int(max_dist), out.ctypes.data))
+        return np.ascontiguousarray(out["sites"]), np.ascontiguousarray(out["occurrences"])
+
+    def offtargets(self, guides, max_dist=4):
+        """-> (offsets uint64[n + 1], records): guide i owns records[offsets[i]:offsets[i + 1]], a structured array
+        (OFFTARGET_DTYPE: site, mit, cfd, guide, id, occ, dist, slice) in the reference's scoring order."""
+        sigs = self._sigs(guides)
+        offsets = np.zeros(len(sigs) + 1, dtype=np.uint64)
+        n = C.c_size_t()
+        args = (self._h, sigs.ctypes.data, len(sigs), int(max_dist), offsets.ctypes.data)
+        check(lib.issl_offtargets(*args, None, 0, C.byref(n)))
+        recs = np.empty(n.value, dtype=OFFTARGET_DTYPE)
+        if n.value:
+            check(lib.issl_offtargets(*args, recs.ctypes.data, n.value, C.byref(n)))
+        return offsets, recs
+
+    def offtarget_profile_device(self, d_guides, d_out, max_dist=4, stream=None):
+        """d_guides: torch CUDA tensor of packed signatures; d_out: torch CUDA uint8 tensor of 88 bytes per guide
+        (PROFILE_DTYPE once copied to the host)."""
+        check(lib.issl_offtarget_profile_device(self._h, d_guides.data_ptr(), d_guides.numel(), int(max_dist),
+                                                d_out.data_ptr(), C.c_void_p(stream) if stream else None))
+
+    def offtargets_device(self, d_guides, d_offsets, d_recs, max_dist=4, stream=None):
+        """d_offsets: int64 CUDA tensor of n + 1 words; d_recs: uint8 CUDA tensor (40 bytes per record, OFFTARGET_DTYPE)
+        or None for the counting call.  -> the number of records; nothing is written when they do not fit d_recs."""
+        n = C.c_size_t()
+        cap = d_recs.numel() * d_recs.element_size() // OFFTARGET_DTYPE.itemsize if d_recs is not None else 0
+        check(lib.issl_offtargets_device(self._h, d_guides.data_ptr(), d_guides.numel(), int(max_dist), d_offsets.data_ptr(),
+                                         d_recs.data_ptr() if cap else None, cap, C.byref(n),
+                                         C.c_void_p(stream) if stream else None))
+        return n.value
 
     def stats(self):
         st = _lib.Stats()

@@ -358,6 +358,52 @@ int issl_score_finish(issl_index *idx, void *stream);
 int issl_dump_hits(issl_index *idx, const uint64_t *guides, size_t n, int max_dist,
                    double threshold, int method, issl_hit *hits, size_t cap, size_t *n_hits);
 
+/* ---- off-target report ---------------------------------------------------------------------- */
+/* The off-targets of a guide are the candidates the reference scores at threshold 0 (maximum_sum = +inf, :326: the loops
+ * of :330,344 never leave early): every site within max_dist (0..6), once, under its first matching slice.  Neither
+ * operation takes a threshold or a method.  issl_dump_hits stays the early-exit-faithful parity view. */
+#define ISSL_PROFILE_BINS 7 /* max_dist 0..6 */
+
+/* One off-target with its score terms (40 bytes, no padding).  Records of a guide come in the reference's scoring order
+ * (slice, then position in the bucket): adding a guide's mit (cfd) terms in record order in f64 and applying
+ * 10000 / (100 + sum) gives the scores of issl_score at threshold 0.0, method "and", bit for bit. */
+typedef struct {
+    uint64_t site;  /* the site's packed signature (issl_decode_guide gives the 20-mer) */
+    double mit;     /* addend of :392-396: local score of the mismatch mask x occ; 0.0 when dist == 0 */
+    double cfd;     /* addend of :460: CFD product x occ; 1.0 x occ when dist == 0 */
+    uint32_t guide; /* index into the guide batch */
+    uint32_t id;    /* site id */
+    uint32_t occ;   /* occurrences */
+    uint16_t dist;  /* mismatches */
+    uint16_t slice; /* first matching slice */
+} issl_offtarget;
+
+/* Per guide and distance d <= max_dist: the number of off-target sites and the sum of their occurrences; bins above
+ * max_dist are zero. */
+typedef struct {
+    uint32_t sites[ISSL_PROFILE_BINS];
+    uint32_t pad;
+    uint64_t occurrences[ISSL_PROFILE_BINS];
+} issl_profile;
+
+/* Profiles of n guides in host memory (any n: cut into pieces like issl_score).  Runs the scoring pipeline with the
+ * replay replaced by a kernel that bins every guide's verified hits by distance; no record is materialised.  Blocking. */
+int issl_offtarget_profile(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, issl_profile *out);
+/* Same with guides and profiles in device memory, one batch, on `stream` (may be NULL); returns when it is done. */
+int issl_offtarget_profile_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist,
+                                  issl_profile *d_out, void *stream);
+
+/* Every off-target of n guides as a CSR list: guide i owns recs[offsets[i] .. offsets[i + 1]).  offsets (n + 1 words)
+ * and *n_total are always complete; when *n_total > cap NO record is written and the call still returns ISSL_OK
+ * (recs == NULL with cap == 0 is the counting call).  Any n: the batch is cut into pieces and at most one piece of
+ * records is held on the device.  Blocking. */
+int issl_offtargets(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, uint64_t *offsets,
+                    issl_offtarget *recs, size_t cap, size_t *n_total);
+/* Same with guides, offsets and records in device memory, one batch, on `stream` (may be NULL); *n_total is host memory
+ * and the call returns when the batch is done. */
+int issl_offtargets_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, uint64_t *d_offsets,
+                           issl_offtarget *d_recs, size_t cap, size_t *n_total, void *stream);
+
 int issl_last_stats(const issl_index *idx, issl_stats *out);
 
 /* Sum over guides of the five bucket lengths (SURVEY 8d cross-check), host arithmetic only. */
