@@ -2209,6 +2209,84 @@ __device__ inline double bcast_f64(double x, int lane)
     return __longlong_as_double((static_cast<uint64_t>(hi) << 32) | lo);
 }
 
+// The value lane (l ^ M) holds, for the lane masks the network below uses.  Inside a row of 16 lanes a DPP modifier does
+// it; across rows ds_swizzle (32-lane halves, no address register) or ds_bpermute_b32.
+template <uint32_t M>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t x)
+{
+    const int xi = static_cast<int>(x);
+    if constexpr (M == 1u) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(xi, xi, 0xB1, 0xF, 0xF, false));       // quad_perm:[1,0,3,2]
+    else if constexpr (M == 2u) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(xi, xi, 0x4E, 0xF, 0xF, false));  // quad_perm:[2,3,0,1]
+    else if constexpr (M == 3u) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(xi, xi, 0x1B, 0xF, 0xF, false));  // quad_perm:[3,2,1,0]
+    else if constexpr (M == 7u) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(xi, xi, 0x141, 0xF, 0xF, false)); // row_half_mirror
+    else if constexpr (M == 8u) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(xi, xi, 0x128, 0xF, 0xF, false)); // row_ror:8
+    else if constexpr (M == 15u) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(xi, xi, 0x140, 0xF, 0xF, false)); // row_mirror
+    else if constexpr (M < 32u) return static_cast<uint32_t>(__builtin_amdgcn_ds_swizzle(xi, static_cast<int>(0x1Fu | (M << 10)))); // and 31, or 0, xor M
+    else return static_cast<uint32_t>(__shfl_xor(xi, static_cast<int>(M), 64));
+}
+
+template <uint32_t M>
+__device__ __forceinline__ uint64_t lane_xor64(uint64_t x)
+{
+    return (static_cast<uint64_t>(lane_xor<M>(static_cast<uint32_t>(x >> 32))) << 32) | lane_xor<M>(static_cast<uint32_t>(x));
+}
+
+// One stage of the network below: element e = lane * R + r meets element e ^ X.  The bits of X below R pick the partner's
+// register (resolved when the stage is compiled), the bits above it the partner's lane; the lower of the two elements --
+// bit TOP of e clear -- keeps the smaller word.
+template <uint32_t R, uint32_t X, uint32_t TOP>
+__device__ __forceinline__ void sort_stage(uint64_t (&w)[R], uint32_t lane)
+{
+    constexpr uint32_t RX = X & (R - 1u), LX = X / R;
+    if constexpr (LX == 0u) {
+#pragma unroll
+        for (uint32_t r = 0; r < R; ++r) {
+            if ((r & TOP) == 0u) { // (TOP < R here: the pair is two registers of the lane)
+                const uint64_t a = w[r], b = w[r ^ RX];
+                const bool swap = a > b;
+                w[r] = swap ? b : a;
+                w[r ^ RX] = swap ? a : b;
+            }
+        }
+    } else {
+        const bool low = (lane & (TOP / R)) == 0u;
+        uint64_t other[R];
+#pragma unroll
+        for (uint32_t r = 0; r < R; ++r) other[r] = lane_xor64<LX>(w[r ^ RX]);
+#pragma unroll
+        for (uint32_t r = 0; r < R; ++r) w[r] = ((other[r] < w[r]) == low) ? other[r] : w[r];
+    }
+}
+
+template <uint32_t R, uint32_t K, uint32_t J>
+__device__ __forceinline__ void sort_merge(uint64_t (&w)[R], uint32_t lane)
+{
+    if constexpr (J >= 1u) {
+        sort_stage<R, J, J>(w, lane); // e meets e | J
+        sort_merge<R, K, J / 2u>(w, lane);
+    }
+}
+
+template <uint32_t R, uint32_t K>
+__device__ __forceinline__ void sort_level(uint64_t (&w)[R], uint32_t lane)
+{
+    if constexpr (K <= 64u * R) {
+        sort_stage<R, K - 1u, K / 2u>(w, lane); // e meets e ^ (K - 1): two ascending runs of K / 2 become a bitonic pair of halves
+        sort_merge<R, K, K / 4u>(w, lane);
+        sort_level<R, 2u * K>(w, lane);
+    }
+}
+
+// Ascending sort of the 64 * R distinct words the wave holds in registers, element lane * R + r in w[r] of `lane`: wave_sort's
+// network (every comparator ascending) with the pairs that share a lane exchanged in registers and the others through
+// lane_xor -- no LDS round trip and no index arithmetic per stage.  The words are distinct (a hit's index is in their low
+// bits; padding words differ from every hit's), so a lane and its partner always agree on who keeps which.
+template <uint32_t R>
+__device__ __forceinline__ void wave_sort_regs(uint64_t (&w)[R], uint32_t lane)
+{
+    sort_level<R, 2u>(w, lane);
+}
+
 // Adds the terms of a chunk of cnt <= 64 hits to the running totals in walking order (:394, :460) and applies the exit test
 // of :467-496 after every hit.  `chunk_lds`: the chunk's terms in LDS, {mit, cfd} per hit in walking order, zeros behind the
 // last hit up to a multiple of 8; lane l also holds the terms of hit l (0.0 beyond cnt).  The sums are a serial chain of
@@ -2219,6 +2297,9 @@ __device__ inline double bcast_f64(double x, int lane)
 // side afterwards, and the first lane that passes decides where the walk stops.  (Testing inside the chain costs a
 // compare, a branch and their latencies per hit: ~200 cycles against ~50.)
 // Returns true when the walk stops; `kept` counts the hits that were scored, the totals are those at that point.
+// SPLIT (k_replay): in the first pass the even lanes add up the MIT terms and the odd lanes the CFD terms, 8
+// bytes and ONE addition per lane and hit instead of 16 bytes and two -- each sum is the same chain of additions.
+template <bool SPLIT>
 __device__ __forceinline__ bool accumulate_chunk(double mit_term, double cfd_term, uint32_t cnt, const ScoreParams &p,
                                                  uint32_t lane, double &tot_mit, double &tot_cfd, uint32_t &kept,
                                                  const double2 *chunk_lds)
@@ -2237,12 +2318,23 @@ __device__ __forceinline__ bool accumulate_chunk(double mit_term, double cfd_ter
     // table with a negative entry, or a NaN, takes the careful pass.)
     {
         double tm = tot_mit, tc = tot_cfd;
-        for (uint32_t l0 = 0; l0 < cnt; l0 += 8) {
+        if constexpr (SPLIT) {
+            const double *half_lds = reinterpret_cast<const double *>(chunk_lds) + (lane & 1u);
+            double acc = (lane & 1u) ? tot_cfd : tot_mit;
+            for (uint32_t l0 = 0; l0 < cnt; l0 += 8) {
 #pragma unroll
-            for (uint32_t l = 0; l < 8; ++l) { // x + 0.0 == x: the zeros behind the last hit change nothing
-                const double2 t = chunk_lds[l0 + l];
-                tm += t.x;
-                tc += t.y;
+                for (uint32_t l = 0; l < 8; ++l) acc += half_lds[2u * (l0 + l)];
+            }
+            tm = bcast_f64(acc, 0);
+            tc = bcast_f64(acc, 1);
+        } else {
+            for (uint32_t l0 = 0; l0 < cnt; l0 += 8) {
+#pragma unroll
+                for (uint32_t l = 0; l < 8; ++l) { // x + 0.0 == x: the zeros behind the last hit change nothing
+                    const double2 t = chunk_lds[l0 + l];
+                    tm += t.x;
+                    tc += t.y;
+                }
             }
         }
         const bool grows = __ballot(lane < cnt && !(mit_term >= 0.0 && cfd_term >= 0.0)) == 0ull;
@@ -2354,12 +2446,14 @@ __device__ inline HitTerms hit_terms(const ImageView &v, uint64_t gsig, uint32_t
     return t;
 }
 
-__global__ __launch_bounds__(64, 8) void k_replay(ImageView v, Workspace ws, const uint64_t *__restrict__ guides,
+template <bool DUMP>
+__global__ __launch_bounds__(64, DUMP ? 4 : 8) void k_replay(ImageView v, Workspace ws, const uint64_t *__restrict__ guides,
                                                uint32_t n, ScoreParams p, double *__restrict__ out_mit,
                                                double *__restrict__ out_cfd, uint32_t *__restrict__ out_kept,
-                                               issl_hit *__restrict__ out_hits)
+                                               issl_hit *__restrict__ hits_or_null)
 {
     short_kernel_priority();
+    issl_hit *const out_hits = DUMP ? hits_or_null : nullptr; // (the expanded records cost registers the plain replay does not pay for)
     __shared__ uint64_t keys[kReplayLds];
     __shared__ __attribute__((aligned(16))) double2 ord[64]; // the terms of the chunk being walked, in key order
     const bool calc_mit = p.method == ISSL_METHOD_MIT || p.method == ISSL_METHOD_AND || p.method == ISSL_METHOD_OR ||
@@ -2389,7 +2483,7 @@ __global__ __launch_bounds__(64, 8) void k_replay(ImageView v, Workspace ws, con
 
         // Running totals in key order, same operations as the reference's (:394,:460), early exit of :467-496.
         auto accumulate = [&](double mit_term, double cfd_term, uint32_t cnt) {
-            stop = accumulate_chunk(mit_term, cfd_term, cnt, p, lane, tot_mit, tot_cfd, kept, ord);
+            stop = accumulate_chunk<true>(mit_term, cfd_term, cnt, p, lane, tot_mit, tot_cfd, kept, ord);
         };
 
         // The terms of every hit were computed by k_verify and sit next to the keys (key_of / terms_of above);
@@ -2423,11 +2517,27 @@ __global__ __launch_bounds__(64, 8) void k_replay(ImageView v, Workspace ws, con
             const double2 t = ord[lane];
             accumulate(t.x, t.y, h);
         } else {
-            // (slice, position) of every key with the key's index behind it, sorted in LDS; the terms follow by index
+            // (slice, position) of every key with the key's index behind it, sorted; the terms follow by index
             uint64_t *data = keys;
-            for (uint32_t i = lane; i < h; i += 64) keys[i] = ((key_of(i) & ((1ull << kKeyGuideShift) - 1ull)) << 9) | i; // h <= 512
-            __syncthreads();
-            wave_sort(data, h);
+            auto word_of = [&](uint32_t i) { return ((key_of(i) & ((1ull << kKeyGuideShift) - 1ull)) << 9) | i; }; // h <= 512
+            // Up to 256 hits: sorted in registers (wave_sort_regs), 2 / 4 words per lane, ~0 behind the last hit; the sorted words
+            // go to LDS once, for the chunks below to pick up by position
+            auto sort_in_registers = [&](auto words_per_lane) {
+                constexpr uint32_t R = decltype(words_per_lane)::value;
+                uint64_t w[R];
+#pragma unroll
+                for (uint32_t r = 0; r < R; ++r) w[r] = lane * R + r < h ? word_of(lane * R + r) : ~0ull;
+                wave_sort_regs<R>(w, lane);
+#pragma unroll
+                for (uint32_t r = 0; r < R; ++r) keys[lane * R + r] = w[r];
+            };
+            if (h <= 128u) sort_in_registers(std::integral_constant<uint32_t, 2u>{});
+            else if (h <= 256u) sort_in_registers(std::integral_constant<uint32_t, 4u>{});
+            else { // (eight words per lane spill at the 64 registers that keep eight waves on a SIMD: beyond 256 hits, in LDS)
+                for (uint32_t i = lane; i < h; i += 64) keys[i] = word_of(i);
+                __syncthreads();
+                wave_sort(data, h);
+            }
             __syncthreads();
             for (uint32_t base = 0; base < h && !stop; base += 64) {
                 const uint32_t idx = base + lane;
@@ -2715,7 +2825,7 @@ __global__ __launch_bounds__(256, 6) void k_replay_mid(ImageView v, Workspace ws
                 for (uint32_t base = 0; base < len && !stop; base += 64) {
                     const uint32_t idx = base + lane;
                     const double2 mine2 = idx < len ? tmc[idx] : make_double2(0.0, 0.0);
-                    stop = accumulate_chunk(mine2.x, mine2.y, (len - base < 64u) ? len - base : 64u, p, lane, tot_mit, tot_cfd, kept,
+                    stop = accumulate_chunk<false>(mine2.x, mine2.y, (len - base < 64u) ? len - base : 64u, p, lane, tot_mit, tot_cfd, kept,
                                             tmc + base);
                 }
                 if (lane == 0) { carry_mit = tot_mit; carry_cfd = tot_cfd; carry_kept = kept; stopped_s = stop ? 1u : 0u; }
@@ -2910,7 +3020,7 @@ __global__ __launch_bounds__(THREADS, THREADS < 1024u ? 6 : 4) void k_replay_big
             walk_terms[lane] = make_double2(mit_term, cfd_term);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            stop = accumulate_chunk(mit_term, cfd_term, cnt, p, lane, tot_mit, tot_cfd, kept, walk_terms);
+            stop = accumulate_chunk<false>(mit_term, cfd_term, cnt, p, lane, tot_mit, tot_cfd, kept, walk_terms);
         };
         for (uint32_t s2 = 0; s2 < v.n_slices; ++s2) {
             const uint32_t off = slice_off[s2], len = slice_cnt[s2];
@@ -3074,8 +3184,9 @@ void launch_replay(const ImageView &v, const Workspace &ws, const uint64_t *d_gu
 {
     if (n == 0) return;
     const uint32_t grid = n < 65536u ? n : 65536u;
-    hipLaunchKernelGGL(k_replay, dim3(grid), dim3(64), 0, static_cast<hipStream_t>(stream), v, ws, d_guides, n, p,
-                       d_mit, d_cfd, d_kept, d_hitrec);
+    const auto replay = d_hitrec ? k_replay<true> : k_replay<false>;
+    hipLaunchKernelGGL(replay, dim3(grid), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       v, ws, d_guides, n, p, d_mit, d_cfd, d_kept, d_hitrec);
     if (ws.lean_tail) return; // (predicted: no guide with more than kReplayLds hits; k_replay checks)
     hipLaunchKernelGGL(k_replay_mid, dim3(2048), dim3(256), 0, static_cast<hipStream_t>(stream), v, ws, d_guides, p,
                        d_mit, d_cfd, d_kept, d_hitrec);
