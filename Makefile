@@ -11,13 +11,25 @@ LIB      = crackling_amd/libissl_hip.so
 
 all: $(LIB) bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslCreateIndex bin/extractOfftargets bin/isslIndexFromFasta
 
-$(LIB): $(CSRC)/issl_kernels.hip $(CSRC)/issl_extract.hip $(CSRC)/issl_build.hip $(CSRC)/issl_capi.cpp $(CSRC)/issl_upload.cpp $(CSRC)/issl_pipeline.cpp \
-        $(CSRC)/issl_options.cpp $(CSRC)/issl_host.cpp $(CSRC)/issl_text.cpp $(CSRC)/issl_index.hpp \
-        $(CSRC)/issl_node.cpp $(CSRC)/issl_host.hpp $(CSRC)/issl_device.hpp $(CSRC)/issl_radix.hpp $(CSRC)/cfd_tables.inc include/issl_hip.h \
-        $(CSRC)/libissl_hip.map
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/issl_kernels.hip $(CSRC)/issl_extract.hip $(CSRC)/issl_build.hip $(CSRC)/issl_capi.cpp \
-	    $(CSRC)/issl_upload.cpp $(CSRC)/issl_pipeline.cpp $(CSRC)/issl_options.cpp $(CSRC)/issl_host.cpp $(CSRC)/issl_text.cpp \
-	    $(CSRC)/issl_node.cpp -Wl,--version-script=$(CSRC)/libissl_hip.map -lpthread -ldl
+# The library: one object per source under build/obj/, the same flags for kernels and host code; the header dependencies
+# come from the compiler (-MMD -MP).
+SRCS = issl_kernels.hip issl_bin.hip issl_verify.hip issl_group.hip issl_replay.hip issl_report.hip issl_extract.hip \
+       issl_build.hip issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
+OBJDIR = build/obj
+OBJS   = $(addprefix $(OBJDIR)/,$(addsuffix .o,$(basename $(SRCS))))
+COMPILE = $(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<
+
+$(OBJDIR):
+	mkdir -p $@
+$(OBJDIR)/%.o: $(CSRC)/%.hip | $(OBJDIR)
+	$(COMPILE)
+$(OBJDIR)/%.o: $(CSRC)/%.cpp | $(OBJDIR)
+	$(COMPILE)
+
+$(LIB): $(OBJS) $(CSRC)/libissl_hip.map
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(OBJS) -Wl,--version-script=$(CSRC)/libissl_hip.map -lpthread -ldl
+
+-include $(OBJS:.o=.d)
 
 # host-only executable: libissl_hip.so is loaded with dlopen when the process has to score by itself, not when a resident
 # server answers (cli_score.cpp)
@@ -47,5 +59,5 @@ oracle:
 	$(MAKE) -C oracle all
 
 clean:
-	rm -rf $(LIB) bin
+	rm -rf $(LIB) bin $(OBJDIR)
 .PHONY: all oracle clean

@@ -288,7 +288,7 @@ struct ScanItem {
                          // every register then holds the lane's 16 / 8 candidates two / four times over and a pass
                          // compares two / four guides at once, with masks the wave makes in LDS (short_unit_masks)
     uint32_t gmid;       // pruned scan: the group's class-0 guides (successor byte = the group's own) sit in the slots from
-                         // here on, its class-1 guides (one mismatch there) in front of them (fine_word, issl_kernels.hip)
+                         // here on, its class-1 guides (one mismatch there) in front of them (fine_word, issl_bin.hip)
 };
 static_assert(sizeof(ScanItem) == 48, "scan items are fetched with scalar loads");
 
@@ -444,7 +444,8 @@ struct ScoreParams {
     double maximum_sum; // (10000 - 100*thr)/thr, isslScoreOfftargets.cpp:326
 };
 
-// Launchers (issl_kernels.hip).  All asynchronous on `stream`.
+// Launchers, one stage file each (issl_bin.hip: pack_scan_* and bin_guides; issl_kernels.hip: scan; issl_verify.hip,
+// issl_group.hip, issl_replay.hip; issl_report.hip: profile and report_*).  All asynchronous on `stream`.
 // error_flag bits: 1 = an entry's id lies beyond the site table, 4 = a list holds a site in a bucket its signature does
 // not select, or twice (`seen`: a zeroed bitmap of n_slices * n_sites bits, list-order layouts; null for the sorted
 // ones, whose construction has checked both).

@@ -1,5 +1,5 @@
 // The scoring pipeline: workspaces, the launch of a batch, its completion, and the host-pointer entry points' pieces.
-// Host code; the kernels are in issl_kernels.hip.
+// Host code; the kernels are in the stage files issl_bin.hip ... issl_report.hip (file map: issl_kernels.hip).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>

@@ -1,5 +1,5 @@
 // The HBM image of an index: layout choice, upload (FileUploader's pinned ring for file-mapped indexes), attach of an
-// image made elsewhere.  Host code; the kernels that build the image are in issl_build.hip and issl_kernels.hip.
+// image made elsewhere.  Host code; the kernels that build the image are in issl_build.hip and issl_bin.hip.
 #include <algorithm>
 #include <atomic>
 #include <cerrno>

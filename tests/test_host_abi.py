@@ -166,7 +166,7 @@ def test_cli_argument_and_file_errors(golden_uniform, tmp_path):
 
 
 def test_scan_word_packing_host_model():
-    """Host model of the device packing (issl_kernels.hip scan_word): the fold of two scan words counts exactly
+    """Host model of the device packing (issl_kernels.hpp scan_word): the fold of two scan words counts exactly
     the mismatches outside the bucket's own slice."""
     rng = np.random.default_rng(3)
 

@@ -121,7 +121,7 @@ def test_first_matching_slice_rule_equals_seen_bitmap():
 
 
 def test_successor_slice_pigeonhole_behind_the_pruned_scan():
-    """What the pruned scan of the HIP path rests on (csrc/issl_kernels.hip, k_fine_count): split the <= 4 mismatches of a
+    """What the pruned scan of the HIP path rests on (csrc/issl_bin.hip, k_fine_count): split the <= 4 mismatches of a
     hit over the five slices in every possible way -- some slice matches exactly AND its cyclic successor has at most
     one mismatch (none at all when there are <= 2 mismatches).  The reference scans whole buckets
     (isslScoreOfftargets.cpp:344) and so finds the site in every exactly matching slice; the pruned scan needs one."""

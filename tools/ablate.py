@@ -4,8 +4,8 @@
     python tools/ablate.py build            # here (hipcc cross-compiles): build/ablate/libissl_hip_<name>.so
     python tools/ablate.py run [bench args] # on the GPU box: bench.py once per variant, stage times side by side
 
-A variant is a list of (old, new) text replacements applied to a COPY of csrc/issl_kernels.hip; the results of a cut
-kernel are wrong by construction -- only its duration is read."""
+A variant is a list of (old, new) text replacements, each applied to a COPY of the one kernel source (csrc/issl_*.hip) that
+holds its text; the results of a cut kernel are wrong by construction -- only its duration is read."""
 import json, os, pathlib, subprocess, sys
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 CSRC = ROOT / "crackling_amd" / "csrc"
@@ -81,34 +81,36 @@ VARIANTS = {
                                  "if (in_use && v.srec) { typedef unsigned int v4u __attribute__((ext_vector_type(4))); const v4u q4 = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(v.srec + static_cast<uint64_t>(tile) * kTileCands + offset)); sr_early = *reinterpret_cast<const StreamRec *>(&q4); }")],
     "verify_slot_nontemporal": [("            ws.slots[at] = r;",
                                  "            { typedef unsigned int v4u __attribute__((ext_vector_type(4))); const v4u *r4 = reinterpret_cast<const v4u *>(&r); v4u *d4 = reinterpret_cast<v4u *>(ws.slots + at); __builtin_nontemporal_store(r4[0], d4); __builtin_nontemporal_store(r4[1], d4 + 1); }")],
-    "verify_no_key_store": [("        if (!in_use) continue;\n        recs[t] = key;", "        if (!in_use) continue;\n        if (key != kDeadKey) recs[t] = key;")],
 }
 
 
 def build():
     OUT.mkdir(parents=True, exist_ok=True)
-    src = (CSRC / "issl_kernels.hip").read_text()
     flags = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", f"-I{CSRC}", f"-I{ROOT / 'include'}"]
-    objs = []
-    for f in ("issl_extract.hip", "issl_build.hip", "issl_capi.cpp", "issl_upload.cpp", "issl_pipeline.cpp", "issl_options.cpp",
-              "issl_node.cpp", "issl_host.cpp", "issl_text.cpp"):  # once for all variants
-        o = OUT / (f + ".o")
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", "-o", str(o), str(CSRC / f)])
-        objs.append(str(o))
+    compile_ = lambda src, obj: subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", "-o", str(obj), str(src)])
+    kernels = {f.name: f.read_text() for f in sorted(CSRC.glob("issl_*.hip"))}
+    objs = {}
+    for f in sorted(CSRC.glob("issl_*.hip")) + sorted(CSRC.glob("issl_*.cpp")):  # the library's sources, once for all variants
+        objs[f.name] = OUT / (f.name + ".o")
+        compile_(f, objs[f.name])
     only = os.environ.get("ABLATE_ONLY")
     for name, edits in VARIANTS.items():
         if only and name not in only.split(","):
             continue
-        text = src
-        for old, new in edits:
-            assert text.count(old) == 1, (name, old[:60], text.count(old))
-            text = text.replace(old, new)
-        tmp = OUT / f"issl_kernels_{name}.hip"
-        tmp.write_text(text)
+        text, mine = dict(kernels), dict(objs)
+        for old, new in edits:  # every edit hits ONE place of ONE kernel source
+            counts = {f: t.count(old) for f, t in text.items()}
+            assert sum(counts.values()) == 1, (name, old[:60], counts)
+            f = next(f for f, c in counts.items() if c)
+            text[f] = text[f].replace(old, new)
         print(name, flush=True)
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", "-o", str(OUT / f"k_{name}.o"), str(tmp)])
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-shared", "-o", str(OUT / f"libissl_hip_{name}.so"), str(OUT / f"k_{name}.o")] + objs + ["-lpthread", "-ldl"])
-        tmp.unlink()
+        for f in (f for f in text if text[f] != kernels[f]):
+            tmp = OUT / f"{name}_{f}"
+            tmp.write_text(text[f])
+            mine[f] = OUT / f"{name}_{f}.o"
+            compile_(tmp, mine[f])
+            tmp.unlink()
+        subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-shared", "-o", str(OUT / f"libissl_hip_{name}.so")] + [str(o) for o in mine.values()] + ["-lpthread", "-ldl"])
 
 
 def run(args):
