@@ -295,12 +295,15 @@ __global__ __launch_bounds__(256) void k_plan(ImageView v, uint32_t *__restrict_
     }
 }
 
-// Scatter every guide into its bucket's range of (gword, gidx), once per slice.
+// Scatter every guide into its bucket's range of (gword, gidx, gsig), once per slice.  (gsig: the guide's signature once
+// more, in bucket order -- 8 bytes per pair, so that the two kernels of the pruned plan that walk a bucket's guides read it
+// beside the index instead of behind it: guides[gidx[k]] was a chain of two round trips in each of them.)
 __global__ __launch_bounds__(256) void k_guide_scatter(const uint64_t *__restrict__ guides, uint32_t n,
                                                        uint32_t slice_width, uint32_t n_slices, uint32_t sorted_layout,
                                                        uint32_t n_buckets, const uint32_t *__restrict__ gstart,
                                                        uint32_t *__restrict__ gfill, uint32_t *__restrict__ gword,
                                                        uint32_t *__restrict__ gidx, uint32_t *__restrict__ gbucket,
+                                                       uint64_t *__restrict__ gsig,
                                                        uint32_t guide_blocks, const PlanInfo *__restrict__ plan,
                                                        const ScanItem *__restrict__ items,
                                                        RangeStart *__restrict__ starts)
@@ -347,6 +350,7 @@ __global__ __launch_bounds__(256) void k_guide_scatter(const uint64_t *__restric
                 gword[slot] = image_word(sig, s, slice_width, sorted_layout != 0u);
                 gidx[slot] = g;
                 gbucket[slot] = b;
+                gsig[slot] = sig;
             }
         }
     }
@@ -422,9 +426,9 @@ __host__ __device__ __forceinline__ uint32_t fine_word(uint32_t word, uint32_t s
 
 // Per bucket: guides per successor byte, and what the bucket's groups add to the plan.
 template <uint32_t WAYS>
-__global__ __launch_bounds__(256) void k_fine_count(ImageView v, const uint64_t *__restrict__ guides,
+__global__ __launch_bounds__(256) void k_fine_count(ImageView v, const uint64_t *__restrict__ gsig,
                                                     const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ gfill,
-                                                    const uint32_t *__restrict__ gidx, uint32_t *__restrict__ fcount,
+                                                    uint32_t *__restrict__ fcount,
                                                     uint32_t *__restrict__ fcount0,
                                                     FineSum *__restrict__ fsum, uint32_t item_guides, uint32_t tail_shapes)
 {
@@ -437,8 +441,8 @@ __global__ __launch_bounds__(256) void k_fine_count(ImageView v, const uint64_t 
     cnt0[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t g0 = gstart[b], n = gfill[b];
-    for (uint32_t i = threadIdx.x; i < n; i += 256) { // one guide per thread and step: its loads once, its ways from registers
-        const uint32_t gj = succ_byte(guides[gidx[g0 + i]], slice, v.slice_width);
+    for (uint32_t i = threadIdx.x; i < n; i += 256) { // one guide per thread and step: its load once, its ways from registers
+        const uint32_t gj = succ_byte(gsig[g0 + i], slice, v.slice_width);
         atomicAdd(&cnt0[gj], 1u); // class 0: the guide's successor byte is the group's own (fine_class)
 #pragma unroll
         for (uint32_t way = 0; way < ways; ++way) atomicAdd(&cnt[fine_way(gj, way)], 1u);
@@ -536,126 +540,187 @@ __global__ __launch_bounds__(256) void k_fine_plan(FineSum *__restrict__ fsum, u
     }
 }
 
-// Per bucket: the items of its successor-byte groups and the guides of every group in its slots.
-template <uint32_t WAYS>
-__global__ __launch_bounds__(256) void k_fine_scatter(ImageView v, const uint64_t *__restrict__ guides,
-                                                      const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ gfill,
-                                                      const uint32_t *__restrict__ gword, const uint32_t *__restrict__ gidx,
-                                                      const uint32_t *__restrict__ fcount, const uint32_t *__restrict__ fcount0,
-                                                      const FineSum *__restrict__ fbase,
-                                                      const PlanInfo *__restrict__ plan, uint32_t *__restrict__ fword,
-                                                      FineMeta *__restrict__ fmeta,
-                                                      ScanItem *__restrict__ fitems, uint32_t item_guides, uint32_t tail_shapes)
+// Per bucket: the items of its successor-byte groups and the guides of every group in its slots -- two halves that need
+// nothing from each other but the slot prefix of the bucket's groups, which each makes for itself from fcount: workgroups
+// [0, nb) write the bucket's items, workgroups [nb, 2 nb) place its guides.  (One workgroup per bucket doing one after the
+// other was a serial chain of dependent loads, the guides waiting for the last item.)  THREADS threads each, 512 or 256: with
+// 512 the ~391 guides of a bucket of a 100 k batch are placed in one trip and its ~770 items staged in two; a batch with
+// fewer guides per bucket than 256 takes the smaller workgroup (half the waves to launch for the same work).
+
+// What an item needs to know of its group: worked out once by the group's thread, read from LDS by the items' threads
+// (which found their group by a search, and had two dependent global loads and group_units behind that).
+struct alignas(16) FineGroup {
+    uint64_t cost0, chunk_cost; // cost in front of the group's first item; of a full chunk of item_guides guides
+    uint32_t s0, s1, n_full, units;
+    uint32_t shape, c, slot, slot0; // c guides in the slots from `slot` on, the class-0 ones from `slot0` on
+};
+template <uint32_t THREADS> struct FineItemLds {
+    uint64_t scan[THREADS / 64u];
+    uint32_t item0_of[257];
+    FineGroup group[256];
+    alignas(16) ScanItem stage[THREADS];
+};
+template <uint32_t THREADS> struct FineGuideLds {
+    uint64_t scan[THREADS / 64u];
+    uint32_t slot_of[256], slot0_of[256], cursor[256], cursor0[256], has_cands[256];
+};
+static_assert(sizeof(FineItemLds<512u>) <= 40u * 1024u, "four workgroups of k_fine_scatter per CU");
+
+// (block_exclusive_scan serves the first 256 threads of a larger block too: the other waves add nothing and ignore what they get)
+template <uint32_t THREADS>
+__device__ __forceinline__ void fine_scatter_items(const ImageView &v, uint32_t b, const uint32_t *__restrict__ fcount,
+                                                   const uint32_t *__restrict__ fcount0, const FineSum *__restrict__ fbase,
+                                                   ScanItem *__restrict__ fitems, uint32_t item_guides, uint32_t tail_shapes,
+                                                   FineItemLds<THREADS> &l)
 {
-    constexpr uint32_t ways = WAYS;
-    short_kernel_priority();
-    if (!plan->fine) return; // the bucket-level plan stays
-    __shared__ uint64_t lds[256];
-    __shared__ uint32_t slot_of[256], slot0_of[256], cursor[256], cursor0[256], has_cands[256];
-    const uint32_t b = blockIdx.x, slice = b >> v.slice_width;
     const uint32_t w = threadIdx.x;
-    const uint32_t c = fcount[static_cast<uint64_t>(b) * 256u + w];
-    const uint32_t c1 = c - fcount0[static_cast<uint64_t>(b) * 256u + w]; // class 1 first, class 0 behind it (fine_class)
-    const uint32_t *ss = v.sub_start + static_cast<uint64_t>(b) * 257u;
-    const uint32_t s0 = ss[w], s1 = ss[w + 1];
+    const FineSum base = fbase[b];
+    const uint64_t blen = v.bucket_start[b + 1] - v.bucket_start[b];
+    const uint32_t tile_first_b = v.tile_first[b];
+    uint32_t c = 0, c1 = 0, s0 = 0, s1 = 0;
+    if (w < 256u) {
+        c = fcount[static_cast<uint64_t>(b) * 256u + w];
+        c1 = c - fcount0[static_cast<uint64_t>(b) * 256u + w]; // class 1 first, class 0 behind it (fine_class)
+        const uint32_t *ss = v.sub_start + static_cast<uint64_t>(b) * 257u;
+        s0 = ss[w];
+        s1 = ss[w + 1];
+    }
     uint64_t cost = 0, slots = 0, items = 0;
-    uint32_t kk = 0;
     GroupUnits gu{};
     if (c) { // (fcount is zero where the group has no candidates)
         gu = group_units(s0, s1, tail_shapes);
-        kk = (c + item_guides - 1u) / item_guides;
+        const uint32_t kk = (c + item_guides - 1u) / item_guides;
         slots = (c + kGuideGroup - 1u) / kGuideGroup * kGuideGroup;
-        items = static_cast<uint64_t>(gu.units) * kk;
+        items = static_cast<uint64_t>(gu.units) * kk; // one item per unit and chunk of guides
         for (uint32_t done = 0; done < c; done += item_guides) cost += group_cost(gu, c - done < item_guides ? c - done : item_guides);
     }
-    const FineSum base = fbase[b];
-    uint64_t cost_at = base.cost + block_exclusive_scan(cost, lds, nullptr);
-    const uint32_t slot_at = base.slots + static_cast<uint32_t>(block_exclusive_scan(slots, lds, nullptr));
-    uint32_t item_at = base.items + static_cast<uint32_t>(block_exclusive_scan(items, lds, nullptr));
-    slot_of[w] = slot_at;
-    slot0_of[w] = slot_at + c1;
-    cursor[w] = 0;
-    cursor0[w] = 0;
-    // The bucket's items -- one per unit and chunk of guides, ~770 of 48 bytes -- are written by the whole workgroup, item i by
-    // thread i % 256 into a staging row in LDS and from there in 16-byte pieces that consecutive lanes put side by side: every
-    // group's thread writing its own three items one after the other touched each 64-byte line of the list three times from
-    // different lanes (four times the requests of the bytes moved; the kernel is the largest part of the binning).
-    __shared__ uint32_t item0_of[257], c_of[256];
-    __shared__ uint64_t cost0_of[256];
-    __shared__ __attribute__((aligned(16))) ScanItem stage[256];
-    item0_of[w] = item_at - base.items;
-    if (w == 255u) item0_of[256] = item_at - base.items + static_cast<uint32_t>(items);
-    c_of[w] = c;
-    cost0_of[w] = cost_at;
-    if (c) // padding slots behind the group's guides
-        for (uint32_t k2 = c; k2 < static_cast<uint32_t>(slots); ++k2) { fmeta[slot_at + k2] = FineMeta{kNoGuide, 0u, 0ull}; fword[slot_at + k2] = kPadGuideWord; }
-    has_cands[w] = s1 > s0 ? 1u : 0u;
-    __syncthreads();
-    {
-        const uint32_t total = item0_of[256];
-        const uint64_t blen = v.bucket_start[b + 1] - v.bucket_start[b];
-        const uint32_t tile_first_b = v.tile_first[b];
-        for (uint32_t i0 = 0; i0 < total; i0 += 256u) {
-            const uint32_t i = i0 + w;
-            if (i < total) {
-                uint32_t lo = 0, hi = 256; // the group of item i: the last one whose first item is <= i (groups without items share a start)
-                while (hi - lo > 1u) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (item0_of[mid] <= i) lo = mid; else hi = mid;
-                }
-                const uint32_t gw = lo, gc = c_of[gw];
-                const uint32_t gs0 = ss[gw], gs1 = ss[gw + 1];
-                const GroupUnits g2 = group_units(gs0, gs1, tail_shapes);
-                const uint32_t j = i - item0_of[gw];
-                const uint32_t chunk = j / g2.units, t = j - chunk * g2.units; // single-unit items: chunk after chunk, unit after unit
-                const uint32_t done = chunk * item_guides;
-                const uint32_t len = (gc - done < item_guides) ? gc - done : item_guides;
-                const bool full = t < g2.n_full;
-                const uint32_t shape = full ? 32u : g2.shape, cap = 64u * shape;  // candidates the unit covers
-                const uint32_t wstart = g2.s0a + t * kTileCands;               // position in the bucket (a lane group)
-                const uint64_t after = blen - wstart;                           // candidates of the bucket from there on
-                const uint32_t gslot = slot_of[gw];
-                ScanItem it;
-                it.bucket = (b << 8) | gw;
-                it.g0 = gslot + done; // item_guides is a multiple of 8
-                it.g1 = it.g0 + len;
-                it.n_tiles = 1;
-                // the chunks in front of this one are full ones; the units in front of this one inside its chunk are full units
-                it.cost0 = cost0_of[gw] + static_cast<uint64_t>(chunk) * group_cost(g2, item_guides) +
-                           static_cast<uint64_t>(t) * (static_cast<uint64_t>(len) * kGuideCost + kTileFixedCost);
-                it.tile0 = base.items + i;
-                it.last_cands = after < cap ? static_cast<uint32_t>(after) : cap;
-                it.group_abs = tile_first_b * 64u + (wstart >> 5);
-                it.window = (t == 0 ? gs0 - g2.s0a : 0u) | ((gs1 - wstart < cap ? gs1 - wstart : cap) << 16);
-                it.shape = shape; it.gmid = slot0_of[gw];
-                stage[w] = it;
-            }
-            __syncthreads();
-            const uint32_t n_here = total - i0 < 256u ? total - i0 : 256u;
-            const uint4 *src4 = reinterpret_cast<const uint4 *>(stage);
-            uint4 *dst4 = reinterpret_cast<uint4 *>(fitems + base.items + i0);
-            for (uint32_t q = w; q < n_here * 3u; q += 256u) dst4[q] = src4[q];
-            __syncthreads();
-        }
+    const uint64_t cost_at = base.cost + block_exclusive_scan(cost, l.scan, nullptr);
+    const uint32_t slot_at = base.slots + static_cast<uint32_t>(block_exclusive_scan(slots, l.scan, nullptr));
+    const uint32_t item_at = static_cast<uint32_t>(block_exclusive_scan(items, l.scan, nullptr)); // (inside the bucket)
+    if (w < 256u) {
+        l.item0_of[w] = item_at;
+        if (w == 255u) l.item0_of[256] = item_at + static_cast<uint32_t>(items);
+        FineGroup g;
+        g.cost0 = cost_at; g.chunk_cost = group_cost(gu, item_guides);
+        g.s0 = s0; g.s1 = s1; g.n_full = gu.n_full; g.units = gu.units;
+        g.shape = gu.shape; g.c = c; g.slot = slot_at; g.slot0 = slot_at + c1;
+        l.group[w] = g;
     }
-    // One guide per thread and step: its index, scan word and signature are loaded once (a chain of two round trips),
-    // its 13 (or 1) places come from registers and LDS.  (One (guide, way) pair per thread and step repeated that chain
-    // 13 times over: 0.18 ms at 100 k guides, two thirds of the binning.)
+    __syncthreads();
+    // The bucket's items -- one per unit and chunk of guides, ~770 of 48 bytes -- are written by the whole workgroup, item i by
+    // thread i % THREADS into a staging row in LDS and from there in 16-byte pieces that consecutive lanes put side by side:
+    // every group's thread writing its own three items one after the other touched each 64-byte line of the list three times
+    // from different lanes (four times the requests of the bytes moved).
+    const uint32_t total = l.item0_of[256];
+    for (uint32_t i0 = 0; i0 < total; i0 += THREADS) {
+        const uint32_t i = i0 + w;
+        if (i < total) {
+            uint32_t lo = 0, hi = 256; // the group of item i: the last one whose first item is <= i (groups without items share a start)
+            while (hi - lo > 1u) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (l.item0_of[mid] <= i) lo = mid; else hi = mid;
+            }
+            const uint32_t gw = lo;
+            const FineGroup g = l.group[gw];
+            const uint32_t s0a = g.s0 & ~31u; // (group_units)
+            const uint32_t j = i - l.item0_of[gw];
+            const uint32_t chunk = j / g.units, t = j - chunk * g.units; // single-unit items: chunk after chunk, unit after unit
+            const uint32_t done = chunk * item_guides;
+            const uint32_t len = (g.c - done < item_guides) ? g.c - done : item_guides;
+            const bool full = t < g.n_full;
+            const uint32_t shape = full ? 32u : g.shape, cap = 64u * shape; // candidates the unit covers
+            const uint32_t wstart = s0a + t * kTileCands;                  // position in the bucket (a lane group)
+            const uint64_t after = blen - wstart;                          // candidates of the bucket from there on
+            ScanItem it;
+            it.bucket = (b << 8) | gw;
+            it.g0 = g.slot + done; // item_guides is a multiple of 8
+            it.g1 = it.g0 + len;
+            it.n_tiles = 1;
+            // the chunks in front of this one are full ones; the units in front of this one inside its chunk are full units
+            it.cost0 = g.cost0 + static_cast<uint64_t>(chunk) * g.chunk_cost +
+                       static_cast<uint64_t>(t) * (static_cast<uint64_t>(len) * kGuideCost + kTileFixedCost);
+            it.tile0 = base.items + i;
+            it.last_cands = after < cap ? static_cast<uint32_t>(after) : cap;
+            it.group_abs = tile_first_b * 64u + (wstart >> 5);
+            it.window = (t == 0 ? g.s0 - s0a : 0u) | ((g.s1 - wstart < cap ? g.s1 - wstart : cap) << 16);
+            it.shape = shape; it.gmid = g.slot0;
+            l.stage[w] = it;
+        }
+        __syncthreads();
+        const uint32_t n_here = total - i0 < THREADS ? total - i0 : THREADS;
+        const uint4 *src4 = reinterpret_cast<const uint4 *>(l.stage);
+        uint4 *dst4 = reinterpret_cast<uint4 *>(fitems + base.items + i0);
+        for (uint32_t q = w; q < n_here * 3u; q += THREADS) dst4[q] = src4[q];
+        __syncthreads();
+    }
+}
+
+template <uint32_t WAYS, uint32_t THREADS>
+__device__ __forceinline__ void fine_scatter_guides(const ImageView &v, uint32_t b, const uint32_t *__restrict__ gstart,
+                                                    const uint32_t *__restrict__ gfill, const uint32_t *__restrict__ gword,
+                                                    const uint32_t *__restrict__ gidx, const uint64_t *__restrict__ gsig,
+                                                    const uint32_t *__restrict__ fcount, const uint32_t *__restrict__ fcount0,
+                                                    const FineSum *__restrict__ fbase, uint32_t *__restrict__ fword,
+                                                    FineMeta *__restrict__ fmeta, FineGuideLds<THREADS> &l)
+{
+    constexpr uint32_t ways = WAYS;
+    const uint32_t w = threadIdx.x, slice = b >> v.slice_width;
     const uint32_t g0 = gstart[b], n = gfill[b];
-    for (uint32_t i = threadIdx.x; i < n; i += 256) {
-        const uint32_t guide = gidx[g0 + i], word = gword[g0 + i];
-        const uint64_t gsig = guides[guide];
-        const uint32_t gj = succ_byte(gsig, slice, v.slice_width);
+    const uint32_t base_slots = fbase[b].slots;
+    uint32_t c = 0, c1 = 0;
+    if (w < 256u) {
+        c = fcount[static_cast<uint64_t>(b) * 256u + w];
+        c1 = c - fcount0[static_cast<uint64_t>(b) * 256u + w]; // class 1 first, class 0 behind it (fine_class)
+    }
+    // One guide per thread and step: its index, scan word and signature, side by side in bucket order, are on their way
+    // while the prefix is made; its 13 (or 1) places come from registers and LDS.
+    uint32_t i = w, guide = 0, word = 0;
+    uint64_t sig = 0;
+    if (i < n) { guide = gidx[g0 + i]; word = gword[g0 + i]; sig = gsig[g0 + i]; }
+    const uint32_t slots = (c + kGuideGroup - 1u) / kGuideGroup * kGuideGroup;
+    const uint32_t slot_at = base_slots + static_cast<uint32_t>(block_exclusive_scan(slots, l.scan, nullptr));
+    if (w < 256u) {
+        l.slot_of[w] = slot_at;
+        l.slot0_of[w] = slot_at + c1;
+        l.cursor[w] = 0;
+        l.cursor0[w] = 0;
+        // fcount is zero where the group has no candidates -- and nowhere else among the groups a guide of this bucket
+        // visits: k_fine_count counted these very guides there
+        l.has_cands[w] = c ? 1u : 0u;
+        for (uint32_t k2 = c; k2 < slots; ++k2) { fmeta[slot_at + k2] = FineMeta{kNoGuide, 0u, 0ull}; fword[slot_at + k2] = kPadGuideWord; } // padding slots behind the group's guides
+    }
+    __syncthreads();
+    while (i < n) {
+        const uint32_t gj = succ_byte(sig, slice, v.slice_width);
         const uint32_t word12 = fine_word(word, slice, v.slice_width);
 #pragma unroll
         for (uint32_t way = 0; way < ways; ++way) {
             const uint32_t ww = fine_way(gj, way);
-            if (!has_cands[ww]) continue; // no candidates there: the group has no slots
-            const uint32_t slot = way ? slot_of[ww] + atomicAdd(&cursor[ww], 1u) : slot0_of[ww] + atomicAdd(&cursor0[ww], 1u);
+            if (!l.has_cands[ww]) continue; // no candidates there: the group has no slots
+            const uint32_t slot = way ? l.slot_of[ww] + atomicAdd(&l.cursor[ww], 1u) : l.slot0_of[ww] + atomicAdd(&l.cursor0[ww], 1u);
             fword[slot] = word12 | (fine_class(way) << 24);
-            fmeta[slot] = FineMeta{guide, (b << 8) | ww, gsig};
+            fmeta[slot] = FineMeta{guide, (b << 8) | ww, sig};
         }
+        i += THREADS;
+        if (i < n) { guide = gidx[g0 + i]; word = gword[g0 + i]; sig = gsig[g0 + i]; }
     }
+}
+
+template <uint32_t WAYS, uint32_t THREADS>
+__global__ __launch_bounds__(THREADS) void k_fine_scatter(ImageView v, const uint32_t *__restrict__ gstart,
+                                                          const uint32_t *__restrict__ gfill, const uint32_t *__restrict__ gword,
+                                                          const uint32_t *__restrict__ gidx, const uint64_t *__restrict__ gsig,
+                                                          const uint32_t *__restrict__ fcount, const uint32_t *__restrict__ fcount0,
+                                                          const FineSum *__restrict__ fbase, const PlanInfo *__restrict__ plan,
+                                                          uint32_t *__restrict__ fword, FineMeta *__restrict__ fmeta,
+                                                          ScanItem *__restrict__ fitems, uint32_t item_guides, uint32_t tail_shapes)
+{
+    short_kernel_priority();
+    if (!plan->fine) return; // the bucket-level plan stays
+    __shared__ union { FineItemLds<THREADS> items; FineGuideLds<THREADS> guides; } lds;
+    const uint32_t nb = v.n_buckets;
+    if (blockIdx.x < nb) fine_scatter_items(v, blockIdx.x, fcount, fcount0, fbase, fitems, item_guides, tail_shapes, lds.items);
+    else fine_scatter_guides<WAYS, THREADS>(v, blockIdx.x - nb, gstart, gfill, gword, gidx, gsig, fcount, fcount0, fbase, fword, fmeta, lds.guides);
 }
 
 // Cost ranges of the pruned scan (the bucket-level ones are resolved by k_guide_scatter's last workgroups).
@@ -872,7 +937,7 @@ void launch_bin_guides(const ImageView &v, const Workspace &ws, const Tuning &tn
                        static_cast<uint32_t>(ws.cap_items), ws.plan, tn.item_guides, tn.scan_blocks, ws.counters);
     const uint32_t range_blocks = (tn.scan_blocks + 1u + 255u) / 256u;
     hipLaunchKernelGGL(k_guide_scatter, dim3(blocks + range_blocks), dim3(256), 0, stream, d_guides, n, v.slice_width,
-                       v.n_slices, (v.srec || v.sid) ? 1u : 0u, nb, ws.gstart, ws.gfill, ws.gword, ws.gidx, ws.gbucket, blocks, ws.plan, ws.items,
+                       v.n_slices, (v.srec || v.sid) ? 1u : 0u, nb, ws.gstart, ws.gfill, ws.gword, ws.gidx, ws.gbucket, ws.gsig, blocks, ws.plan, ws.items,
                        ws.range_start);
     if (prune_mode) { // regroup by (bucket, successor byte); k_fine_plan decides which of the two plans the scan follows
         const uint32_t ways = fine_ways_of(prune_mode);
@@ -880,13 +945,18 @@ void launch_bin_guides(const ImageView &v, const Workspace &ws, const Tuning &tn
         const uint32_t tail_shapes = prune_mode == 3 ? 0u : static_cast<uint32_t>(tn.tail_shapes);
         auto launch_fine = [&](auto ways_tag) {
             constexpr uint32_t W = decltype(ways_tag)::value;
-            hipLaunchKernelGGL(k_fine_count<W>, dim3(nb), dim3(256), 0, stream, v, d_guides, ws.gstart, ws.gfill, ws.gidx, ws.fcount,
+            hipLaunchKernelGGL(k_fine_count<W>, dim3(nb), dim3(256), 0, stream, v, ws.gsig, ws.gstart, ws.gfill, ws.fcount,
                                ws.fcount0, ws.fsum, tn.item_guides, tail_shapes);
             hipLaunchKernelGGL(k_fine_plan, dim3(1), dim3(256), 0, stream, ws.fsum, nb, ws.fitems,
                                static_cast<uint32_t>(ws.cap_fitems), static_cast<uint32_t>(ws.cap_fslots), ws.plan, tn.scan_blocks,
                                prune_mode, tn.prune == 1 ? 1u : 0u, ws.sticky, ws.counters);
-            hipLaunchKernelGGL(k_fine_scatter<W>, dim3(nb), dim3(256), 0, stream, v, d_guides, ws.gstart, ws.gfill, ws.gword, ws.gidx,
-                               ws.fcount, ws.fcount0, ws.fsum, ws.plan, ws.fword, ws.fmeta, ws.fitems, tn.item_guides, tail_shapes);
+            // (the workgroup size from the mean bucket: 391 guides at 100 k guides of five slices over 1280 buckets)
+            if (static_cast<uint64_t>(n) * v.n_slices > 256ull * nb)
+                hipLaunchKernelGGL((k_fine_scatter<W, 512u>), dim3(2u * nb), dim3(512), 0, stream, v, ws.gstart, ws.gfill, ws.gword, ws.gidx, ws.gsig,
+                                   ws.fcount, ws.fcount0, ws.fsum, ws.plan, ws.fword, ws.fmeta, ws.fitems, tn.item_guides, tail_shapes);
+            else
+                hipLaunchKernelGGL((k_fine_scatter<W, 256u>), dim3(2u * nb), dim3(256), 0, stream, v, ws.gstart, ws.gfill, ws.gword, ws.gidx, ws.gsig,
+                                   ws.fcount, ws.fcount0, ws.fsum, ws.plan, ws.fword, ws.fmeta, ws.fitems, tn.item_guides, tail_shapes);
         };
         if (ways == 1u) launch_fine(std::integral_constant<uint32_t, 1u>{});
         else if (ways == kFineWays) launch_fine(std::integral_constant<uint32_t, kFineWays>{});

@@ -377,6 +377,7 @@ struct Workspace {
     uint32_t *gword = nullptr;   // scan word of the guide for that slice
     uint32_t *gidx = nullptr;    // guide index, kNoGuide in padding
     uint32_t *gbucket = nullptr; // bucket of the slot (valid where gidx is a guide)
+    uint64_t *gsig = nullptr;    // the guide's packed signature (valid where gidx is a guide): what the pruned plan's kernels read in bucket order
     ScanItem *items = nullptr;   // [max_items+1]
     // pruned scan: the guide arrays and the item list once more, grouped by (bucket, successor byte)
     uint32_t *fword = nullptr;   // scan words of the guides, grouped

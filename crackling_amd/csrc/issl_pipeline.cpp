@@ -40,7 +40,7 @@ int select_device(int device)
 
 static void free_workspace(Workspace &w)
 {
-    void *ptrs[] = {w.ng, w.gfill, w.gstart, w.gword, w.gidx, w.gbucket, w.items, w.plan, w.range_start, w.counters, w.scan_count, w.scan_span, w.sticky, w.stamps, w.gcur_big, w.gcur_big2, w.terms, w.sorted, w.gcount,
+    void *ptrs[] = {w.ng, w.gfill, w.gstart, w.gword, w.gidx, w.gbucket, w.gsig, w.items, w.plan, w.range_start, w.counters, w.scan_count, w.scan_span, w.sticky, w.stamps, w.gcur_big, w.gcur_big2, w.terms, w.sorted, w.gcount,
                     w.goff, w.blocksum, w.d_guides, w.d_mit, w.d_cfd, w.d_kept, w.d_hitrec, w.pay, w.rank, w.fword, w.fmeta,
                     w.fitems, w.fcount, w.fcount0, w.fsum, w.slots};
     for (void *p : ptrs)
@@ -164,6 +164,7 @@ int ensure_workspace(issl_index *ix, size_t n, Lane &lane, uint32_t fine_ways)
         if ((rc = dev_alloc(w.gword, slots))) return rc;
         if ((rc = dev_alloc(w.gidx, slots))) return rc;
         if ((rc = dev_alloc(w.gbucket, slots))) return rc;
+        if ((rc = dev_alloc(w.gsig, slots))) return rc;
         if ((rc = dev_alloc(w.items, items + 1))) return rc;
         if ((rc = dev_alloc(w.gcount, cap + 1))) return rc;
         if ((rc = dev_alloc(w.goff, cap + 1))) return rc;
