@@ -1,5 +1,7 @@
 // Input list of the FASTA-reading executables (bin/extractOfftargets, bin/isslIndexFromFasta): the arguments as given,
-// or, when the one argument is a directory, its non-hidden entries in sorted order (extractOfftargets.py:204-210).
+// or, when the one argument is a directory, its non-hidden entries in sorted order (extractOfftargets.py:201-207).
+// The number of inputs left decides the rules the library reads them by: one -> the reference's explode rules,
+// several -> its per-file rules (issl_extract.hip, append_records).
 #pragma once
 #include <algorithm>
 #include <dirent.h>

@@ -24,8 +24,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <array>
 #include <string>
+#include <string_view>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "issl_host.hpp"
@@ -232,31 +235,92 @@ int radix_sort(uint64_t *d_keys, uint64_t *d_tmp, uint64_t n, uint32_t bits)
     return ISSL_OK;
 }
 
-// FASTA bytes -> upper-cased sequence text with '\n' after every record (extractOfftargets.py:27-61,72-88).
-// Lines [begin, end) of one piece of a file; `begin` is a line start.  A header line closes the record before it.
-static void parse_fasta_lines(const char *fasta, size_t begin, size_t end, std::string &seq)
+// FASTA bytes -> upper-cased sequence text with '\n' after every record.  The reference (extractOfftargets.py) reads
+// its inputs in Python's text mode -- "\n", "\r\n" and a lone "\r" each end a line -- and has two sets of rules:
+//   one input (:209-222, explodeMultiFastaFile :26-62): every line is stripped; a stripped line that starts with '>'
+//     opens a record;
+//   several inputs (processingNode :74-90 on each file as it is): a line is a header when its first raw character is
+//     '>'; other lines lose their trailing blanks only, so leading blanks are sequence text; the records of one file are
+//     keyed by the header line, and a repeated header empties the record before it (:83-85).
+// Where the reference raises on one input -- a blank line (IndexError, :36), sequence before the first header
+// (AttributeError, :56) -- the blank line is skipped and the sequence is a record of its own.
+
+// What str.strip() removes from ASCII text: C's isspace() and the separators FS GS RS US.
+static inline bool py_blank(char c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
+
+// A header line of the per-file rules: its text behind '>' in the file, whether the line has a line end (text mode
+// makes every line end "\n"; the last line of a file may have none, and is then another key), and where its record's
+// sequence starts in the piece's text.
+struct HeaderMark {
+    size_t hdr, hdr_len;
+    bool ended;
+    size_t at;
+};
+
+struct Piece {
+    std::string text;              // explode rules: records closed by '\n'; per-file rules: no separators, see marks
+    std::vector<HeaderMark> marks; // per-file rules only
+};
+
+// Lines [begin, end) of one piece of a file; `begin` is a line start, `end` the end of the file or behind a '\n'.
+static void parse_fasta_lines(const char *fasta, size_t begin, size_t end, bool per_file, Piece &out)
 {
+    std::string &seq = out.text;
     size_t p = begin;
     while (p < end) {
         size_t e = p;
-        while (e < end && fasta[e] != '\n') ++e;
+        while (e < end && fasta[e] != '\n' && fasta[e] != '\r') ++e;
+        size_t next = e < end ? e + 1 : end;
+        if (e + 1 < end && fasta[e] == '\r' && fasta[e + 1] == '\n') ++next;
         size_t a = p, b = e;
-        while (a < b && std::isspace(static_cast<unsigned char>(fasta[a]))) ++a;
-        while (b > a && std::isspace(static_cast<unsigned char>(fasta[b - 1]))) --b;
-        if (b > a && fasta[a] == '>') {
+        if (!per_file)
+            while (a < b && py_blank(fasta[a])) ++a;
+        while (b > a && py_blank(fasta[b - 1])) --b;
+        if (per_file && fasta[p] == '>') {
+            out.marks.push_back({p + 1, e - p - 1, e < end, seq.size()});
+        } else if (!per_file && b > a && fasta[a] == '>') {
             if (seq.empty() || seq.back() != '\n') seq.push_back('\n'); // (a piece's leading separator is settled when it is joined)
         } else {
             for (size_t k = a; k < b; ++k) seq.push_back(static_cast<char>(std::toupper(static_cast<unsigned char>(fasta[k]))));
         }
-        p = e + 1;
+        p = next;
+    }
+}
+
+// Per-file rules: the pieces' records in file order, those dropped whose header line comes again later in the file (in
+// whichever piece), the others appended to seq with a '\n' behind each.  A piece's text ahead of its first header
+// continues the record open at the end of the piece before it.
+static void join_file_records(const char *fasta, const std::vector<Piece> &piece, std::string &seq)
+{
+    struct Span { uint32_t rec; const std::string *text; size_t from, to; };
+    struct Key { std::string_view hdr; bool ended; };
+    std::vector<Span> spans;
+    std::vector<Key> keys(1);  // record 0: the lines before the first header (keyed by the path in the reference)
+    for (const auto &pc : piece) {
+        size_t from = 0;
+        for (const auto &m : pc.marks) {
+            spans.push_back({static_cast<uint32_t>(keys.size() - 1), &pc.text, from, m.at});
+            keys.push_back({std::string_view(fasta + m.hdr, m.hdr_len), m.ended});
+            from = m.at;
+        }
+        spans.push_back({static_cast<uint32_t>(keys.size() - 1), &pc.text, from, pc.text.size()});
+    }
+    std::unordered_map<std::string_view, std::array<uint32_t, 2>> last; // header text -> last record, by `ended`
+    for (uint32_t r = 1; r < keys.size(); ++r) last[keys[r].hdr][keys[r].ended] = r;
+    uint32_t open = 0;
+    for (const auto &sp : spans) {
+        if (sp.from == sp.to || (sp.rec && last[keys[sp.rec].hdr][keys[sp.rec].ended] != sp.rec)) continue;
+        if (sp.rec != open && !seq.empty() && seq.back() != '\n') seq.push_back('\n');
+        open = sp.rec;
+        seq.append(*sp.text, sp.from, sp.to - sp.from);
     }
 }
 
 // The one host pass of the extraction, on up to 16 threads: the file is cut at line starts, every piece is parsed on
 // its own, and the pieces are joined with the sequential rule for record separators (none at the very start, never two
-// in a row), so the result is byte-for-byte what one thread produces.  (One thread manages ~0.3 GB/s: 10 s for a human
-// genome, against ~0.3 s for everything that follows on the GPU.)
-void append_records(const char *fasta, size_t len, std::string &seq)
+// in a row), so the result is byte-for-byte what one thread produces.  per_file: the rules for several inputs.  (One
+// thread manages ~0.3 GB/s: 10 s for a human genome, against ~0.3 s for everything that follows on the GPU.)
+void append_records(const char *fasta, size_t len, bool per_file, std::string &seq)
 {
     const size_t want = std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()), len / (size_t(4) << 20) + 1});
     std::vector<size_t> cut(want + 1, len);
@@ -266,22 +330,26 @@ void append_records(const char *fasta, size_t len, std::string &seq)
         while (at < len && fasta[at] != '\n') ++at;  // the piece starts behind the next line end
         cut[t] = at < len ? at + 1 : len;
     }
-    std::vector<std::string> piece(want);
+    std::vector<Piece> piece(want);
     {
         issl::ThreadGroup pool;
         for (size_t t = 1; t < want; ++t)
-            pool.add([&, t] { piece[t].reserve(cut[t + 1] - cut[t]); parse_fasta_lines(fasta, cut[t], cut[t + 1], piece[t]); });
-        piece[0].reserve(cut[1] - cut[0]);
-        parse_fasta_lines(fasta, cut[0], cut[1], piece[0]);
+            pool.add([&, t] { piece[t].text.reserve(cut[t + 1] - cut[t]); parse_fasta_lines(fasta, cut[t], cut[t + 1], per_file, piece[t]); });
+        piece[0].text.reserve(cut[1] - cut[0]);
+        parse_fasta_lines(fasta, cut[0], cut[1], per_file, piece[0]);
         pool.join();
     }
     size_t total = seq.size() + 1;
-    for (const auto &pc : piece) total += pc.size();
+    for (const auto &pc : piece) total += pc.text.size() + (per_file ? pc.marks.size() : 0);
     seq.reserve(total);
-    for (const auto &pc : piece) {
-        size_t from = 0;
-        if (!pc.empty() && pc[0] == '\n' && (seq.empty() || seq.back() == '\n')) from = 1;
-        seq.append(pc, from, std::string::npos);
+    if (per_file) {
+        join_file_records(fasta, piece, seq);
+    } else {
+        for (const auto &pc : piece) {
+            size_t from = 0;
+            if (!pc.text.empty() && pc.text[0] == '\n' && (seq.empty() || seq.back() == '\n')) from = 1;
+            seq.append(pc.text, from, std::string::npos);
+        }
     }
     if (!seq.empty() && seq.back() != '\n') seq.push_back('\n');
 }
@@ -455,7 +523,7 @@ int build_index_from_seq(const std::string &seq, size_t slice_width, int device,
     return ISSL_OK;
 }
 
-// The FASTA files at paths[0..n) -> seq (extractOfftargets.py:72-88 over every input in turn).
+// The FASTA files at paths[0..n) -> seq: the explode rules for one input, the per-file rules for several.
 int read_fasta_files(const char *const *paths, int n, std::string &seq)
 {
     for (int f = 0; f < n; ++f) {
@@ -474,7 +542,7 @@ int read_fasta_files(const char *const *paths, int n, std::string &seq)
             return ISSL_E_IO;
         }
         std::fclose(fp);
-        append_records(buf.data(), buf.size(), seq);
+        append_records(buf.data(), buf.size(), n > 1, seq);
     }
     return ISSL_OK;
 }
@@ -501,7 +569,7 @@ int issl_extract_from_memory(const char *const *files, const size_t *lens, int n
     }
     return issl::abi_call([&] {
         std::string seq;
-        for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], seq);
+        for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], n_files > 1, seq);
         return issl::extract_sorted_text(seq, device, out_text, out_len, n_sites);
     });
 }
@@ -549,7 +617,7 @@ int issl_index_build_from_fasta(const char *const *files, const size_t *lens, in
         issl::StageClock clock{issl::Tuning::from_env().upload_timing};
         clock.start();
         std::string seq;
-        for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], seq);
+        for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], n_files > 1, seq);
         clock.note("parse");
         return issl::build_index_from_seq(seq, slice_width, device, options, clock, out);
     });

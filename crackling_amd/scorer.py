@@ -410,7 +410,8 @@ class IsslNode:
 
 def extract_offtargets(fasta_blobs, device=0):
     """Sorted site list (bytes, one 20-mer per line) of FASTA / multi-FASTA contents -- the GPU counterpart of
-    crackling/utils/extractOfftargets.py.  fasta_blobs: iterable of bytes."""
+    crackling/utils/extractOfftargets.py.  fasta_blobs: iterable of bytes; one blob is read by the reference's
+    single-file rules, several by its per-file rules ("Index preparation")."""
     blobs = [b if isinstance(b, bytes) else b.encode() for b in fasta_blobs]
     files = (C.c_char_p * len(blobs))(*blobs)
     lens = (C.c_size_t * len(blobs))(*[len(b) for b in blobs])

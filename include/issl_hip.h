@@ -455,7 +455,10 @@ int issl_node_close(issl_node *node);
 /* Counterpart of src/crackling/utils/extractOfftargets.py: every N20 site next to a PAM on either strand
  * (patterns of :23-24, overlapping matches, first 20 characters of the match, reverse-complemented for the
  * reverse pattern), sorted as text, duplicates kept, one per line.  Runs on `device`; no CPU fallback.
- * files[i]/lens[i]: the bytes of FASTA / multi-FASTA files.  *out_text is malloc'd (issl_free). */
+ * files[i]/lens[i]: the bytes of FASTA / multi-FASTA files.  *out_text is malloc'd (issl_free).
+ * n_files == 1: the reference's single-file rules (lines stripped, every record counts); n_files > 1: its per-file
+ * rules ('>' must be the first character of a header line, leading blanks stay in the sequence, a header line that
+ * comes again in the same file replaces the earlier record).  INTEGRATION.md, "Index preparation". */
 int issl_extract_from_memory(const char *const *files, const size_t *lens, int n_files, int device,
                              char **out_text, size_t *out_len, uint64_t *n_sites);
 /* Same from files on disk into `output_path` (what bin/extractOfftargets calls). */

@@ -11,6 +11,7 @@ import pytest
 
 import crackling_amd as ca
 import oracle_util as ou
+from test_extract import CASES, REF_CASES, case_inputs
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 GOLD = ROOT / "tests" / "golden" / "extract"
@@ -154,6 +155,32 @@ def test_fixture_genomes_give_the_chain_bytes(name, width, tmp_path):
             guides = guides_near(sigs, 500, seed=width)
             assert_scores_match(got, tmp_path / "want.issl", guides)
         got.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", REF_CASES)
+def test_input_shapes_give_the_index_of_the_reference_site_list(name, tmp_path):
+    """One input or several, odd line ends, repeated headers, ...: the .issl of the reference script's own sites.txt
+    (tests/golden/extract/cases), from blobs and from paths at every width, from the executable at width 8 (a
+    directory case as the directory)."""
+    blobs, sites_txt, args = case_inputs(name, tmp_path)
+    case = next(c for c in CASES if c["case"] == name)
+    paths = [GOLD / "cases" / name / f for f in case["inputs"] if not (case["as"] == "dir" and f.startswith("."))]
+    for width in WIDTHS:
+        ix = ca.IsslIndex.build_from_text(sites_txt, slice_width=width)
+        ix.write(tmp_path / "want.issl")
+        ix.close()
+        want = (tmp_path / "want.issl").read_bytes()
+        for inputs in (blobs, paths):
+            got, p = fasta_bytes(inputs, width, tmp_path)
+            assert got.header["n_lines"] == case["lines"]
+            got.close()
+            assert p.read_bytes() == want, (width, inputs[0].__class__)
+        if width == 8:
+            out = tmp_path / "cli.issl"
+            r = subprocess.run([str(CLI), str(out), "8"] + args, capture_output=True)
+            assert r.returncode == 0, r.stderr.decode()
+            assert out.read_bytes() == want
 
 
 @pytest.mark.gpu
