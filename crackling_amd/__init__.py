@@ -9,8 +9,10 @@ library raises immediately -- there is no CPU fallback.
 """
 from ._lib import lib, IsslError, LIB_PATH  # noqa: F401
 from .scorer import (  # noqa: F401
+    Genome,
     IsslIndex,
     IsslNode,
+    LOCATION_DTYPE,
     METHODS,
     OFFTARGET_DTYPE,
     PROFILE_DTYPE,
@@ -25,6 +27,6 @@ from .scorer import (  # noqa: F401
 )
 
 __all__ = [
-    "IsslIndex", "IsslNode", "IsslError", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
+    "Genome", "IsslIndex", "IsslNode", "IsslError", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH",
 ]

@@ -66,6 +66,11 @@ class Profile(C.Structure):
     _fields_ = [("sites", C.c_uint32 * PROFILE_BINS), ("pad", C.c_uint32), ("occurrences", C.c_uint64 * PROFILE_BINS)]
 
 
+class Location(C.Structure):
+    """issl_location: 16 bytes, no padding."""
+    _fields_ = [("pos", C.c_uint64), ("record", C.c_uint32), ("strand", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_guides", C.c_uint64), ("candidates", C.c_uint64), ("hits", C.c_uint64), ("scan_tiles", C.c_uint64),
@@ -141,6 +146,13 @@ _protos = {
     "issl_extract_from_memory": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                            C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "issl_extract_offtargets": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "issl_genome_open": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(_P)]),
+    "issl_genome_open_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(_P)]),
+    "issl_genome_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "issl_genome_record": (C.c_int, [_P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "issl_genome_locate": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_genome_locate_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_genome_close": (C.c_int, [_P]),
     "issl_node_create": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "issl_node_score": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P]),
     "issl_node_get_info": (C.c_int, [_P, C.POINTER(NodeInfo)]),

@@ -33,55 +33,12 @@
 
 #include "issl_host.hpp"
 #include "issl_index.hpp"
+#include "issl_match.hpp"
 #include "issl_radix.hpp"
 
 namespace issl {
 
 namespace {
-
-#define EX_HIP_TRY(expr)                                                                           \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr);          \
-            return ISSL_E_DEVICE;                                                                  \
-        }                                                                                          \
-    } while (0)
-
-constexpr uint32_t kPosPerBlock = 4096; // text positions per 256-thread workgroup
-
-// 0..3 for A C G T, 4 for anything else
-__device__ __forceinline__ uint32_t base_code(uint8_t c)
-{
-    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-}
-
-// Matches starting at position i: bit 0 = forward pattern, bit 1 = reverse pattern; keys of the two sites.
-__device__ __forceinline__ uint32_t match_at(const uint8_t *__restrict__ s, uint64_t i, uint64_t len, uint64_t &key_fwd,
-                                             uint64_t &key_rev)
-{
-    if (i + 23 > len) return 0;
-    uint32_t code[23];
-    bool body = true; // characters 1..20 are [ACGT] in both patterns
-#pragma unroll
-    for (int k = 0; k < 23; ++k) code[k] = base_code(s[i + k]);
-#pragma unroll
-    for (int k = 1; k <= 20; ++k) body = body && code[k] < 4u;
-    if (!body) return 0;
-    const bool fwd = code[0] < 3u && (code[21] == 0u || code[21] == 2u) && code[22] == 2u;
-    const bool rev = code[0] == 1u && (code[1] == 1u || code[1] == 3u) && code[21] < 4u &&
-                     (code[22] == 3u || code[22] == 2u || code[22] == 1u);
-    if (!fwd && !rev) return 0;
-    uint64_t kf = 0, kr = 0;
-#pragma unroll
-    for (int p = 0; p < 20; ++p) {
-        kf |= static_cast<uint64_t>(code[p]) << (2 * (19 - p));   // text order: base 0 most significant
-        kr |= static_cast<uint64_t>(3u - code[p]) << (2 * p);      // reverse complement of the same 20 characters
-    }
-    key_fwd = kf;
-    key_rev = kr;
-    return (fwd ? 1u : 0u) | (rev ? 2u : 0u);
-}
 
 __global__ __launch_bounds__(256) void k_match_count(const uint8_t *__restrict__ s, uint64_t len,
                                                      unsigned long long *__restrict__ total)
@@ -210,31 +167,6 @@ __global__ __launch_bounds__(256) void k_run_sites(const uint64_t *__restrict__ 
     }
 }
 
-// Sort d_keys[0..n) ascending on the low `bits` bits; d_tmp has the same size.  Result in d_keys.
-int radix_sort(uint64_t *d_keys, uint64_t *d_tmp, uint64_t n, uint32_t bits)
-{
-    if (n < 2) return ISSL_OK;
-    const uint32_t n_blocks = static_cast<uint32_t>((n + 256ull * kSortItems - 1) / (256ull * kSortItems));
-    uint32_t *d_hist = nullptr;
-    EX_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_hist), 4ull * radix_hist_words(n_blocks)));
-    uint64_t *src = d_keys, *dst = d_tmp;
-    for (uint32_t shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(k_radix_hist, dim3(n_blocks), dim3(256), 0, nullptr, src, n, shift, d_hist, n_blocks, 0xFFu);
-        launch_radix_scan(d_hist, n_blocks, nullptr);
-        hipLaunchKernelGGL(k_radix_scatter<KeyItself>, dim3(n_blocks), dim3(256), 0, nullptr, src, dst, n, shift, d_hist,
-                           n_blocks, KeyItself{}, 0xFFu);
-        std::swap(src, dst);
-    }
-    hipError_t e = hipDeviceSynchronize();
-    (void)hipFree(d_hist);
-    if (e != hipSuccess) {
-        set_error(std::string("HIP error in radix sort: ") + hipGetErrorString(e));
-        return ISSL_E_DEVICE;
-    }
-    if (src != d_keys) EX_HIP_TRY(hipMemcpy(d_keys, src, 8 * n, hipMemcpyDeviceToDevice));
-    return ISSL_OK;
-}
-
 // FASTA bytes -> upper-cased sequence text with '\n' after every record.  The reference (extractOfftargets.py) reads
 // its inputs in Python's text mode -- "\n", "\r\n" and a lone "\r" each end a line -- and has two sets of rules:
 //   one input (:209-222, explodeMultiFastaFile :26-62): every line is stripped; a stripped line that starts with '>'
@@ -248,8 +180,8 @@ int radix_sort(uint64_t *d_keys, uint64_t *d_tmp, uint64_t n, uint32_t bits)
 // What str.strip() removes from ASCII text: C's isspace() and the separators FS GS RS US.
 static inline bool py_blank(char c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
 
-// A header line of the per-file rules: its text behind '>' in the file, whether the line has a line end (text mode
-// makes every line end "\n"; the last line of a file may have none, and is then another key), and where its record's
+// A header line: its text behind '>' in the file, whether the line has a line end (text mode makes every line end
+// "\n"; the last line of a file may have none, and is then another key of the per-file rules), and where its record's
 // sequence starts in the piece's text.
 struct HeaderMark {
     size_t hdr, hdr_len;
@@ -259,7 +191,7 @@ struct HeaderMark {
 
 struct Piece {
     std::string text;              // explode rules: records closed by '\n'; per-file rules: no separators, see marks
-    std::vector<HeaderMark> marks; // per-file rules only
+    std::vector<HeaderMark> marks; // the join of the per-file rules needs them, the record table of either rules
 };
 
 // Lines [begin, end) of one piece of a file; `begin` is a line start, `end` the end of the file or behind a '\n'.
@@ -280,6 +212,7 @@ static void parse_fasta_lines(const char *fasta, size_t begin, size_t end, bool 
             out.marks.push_back({p + 1, e - p - 1, e < end, seq.size()});
         } else if (!per_file && b > a && fasta[a] == '>') {
             if (seq.empty() || seq.back() != '\n') seq.push_back('\n'); // (a piece's leading separator is settled when it is joined)
+            out.marks.push_back({a + 1, e - a - 1, e < end, seq.size()});
         } else {
             for (size_t k = a; k < b; ++k) seq.push_back(static_cast<char>(std::toupper(static_cast<unsigned char>(fasta[k]))));
         }
@@ -289,8 +222,10 @@ static void parse_fasta_lines(const char *fasta, size_t begin, size_t end, bool 
 
 // Per-file rules: the pieces' records in file order, those dropped whose header line comes again later in the file (in
 // whichever piece), the others appended to seq with a '\n' behind each.  A piece's text ahead of its first header
-// continues the record open at the end of the piece before it.
-static void join_file_records(const char *fasta, const std::vector<Piece> &piece, std::string &seq)
+// continues the record open at the end of the piece before it.  records: every record that is not dropped gets an entry
+// when its first span comes by -- a header without sequence too, the lines ahead of the first header only when they
+// hold text.
+static void join_file_records(const char *fasta, const std::vector<Piece> &piece, std::string &seq, std::vector<FastaRecord> *records)
 {
     struct Span { uint32_t rec; const std::string *text; size_t from, to; };
     struct Key { std::string_view hdr; bool ended; };
@@ -308,11 +243,21 @@ static void join_file_records(const char *fasta, const std::vector<Piece> &piece
     std::unordered_map<std::string_view, std::array<uint32_t, 2>> last; // header text -> last record, by `ended`
     for (uint32_t r = 1; r < keys.size(); ++r) last[keys[r].hdr][keys[r].ended] = r;
     uint32_t open = 0;
+    bool listed = false; // the record of the span before this one has its entry
+    uint32_t listed_rec = 0;
     for (const auto &sp : spans) {
-        if (sp.from == sp.to || (sp.rec && last[keys[sp.rec].hdr][keys[sp.rec].ended] != sp.rec)) continue;
+        const bool dropped = sp.rec && last[keys[sp.rec].hdr][keys[sp.rec].ended] != sp.rec;
+        if (records && !dropped && (sp.from != sp.to || sp.rec) && !(listed && listed_rec == sp.rec)) {
+            records->push_back({seq.size(), 0, std::string(keys[sp.rec].hdr)});
+            listed = true;
+            listed_rec = sp.rec;
+        }
+        if (sp.from == sp.to || dropped) continue;
         if (sp.rec != open && !seq.empty() && seq.back() != '\n') seq.push_back('\n');
         open = sp.rec;
+        if (records && records->back().length == 0) records->back().start = seq.size(); // behind its separator
         seq.append(*sp.text, sp.from, sp.to - sp.from);
+        if (records) records->back().length += sp.to - sp.from;
     }
 }
 
@@ -320,7 +265,11 @@ static void join_file_records(const char *fasta, const std::vector<Piece> &piece
 // its own, and the pieces are joined with the sequential rule for record separators (none at the very start, never two
 // in a row), so the result is byte-for-byte what one thread produces.  per_file: the rules for several inputs.  (One
 // thread manages ~0.3 GB/s: 10 s for a human genome, against ~0.3 s for everything that follows on the GPU.)
-void append_records(const char *fasta, size_t len, bool per_file, std::string &seq)
+// records: the table of the records appended, by the same sequential rules (a header's record starts where the text
+// stands once its separator is settled; under the explode rules a record ends one short of the next one's start).
+} // namespace
+
+void append_records(const char *fasta, size_t len, bool per_file, std::string &seq, std::vector<FastaRecord> *records)
 {
     const size_t want = std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()), len / (size_t(4) << 20) + 1});
     std::vector<size_t> cut(want + 1, len);
@@ -342,27 +291,30 @@ void append_records(const char *fasta, size_t len, bool per_file, std::string &s
     size_t total = seq.size() + 1;
     for (const auto &pc : piece) total += pc.text.size() + (per_file ? pc.marks.size() : 0);
     seq.reserve(total);
+    const size_t seq0 = seq.size(), rec0 = records ? records->size() : 0;
     if (per_file) {
-        join_file_records(fasta, piece, seq);
+        join_file_records(fasta, piece, seq, records);
     } else {
         for (const auto &pc : piece) {
             size_t from = 0;
             if (!pc.text.empty() && pc.text[0] == '\n' && (seq.empty() || seq.back() == '\n')) from = 1;
+            if (records)
+                for (const auto &m : pc.marks) records->push_back({seq.size() + m.at - from, 0, std::string(fasta + m.hdr, m.hdr_len)});
             seq.append(pc.text, from, std::string::npos);
         }
     }
     if (!seq.empty() && seq.back() != '\n') seq.push_back('\n');
+    if (records && !per_file) {
+        const uint64_t first = records->size() > rec0 ? (*records)[rec0].start : seq.size();
+        if (first > seq0) records->insert(records->begin() + rec0, FastaRecord{seq0, 0, std::string()}); // text ahead of the first header
+        for (size_t r = rec0; r < records->size(); ++r) {
+            const uint64_t next = r + 1 < records->size() ? (*records)[r + 1].start : seq.size();
+            (*records)[r].length = next > (*records)[r].start ? next - (*records)[r].start - 1 : 0;
+        }
+    }
 }
 
-// Device buffers are released on every path out of the functions that hold them.
-struct DevBuf {
-    void *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
+namespace {
 
 // ISSL_UPLOAD_TIMING=1: one stderr line per stage of the genome -> index path, the device synchronised at each boundary.
 struct StageClock {
@@ -384,6 +336,8 @@ struct StageClock {
     }
 };
 
+} // namespace
+
 int use_device(int device)
 {
     int count = 0;
@@ -398,6 +352,8 @@ int use_device(int device)
     EX_HIP_TRY(hipSetDevice(device));
     return ISSL_OK;
 }
+
+namespace {
 
 // seq (host) -> sorted site keys in the memory of the current device: keys.p holds *n_sites of them (null when there
 // are none).  Peak: the sequence, then 16 B per site (keys + sort scratch).
@@ -523,8 +479,10 @@ int build_index_from_seq(const std::string &seq, size_t slice_width, int device,
     return ISSL_OK;
 }
 
+} // namespace
+
 // The FASTA files at paths[0..n) -> seq: the explode rules for one input, the per-file rules for several.
-int read_fasta_files(const char *const *paths, int n, std::string &seq)
+int read_fasta_files(const char *const *paths, int n, std::string &seq, std::vector<FastaRecord> *records)
 {
     for (int f = 0; f < n; ++f) {
         FILE *fp = std::fopen(paths[f], "rb");
@@ -542,10 +500,12 @@ int read_fasta_files(const char *const *paths, int n, std::string &seq)
             return ISSL_E_IO;
         }
         std::fclose(fp);
-        append_records(buf.data(), buf.size(), n > 1, seq);
+        append_records(buf.data(), buf.size(), n > 1, seq, records);
     }
     return ISSL_OK;
 }
+
+namespace {
 
 bool fasta_index_width(size_t slice_width)
 {

@@ -19,6 +19,7 @@ METHODS = {"unknown": 0, "mit": 1, "cfd": 2, "and": 3, "or": 4, "avg": 5}
 # issl_offtarget (40 bytes) and issl_profile (88 bytes) of include/issl_hip.h
 OFFTARGET_DTYPE = np.dtype([("site", "<u8"), ("mit", "<f8"), ("cfd", "<f8"), ("guide", "<u4"), ("id", "<u4"), ("occ", "<u4"),
                             ("dist", "<u2"), ("slice", "<u2")])
+LOCATION_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("strand", "<u4")])  # issl_location (16 bytes)
 PROFILE_DTYPE = np.dtype([("sites", "<u4", (_lib.PROFILE_BINS,)), ("pad", "<u4"), ("occurrences", "<u8", (_lib.PROFILE_BINS,))])
 
 
@@ -400,6 +401,90 @@ class IsslNode:
         if self._h:
             lib.issl_node_close(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Genome:
+    """A genome resident on the GPU that says where sites lie (issl_genome_* of include/issl_hip.h): the records of the
+    FASTA inputs as the extraction joins them, 1 B per base of HBM.  A location is a match of the extraction: `pos` is
+    its 0-based start inside record `record`; strand 0 is the forward pattern, whose site is seq[pos:pos+20]; strand 1 is
+    the reverse pattern, whose site is the reverse complement of seq[pos:pos+20], the first 20 of the 23 matched
+    characters."""
+
+    def __init__(self, handle):
+        self._h = handle
+        n_rec, n_bases = C.c_uint64(), C.c_uint64()
+        check(lib.issl_genome_info(self._h, C.byref(n_rec), C.byref(n_bases)))
+        self.n_bases = n_bases.value
+        self.records = []
+        name, name_len, length = C.c_void_p(), C.c_size_t(), C.c_uint64()
+        for r in range(n_rec.value):
+            check(lib.issl_genome_record(self._h, r, C.byref(name), C.byref(name_len), C.byref(length)))
+            self.records.append((C.string_at(name, name_len.value) if name_len.value else b"", length.value))
+
+    @classmethod
+    def open(cls, inputs, device=0):
+        """inputs: a list of bytes blobs (FASTA contents) or of paths (str / os.PathLike; a lone directory stands for its
+        non-hidden entries), as for IsslIndex.build_from_fasta: one input is read by the reference's single-file rules,
+        several by its per-file rules."""
+        inputs = list(inputs)
+        h = C.c_void_p()
+        if inputs and all(isinstance(x, (bytes, bytearray, memoryview)) for x in inputs):
+            blobs = [bytes(x) for x in inputs]
+            files = (C.c_char_p * len(blobs))(*blobs)
+            lens = (C.c_size_t * len(blobs))(*[len(b) for b in blobs])
+            check(lib.issl_genome_open(files, lens, len(blobs), device, C.byref(h)))
+        elif inputs and all(isinstance(x, (str, os.PathLike)) for x in inputs):
+            paths = [os.fsencode(x) for x in inputs]
+            arr = (C.c_char_p * len(paths))(*paths)
+            check(lib.issl_genome_open_files(arr, len(paths), device, C.byref(h)))
+        else:
+            raise TypeError("inputs: a non-empty list of bytes blobs or of paths")
+        return cls(h)
+
+    def locate(self, sites):
+        """sites: 20-mer strings or a uint64 array of packed signatures (IsslIndex.offtargets()[1]["site"]).
+        -> (offsets uint64[n + 1], locs): site k owns locs[offsets[k]:offsets[k + 1]], a structured array
+        (LOCATION_DTYPE: pos, record, strand) sorted by (record, pos, strand); a site that does not occur has none."""
+        if isinstance(sites, np.ndarray):
+            sigs = np.ascontiguousarray(sites, dtype=np.uint64)
+        else:
+            sigs = encode_guides(sites)
+        offsets = np.zeros(len(sigs) + 1, dtype=np.uint64)
+        n = C.c_size_t()
+        args = (self._h, sigs.ctypes.data, len(sigs), offsets.ctypes.data)
+        check(lib.issl_genome_locate(*args, None, 0, C.byref(n)))
+        locs = np.empty(n.value, dtype=LOCATION_DTYPE)
+        if n.value:
+            check(lib.issl_genome_locate(*args, locs.ctypes.data, n.value, C.byref(n)))
+        return offsets, locs
+
+    def locate_device(self, d_sites, d_offsets, d_locs, stream=None):
+        """d_sites: int64 CUDA tensor of packed signatures; d_offsets: int64 CUDA tensor of n + 1 words; d_locs: uint8 CUDA
+        tensor (16 bytes per location, LOCATION_DTYPE) or None for the counting call.  -> the number of locations;
+        nothing is written when they do not fit d_locs."""
+        n = C.c_size_t()
+        cap = d_locs.numel() * d_locs.element_size() // LOCATION_DTYPE.itemsize if d_locs is not None else 0
+        check(lib.issl_genome_locate_device(self._h, d_sites.data_ptr(), d_sites.numel(), d_offsets.data_ptr(),
+                                            d_locs.data_ptr() if cap else None, cap, C.byref(n),
+                                            C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def close(self):
+        if self._h:
+            lib.issl_genome_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

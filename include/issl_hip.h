@@ -465,6 +465,54 @@ int issl_extract_from_memory(const char *const *files, const size_t *lens, int n
 int issl_extract_offtargets(const char *const *inputs, int n_inputs, const char *output_path, int device,
                             uint64_t *n_sites);
 
+/* ---- where a site lies in the genome: record, position, strand ----------------------------------------------------- */
+/* The .issl format holds no coordinates.  A genome handle keeps the text the extraction scans -- the records of the
+ * inputs, upper-cased and joined by the rules of the extraction above (n_files == 1: the single-file rules, n_files > 1:
+ * the per-file rules) -- resident in the memory of `device` at 1 B per base, with the table of record starts, and
+ * answers where given sites occur.
+ *   location  a match of the extraction: a start i in a record's sequence where the forward pattern (strand 0) or the
+ *             reverse pattern (strand 1) of extractOfftargets.py:23-24 matches -- exactly the matches the extraction turns
+ *             into site lines.  The site of a forward match is seq[i:i+20].  The site of a reverse match is the reverse
+ *             complement of seq[i:i+20], the FIRST 20 OF THE 23 matched characters (the reference's rule,
+ *             extractOfftargets.py:97-110) -- not the 20 characters behind the reverse PAM, so do not expect the
+ *             protospacer's own span there.  One start can match both patterns: two locations, two sites
+ *   pos       = i, 0-based inside the record, counted in the record's sequence as the extraction builds it: with one
+ *             input lines are stripped and joined (the usual FASTA coordinate); with several inputs the per-file rules
+ *             apply and the leading blanks that count as sequence there are counted too
+ *   record    index among the surviving records in the order the extraction joins them.  A record dropped by the
+ *             repeated-header rule has no index; a header without sequence is a record of length 0; text before the
+ *             first header is a record with an empty name.  name = the header line without '>' and without its line
+ *             end, as the bytes stand in the file (issl_genome_record; valid until the handle is closed, not terminated)
+ *   sites     packed signatures, as in issl_offtarget.site and issl_encode_guides
+ * Site k of the call owns locs[offsets[k] .. offsets[k + 1]), sorted by (record, pos, strand).  A site that does not
+ * occur has an empty range; a site named twice gets the same list twice.  offsets (n + 1 words) and *n_total are always
+ * complete; when *n_total > cap NO location is written and the call still returns ISSL_OK (locs == NULL with cap == 0 is
+ * the counting call) -- the rules of issl_offtargets.  The output is deterministic: the same bytes on every run.  Any n:
+ * the query is cut into pieces of 2^22 sites, each of which scans the text once.  More than 2^32 - 1 locations in one
+ * call: ISSL_E_UNSUPPORTED, as the extraction refuses.  No device: ISSL_E_DEVICE (no CPU fallback); NULL arguments and
+ * n_files <= 0: ISSL_E_ARG; *out is NULL after a failed open.  ISSL_LOCATE_TIMING=1 (read when the handle is made) prints
+ * one stderr line per call with the stage times and the counters of the scan.  One handle is used by one thread at a time. */
+typedef struct issl_genome issl_genome; /* opaque */
+typedef struct {
+    uint64_t pos;    /* 0-based start of the match inside the record */
+    uint32_t record; /* index of the record */
+    uint32_t strand; /* 0: forward pattern, 1: reverse pattern */
+} issl_location;     /* 16 bytes, no padding */
+
+int issl_genome_open(const char *const *files, const size_t *lens, int n_files, int device, issl_genome **out);
+/* Same from files on disk; a lone directory stands for its non-hidden entries in sorted order, as for bin/extractOfftargets. */
+int issl_genome_open_files(const char *const *paths, int n_paths, int device, issl_genome **out);
+int issl_genome_info(const issl_genome *g, uint64_t *n_records, uint64_t *n_bases);
+int issl_genome_record(const issl_genome *g, uint64_t r, const char **name, size_t *name_len, uint64_t *length);
+/* Sites, offsets and locations in host memory.  Blocking. */
+int issl_genome_locate(issl_genome *g, const uint64_t *sites, size_t n, uint64_t *offsets, issl_location *locs, size_t cap,
+                       size_t *n_total);
+/* Same with sites, offsets and locations in the memory of the handle's device, on `stream` (may be NULL); *n_total is host
+ * memory and the call returns when it is done. */
+int issl_genome_locate_device(issl_genome *g, const uint64_t *d_sites, size_t n, uint64_t *d_offsets, issl_location *d_locs,
+                              size_t cap, size_t *n_total, void *stream);
+int issl_genome_close(issl_genome *g);
+
 #ifdef __cplusplus
 }
 #endif

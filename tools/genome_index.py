@@ -9,7 +9,13 @@ The fused path (IsslIndex.build_from_fasta, in this process) is timed per stage 
 synchronises the device at every boundary: parse (host FASTA pass), upload, match, sort, collapse, build (image), then
 the file write (up to --write-max-mbp); free HBM is sampled every 5 ms for the high-water mark.  The chain (bin/extractOfftargets sites.txt,
 then bin/isslCreateIndex sites.txt 20 W) runs as the two processes a user runs, on the same file, up to --chain-max-mbp;
-its .issl must be byte-identical.  Prints one JSON object per genome size (and writes them to --out)."""
+its .issl must be byte-identical.  Prints one JSON object per genome size (and writes them to --out).
+
+--locate: instead of the chain, the genome is opened as a resident crackling_amd.Genome and --locate-sites query sites
+(forward sites read off the genome's own text at seeded positions) are located: wall time of Genome.locate (its counting
+call and its filling call) on a handle without timing, and, on a handle made under ISSL_LOCATE_TIMING=1, the stage times
+(prep, count, emit, sort, offsets, finish) and the scan's counters (matches, those the filter let through, hits) of the
+filling call.  The yardstick beside them is the `match` stage of the fused build on the same genome."""
 import argparse
 import filecmp
 import json
@@ -102,7 +108,59 @@ def stderr_of(fn):
         return out, tmp.read().decode(errors="replace")
 
 
-def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout):
+def sample_sites(fa, n, seed):
+    """n distinct packed forward sites ([ACG][ACGT]{19}[ACGT][AG]G at the sampled start) from the records of the FASTA,
+    as the site table holds them (a site named k times would get its list k times: the repeated 23-mer alone has 200 000
+    locations)."""
+    rng = np.random.default_rng(seed)
+    code = np.full(256, 4, dtype=np.uint8)
+    code[np.frombuffer(b"ACGT", dtype=np.uint8)] = np.arange(4, dtype=np.uint8)
+    recs = [b"".join(r.split(b"\n")[1:]) for r in pathlib.Path(fa).read_bytes().split(b">")[1:]]
+    out = []
+    per = -(-n // len(recs)) * 2
+    for rec in recs:
+        c = code[np.frombuffer(rec, dtype=np.uint8)]
+        at = rng.integers(0, len(c) - 23, size=per * 16)
+        ok = (c[at] < 3) & ((c[at + 21] == 0) | (c[at + 21] == 2)) & (c[at + 22] == 2)
+        at = at[ok][:per]
+        sig = np.zeros(len(at), dtype=np.uint64)
+        for p in range(20):
+            ok_p = c[at + p]
+            sig |= ok_p.astype(np.uint64) << np.uint64(2 * p)
+        out.append(sig)
+    return rng.permutation(np.unique(np.concatenate(out)))[:n]
+
+
+def locate_leg(fa, n_sites, seed):
+    import crackling_amd as ca
+    res = []
+    t = time.perf_counter()
+    plain = ca.Genome.open([str(fa)])
+    open_s = time.perf_counter() - t
+    os.environ["ISSL_LOCATE_TIMING"] = "1"   # read when the handle is made
+    timed = ca.Genome.open([str(fa)])
+    os.environ.pop("ISSL_LOCATE_TIMING")
+    plain.locate(sample_sites(fa, 64, seed))  # code objects
+    for n in n_sites:
+        sites = sample_sites(fa, n, seed + n)
+        t = time.perf_counter()
+        offsets, locs = plain.locate(sites)
+        wall = time.perf_counter() - t
+        _, err = stderr_of(lambda: timed.locate(sites))
+        lines = [ln for ln in err.splitlines() if ln.startswith("[issl locate]")]
+        fill = lines[len(lines) // 2:]   # the filling call's lines (the counting call's come first)
+        stages = {m.group(1): float(m.group(2)) for ln in fill for m in re.finditer(r" (\w+) ([0-9.]+) ms", ln)}
+        ctr = {m.group(1).replace(" ", "_"): int(m.group(2)) for ln in fill
+               for m in re.finditer(r"(matches|filter passed|hits|locations) (\d+)", ln)}
+        res.append({"query_sites": int(n), "distinct_query_sites": int(len(np.unique(sites))), "locations": int(len(locs)),
+                    "locate_wall_ms_counting_and_filling_call": wall * 1e3, "filling_call_stages_ms": stages,
+                    "scan_counters": ctr, "filter_pass_rate": ctr.get("filter_passed", 0) / max(ctr.get("matches", 1), 1)})
+    plain.close()
+    timed.close()
+    return {"open_s": open_s, "n_bases": plain.n_bases, "records": len(plain.records), "queries": res}
+
+
+def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, locate_sites=None):
     import torch
     import crackling_amd as ca
     fa = work / f"genome_{kind}_{mbp:g}.fa"
@@ -128,7 +186,11 @@ def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout):
                           "hbm_high_water_per_raw_site": hbm.peak / max(hd["n_lines"], 1),
                           "upload_notes": [ln for ln in err.splitlines() if ln.startswith("[issl upload]")]}})
     ix.close()
-    if mbp <= chain_max_mbp:
+    if locate_sites:
+        res["locate"] = locate_leg(fa, locate_sites, seed)
+        res["locate"]["yardstick_match_stage_ms"] = stages.get("match", 0.0) * 1e3
+        res["chain"] = "not run with --locate"
+    elif mbp <= chain_max_mbp:
         sites = work / "sites.txt"
         chain_issl = work / "chain.issl"
         t = time.perf_counter()
@@ -160,6 +222,8 @@ def main():
     ap.add_argument("--chain-max-mbp", type=float, default=1000.0)
     ap.add_argument("--write-max-mbp", type=float, default=1000.0, help="time the .issl write up to this size (~48 B per site on disk)")
     ap.add_argument("--timeout", type=float, default=900.0, help="time limit of each chain process (s)")
+    ap.add_argument("--locate", action="store_true", help="locate query sites in the resident genome instead of running the chain")
+    ap.add_argument("--locate-sites", type=int, nargs="+", default=[1000, 1000000])
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -171,7 +235,8 @@ def main():
     results = []
     with tempfile.TemporaryDirectory(dir=a.workdir) as tmp:
         for mbp in a.mbp:
-            r = run(mbp, a.kind, a.seed, a.width, pathlib.Path(tmp), a.chain_max_mbp, a.write_max_mbp, a.timeout)
+            r = run(mbp, a.kind, a.seed, a.width, pathlib.Path(tmp), 0.0 if a.locate else a.chain_max_mbp, 0.0 if a.locate else a.write_max_mbp, a.timeout,
+                    a.locate_sites if a.locate else None)
             print(json.dumps(r), flush=True)
             results.append(r)
     if a.out:
