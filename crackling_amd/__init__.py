@@ -9,7 +9,9 @@ library raises immediately -- there is no CPU fallback.
 """
 from ._lib import lib, IsslError, LIB_PATH  # noqa: F401
 from .scorer import (  # noqa: F401
+    GUIDE_DTYPE,
     Genome,
+    GuideSet,
     IsslIndex,
     IsslNode,
     LOCATION_DTYPE,
@@ -27,6 +29,6 @@ from .scorer import (  # noqa: F401
 )
 
 __all__ = [
-    "Genome", "IsslIndex", "IsslNode", "IsslError", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
+    "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH",
 ]

@@ -71,6 +71,12 @@ class Location(C.Structure):
     _fields_ = [("pos", C.c_uint64), ("record", C.c_uint32), ("strand", C.c_uint32)]
 
 
+class Guide(C.Structure):
+    """issl_guide: 32 bytes, no padding."""
+    _fields_ = [("guide23", C.c_uint64), ("start", C.c_uint64), ("record", C.c_uint32), ("strand", C.c_uint32),
+                ("seen", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_guides", C.c_uint64), ("candidates", C.c_uint64), ("hits", C.c_uint64), ("scan_tiles", C.c_uint64),
@@ -153,6 +159,13 @@ _protos = {
     "issl_genome_locate": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "issl_genome_locate_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "issl_genome_close": (C.c_int, [_P]),
+    "issl_guides_extract": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(_P)]),
+    "issl_guides_extract_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(_P)]),
+    "issl_guides_info": (C.c_int, [_P, _u64p, _u64p, _u64p, _u64p]),
+    "issl_guides_record": (C.c_int, [_P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "issl_guides_copy": (C.c_int, [_P, _P, C.c_size_t]),
+    "issl_guides_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "issl_guides_close": (C.c_int, [_P]),
     "issl_node_create": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "issl_node_score": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P]),
     "issl_node_get_info": (C.c_int, [_P, C.POINTER(NodeInfo)]),

@@ -59,11 +59,6 @@ constexpr uint64_t kHashMul = 0x9E3779B97F4A7C15ull;
 
 static_assert(sizeof(issl_location) == 16, "issl_location is 16 bytes");
 
-__device__ __forceinline__ uint32_t lanes_before(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
-
 // ---- query prep ---------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void k_query_words(const uint64_t *__restrict__ sites, uint32_t n, uint64_t *__restrict__ words)
@@ -273,18 +268,6 @@ __global__ __launch_bounds__(256) void k_write_offsets(const uint32_t *__restric
 
 // ---- finish ------------------------------------------------------------------------------------------------------
 
-// Last index i of tab[0..n) with tab[i] <= x (0 when there is none).
-template <class T> __device__ __forceinline__ uint32_t last_not_above(const T *tab, uint32_t n, uint64_t x)
-{
-    uint32_t lo = 0, hi = n; // first index with tab[i] > x
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (static_cast<uint64_t>(tab[mid]) <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo ? lo - 1 : 0;
-}
-
 // Location j of the piece (j < total = offs[n]): query = the last one whose offset is <= j (queries without a location
 // share their offset with the next one and are passed over), its word the (j - offset)-th of its rank's run.
 template <bool kLds>
@@ -309,44 +292,6 @@ __global__ __launch_bounds__(256) void k_locate_finish(const uint64_t *__restric
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------
-
-struct StageTimer {
-    bool on;
-    hipStream_t stream;
-    double t0 = 0;
-    std::string line;
-    static double now_ms()
-    {
-        using namespace std::chrono;
-        return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-    }
-    StageTimer(bool on_, hipStream_t s) : on(on_), stream(s) { if (on) { (void)hipStreamSynchronize(stream); t0 = now_ms(); } }
-    void note(const char *stage)
-    {
-        if (!on) return;
-        (void)hipStreamSynchronize(stream);
-        const double t = now_ms();
-        char buf[64];
-        std::snprintf(buf, sizeof buf, " %s %.3f ms", stage, t - t0);
-        line += buf;
-        t0 = t;
-    }
-};
-
-// Sections of one allocation, 256-byte aligned.
-struct Arena {
-    DevBuf buf;
-    size_t size = 0;
-    size_t reserve(size_t bytes) { const size_t at = size; size = (size + bytes + 255) & ~size_t(255); return at; }
-    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(static_cast<char *>(buf.p) + off); }
-};
-
-inline uint32_t bits_for(uint64_t values) // bits that hold 0 .. values - 1
-{
-    uint32_t b = 1;
-    while (b < 64 && (1ull << b) < values) ++b;
-    return b;
-}
 
 // What a piece leaves behind for its finish.
 struct Piece {

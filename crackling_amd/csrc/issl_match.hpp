@@ -1,11 +1,13 @@
 // What the units that read genome text share (issl_extract.hip: site extraction and genome -> index; issl_locate.hip:
-// resident genome and locate): the pattern test of extractOfftargets.py:23-24 on the device, the LSD radix sort of 64-bit
+// resident genome and locate; issl_guides.hip: candidate guides): the pattern test of extractOfftargets.py:23-24 on the device, the LSD radix sort of 64-bit
 // words, the FASTA -> record text pass of the host and the small helpers around device memory.  Kernels and device
 // functions live in an anonymous namespace, one copy per translation unit, like issl_radix.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <string>
 #include <utility>
 #include <vector>
@@ -86,6 +88,63 @@ __device__ __forceinline__ uint32_t match_at(const uint8_t *__restrict__ s, uint
     key_fwd = kf;
     key_rev = kr;
     return (fwd ? 1u : 0u) | (rev ? 2u : 0u);
+}
+
+__device__ __forceinline__ uint32_t lanes_before(uint64_t mask)
+{
+    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
+}
+
+// Last index i of tab[0..n) with tab[i] <= x (0 when there is none).
+template <class T> __device__ __forceinline__ uint32_t last_not_above(const T *tab, uint32_t n, uint64_t x)
+{
+    uint32_t lo = 0, hi = n; // first index with tab[i] > x
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (static_cast<uint64_t>(tab[mid]) <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo ? lo - 1 : 0;
+}
+
+// Stage times of one call on one stream, for the stderr line of ISSL_LOCATE_TIMING / ISSL_GUIDES_TIMING: the stream is
+// synchronised at every note(); when it is off, note() does nothing and the call waits nowhere for the clock.
+struct StageTimer {
+    bool on;
+    hipStream_t stream;
+    double t0 = 0;
+    std::string line;
+    static double now_ms()
+    {
+        using namespace std::chrono;
+        return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+    }
+    StageTimer(bool on_, hipStream_t s) : on(on_), stream(s) { if (on) { (void)hipStreamSynchronize(stream); t0 = now_ms(); } }
+    void note(const char *stage)
+    {
+        if (!on) return;
+        (void)hipStreamSynchronize(stream);
+        const double t = now_ms();
+        char buf[64];
+        std::snprintf(buf, sizeof buf, " %s %.3f ms", stage, t - t0);
+        line += buf;
+        t0 = t;
+    }
+};
+
+// Sections of one allocation, 256-byte aligned.
+struct Arena {
+    DevBuf buf;
+    size_t size = 0;
+    size_t reserve(size_t bytes) { const size_t at = size; size = (size + bytes + 255) & ~size_t(255); return at; }
+    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(static_cast<char *>(buf.p) + off); }
+};
+
+inline uint32_t bits_for(uint64_t values) // bits that hold 0 .. values - 1
+{
+    uint32_t b = 1;
+    while (b < 64 && (1ull << b) < values) ++b;
+    return b;
 }
 
 // LSD radix sort of d_keys[0..n) on the bits [lo, hi), 8 per pass, all launches on `stream`, no synchronisation.  d_tmp

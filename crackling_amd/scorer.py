@@ -20,6 +20,8 @@ METHODS = {"unknown": 0, "mit": 1, "cfd": 2, "and": 3, "or": 4, "avg": 5}
 OFFTARGET_DTYPE = np.dtype([("site", "<u8"), ("mit", "<f8"), ("cfd", "<f8"), ("guide", "<u4"), ("id", "<u4"), ("occ", "<u4"),
                             ("dist", "<u2"), ("slice", "<u2")])
 LOCATION_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("strand", "<u4")])  # issl_location (16 bytes)
+# issl_guide (32 bytes)
+GUIDE_DTYPE = np.dtype([("guide23", "<u8"), ("start", "<u8"), ("record", "<u4"), ("strand", "<u4"), ("seen", "<u4"), ("reserved", "<u4")])
 PROFILE_DTYPE = np.dtype([("sites", "<u4", (_lib.PROFILE_BINS,)), ("pad", "<u4"), ("occurrences", "<u8", (_lib.PROFILE_BINS,))])
 
 
@@ -478,6 +480,128 @@ class Genome:
     def close(self):
         if self._h:
             lib.issl_genome_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DeviceArray:
+    """Device memory of a handle as torch sees it (the CUDA array interface): torch.as_tensor() wraps it without a copy
+    and keeps this object, and with it the owner, alive."""
+
+    def __init__(self, owner, ptr, shape, typestr):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
+
+
+class GuideSet:
+    """The candidate guides of FASTA inputs, extracted on the GPU and resident there (issl_guides_* of include/issl_hip.h):
+    Crackling's extraction step (Crackling.py:151-305).  Distinct 23-mers in the order the reference first meets them;
+    `record`, `start` and `strand` are the place of the first occurrence (strand 1: the guide is the reverse complement
+    of seq[start:start+23]), `seen` the number of occurrences; seen == 1 is the reference's isUnique."""
+
+    def __init__(self, handle, device=0):
+        self._h = handle
+        self.device = device
+        n_guides, n_unique, n_matches, n_rec = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib.issl_guides_info(self._h, C.byref(n_guides), C.byref(n_unique), C.byref(n_matches), C.byref(n_rec)))
+        self.n_guides, self.n_unique, self.n_matches = n_guides.value, n_unique.value, n_matches.value
+        self.records = []
+        name, name_len, length = C.c_void_p(), C.c_size_t(), C.c_uint64()
+        for r in range(n_rec.value):
+            check(lib.issl_guides_record(self._h, r, C.byref(name), C.byref(name_len), C.byref(length)))
+            self.records.append((C.string_at(name, name_len.value) if name_len.value else b"", length.value))
+        self._guides = None
+
+    @classmethod
+    def extract(cls, inputs, device=0):
+        """inputs: a list of bytes blobs (FASTA contents) or of paths (str / os.PathLike), read in the order given; a lone
+        directory stands for the files in it in reverse sorted name order, as the reference reads it."""
+        inputs = list(inputs)
+        h = C.c_void_p()
+        if inputs and all(isinstance(x, (bytes, bytearray, memoryview)) for x in inputs):
+            blobs = [bytes(x) for x in inputs]
+            files = (C.c_char_p * len(blobs))(*blobs)
+            lens = (C.c_size_t * len(blobs))(*[len(b) for b in blobs])
+            check(lib.issl_guides_extract(files, lens, len(blobs), device, C.byref(h)))
+        elif inputs and all(isinstance(x, (str, os.PathLike)) for x in inputs):
+            paths = [os.fsencode(x) for x in inputs]
+            arr = (C.c_char_p * len(paths))(*paths)
+            check(lib.issl_guides_extract_files(arr, len(paths), device, C.byref(h)))
+        else:
+            raise TypeError("inputs: a non-empty list of bytes blobs or of paths")
+        return cls(h, device)
+
+    def __len__(self):
+        return self.n_guides
+
+    @property
+    def guides(self):
+        """Structured array (GUIDE_DTYPE) of the guides in first-seen order; copied from the device once."""
+        if self._guides is None:
+            out = np.empty(self.n_guides, dtype=GUIDE_DTYPE)
+            check(lib.issl_guides_copy(self._h, out.ctypes.data, len(out)))
+            self._guides = out
+        return self._guides
+
+    def strings(self):
+        """The 23-mers as str, in first-seen order."""
+        return decode_guides(self.guides["guide23"], 23)
+
+    def _pointers(self):
+        d_guides, d_sigs = C.c_void_p(), C.c_void_p()
+        check(lib.issl_guides_device(self._h, C.byref(d_guides), C.byref(d_sigs)))
+        return d_guides.value, d_sigs.value
+
+    def sigs_tensor(self):
+        """int64 CUDA tensor over the set's own signature array (packed guide[0:20] per guide): no copy; the tensor keeps
+        the set alive, and close() must not be called while it is in use."""
+        import torch
+        if not self.n_guides:
+            return torch.empty(0, dtype=torch.int64, device=f"cuda:{self.device}")
+        return torch.as_tensor(_DeviceArray(self, self._pointers()[1], (self.n_guides,), "<i8"), device=f"cuda:{self.device}")
+
+    def guides_tensor(self):
+        """int32 CUDA tensor [n_guides, 8] over the set's own guide records (GUIDE_DTYPE as 32-bit words: column 6 is
+        `seen`): no copy."""
+        import torch
+        if not self.n_guides:
+            return torch.empty((0, 8), dtype=torch.int32, device=f"cuda:{self.device}")
+        return torch.as_tensor(_DeviceArray(self, self._pointers()[0], (self.n_guides, 8), "<i4"), device=f"cuda:{self.device}")
+
+    def score(self, index, max_dist=4, threshold=75.0, method="and", only_unique=True):
+        """Score the guides against an uploaded IsslIndex without taking them through the host: the rows to score are
+        selected on the device (only_unique: those with seen == 1, the ones the reference scores) and their signatures
+        go to index.score_device.  The selection makes the host wait for the device once (torch.nonzero has to learn how
+        many rows there are); no guide is copied.  -> (idx, mit, cfd) as numpy arrays: idx = the rows of .guides that
+        were scored, ascending."""
+        import torch
+        sigs = self.sigs_tensor()
+        if only_unique:
+            idx = torch.nonzero(self.guides_tensor()[:, 6] == 1).flatten()
+            sigs = sigs[idx]
+        else:
+            idx = torch.arange(self.n_guides, dtype=torch.int64, device=sigs.device)
+        mit = torch.empty(sigs.numel(), dtype=torch.float64, device=sigs.device)
+        cfd = torch.empty_like(mit)
+        if sigs.numel():
+            index.score_device(sigs.contiguous(), mit, cfd, max_dist, threshold, method,
+                               stream=torch.cuda.current_stream(sigs.device).cuda_stream)
+        return idx.cpu().numpy(), mit.cpu().numpy(), cfd.cpu().numpy()
+
+    def close(self):
+        if self._h:
+            lib.issl_guides_close(self._h)
             self._h = None
 
     def __enter__(self):

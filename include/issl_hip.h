@@ -513,6 +513,60 @@ int issl_genome_locate_device(issl_genome *g, const uint64_t *d_sites, size_t n,
                               size_t cap, size_t *n_total, void *stream);
 int issl_genome_close(issl_genome *g);
 
+/* ---- candidate guides from FASTA: Crackling's extraction step ------------------------------------------------------- */
+/* Counterpart of src/crackling/Crackling.py:151-305: the candidate 23-mers of the inputs, on `device`; no CPU fallback.
+ *   inputs    files[i]/lens[i]: the bytes of FASTA files, taken in the order given.  Lines end at "\n", "\r\n" or a lone
+ *             "\r" and are stripped of blanks (Python's str.strip() on ASCII); a stripped line that starts with '>' is a
+ *             header, its name the rest of the line; other lines are joined WITHOUT a change of case.  A line that is empty
+ *             after the strip stops the reference with an IndexError: ISSL_E_FORMAT here, the message names the input and
+ *             the line
+ *   records   a record is finished by the next header and counts when no record of that name was finished before, in this
+ *             input or an earlier one, or when it has no name but a sequence; the last record of every input counts
+ *             whatever its name, and its name is not remembered.  Text ahead of the first header is a record with an
+ *             empty name.  A record that does not count has no index; a header without sequence is a record of length 0.
+ *             name = the stripped header line without '>', as the bytes stand in the file (issl_guides_record; valid until
+ *             the set is closed, not terminated)
+ *   match     forward, strand 0: seq[i..i+21) all in ACGT -- upper case only, soft-masked bases never match -- and
+ *             seq[i+21] == seq[i+22] == 'G'; the guide is seq[i:i+23].  Reverse, strand 1: seq[i] == seq[i+1] == 'C' and
+ *             seq[i+2..i+23) all in ACGT; the guide is the reverse complement of seq[i:i+23].  Overlapping matches all
+ *             count, one start can match both ways, nothing straddles a record.  start = i for both strands, 0-based in the
+ *             record's joined sequence; the reference's `end` is start + 23
+ *   order     the reference meets the matches input by input, record by record, and in a record all forward matches by
+ *             position, then all reverse matches by position
+ *   guide set the distinct guides in the order they are first met; each with the record, start and strand of its first
+ *             occurrence and `seen`, the number of its occurrences in the whole input.  seen == 1 is the reference's
+ *             isUnique; a guide seen more often is the row the reference keeps with blanked coordinates and never scores
+ *   guide23   base p of the guide at bits [2p, 2p + 2), A C G T = 0..3 (issl_encode_guides with seq_len 23).  The signature
+ *             array beside the guides holds guide23 & (2^40 - 1), the packed guide[0:20]: what Crackling.py:747-752 sends to
+ *             the scorer, ready for issl_score_device
+ * Input without any match is an empty set (n_guides == 0, device pointers NULL), not an error.  More than 2^32 - 1 matches
+ * in one call: ISSL_E_UNSUPPORTED, as the extraction refuses.  No device: ISSL_E_DEVICE (no CPU fallback); NULL arguments
+ * and n_files <= 0: ISSL_E_ARG; *out is NULL after a failure.  The output is deterministic: the same bytes on every run.
+ * ISSL_GUIDES_TIMING=1 (read when the call starts) prints one stderr line with the stage times and the counts.  One set is
+ * used by one thread at a time. */
+typedef struct issl_guide_set issl_guide_set; /* opaque; owns device and host memory */
+typedef struct {
+    uint64_t guide23;  /* packed 23-mer */
+    uint64_t start;    /* 0-based start of the first occurrence inside its record */
+    uint32_t record;   /* index of that record */
+    uint32_t strand;   /* 0: forward pattern, 1: reverse pattern */
+    uint32_t seen;     /* occurrences in the whole input */
+    uint32_t reserved; /* 0 */
+} issl_guide;          /* 32 bytes, no padding */
+
+int issl_guides_extract(const char *const *files, const size_t *lens, int n_files, int device, issl_guide_set **out);
+/* Same from files on disk, in the order given; a lone directory stands for the files in it, top level only, in REVERSE
+ * sorted name order (ConfigManager.py:181-184).  A file that cannot be read: ISSL_E_IO. */
+int issl_guides_extract_files(const char *const *paths, int n_paths, int device, issl_guide_set **out);
+/* n_matches: all occurrences (the sum of `seen`); n_unique: guides with seen == 1. */
+int issl_guides_info(const issl_guide_set *g, uint64_t *n_guides, uint64_t *n_unique, uint64_t *n_matches, uint64_t *n_records);
+int issl_guides_record(const issl_guide_set *g, uint64_t r, const char **name, size_t *name_len, uint64_t *length);
+/* The guides to host memory, first-seen order; cap < n_guides: ISSL_E_ARG. */
+int issl_guides_copy(const issl_guide_set *g, issl_guide *out, size_t cap);
+/* The guides and their signatures in the memory of the set's device, n_guides each, valid until the set is closed. */
+int issl_guides_device(const issl_guide_set *g, const issl_guide **d_guides, const uint64_t **d_sigs);
+int issl_guides_close(issl_guide_set *g);
+
 #ifdef __cplusplus
 }
 #endif

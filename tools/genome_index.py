@@ -15,7 +15,13 @@ its .issl must be byte-identical.  Prints one JSON object per genome size (and w
 (forward sites read off the genome's own text at seeded positions) are located: wall time of Genome.locate (its counting
 call and its filling call) on a handle without timing, and, on a handle made under ISSL_LOCATE_TIMING=1, the stage times
 (prep, count, emit, sort, offsets, finish) and the scan's counters (matches, those the filter let through, hits) of the
-filling call.  The yardstick beside them is the `match` stage of the fused build on the same genome."""
+filling call.  The yardstick beside them is the `match` stage of the fused build on the same genome.
+
+--guides: instead of the chain, the candidate guides of the genome are extracted (crackling_amd.GuideSet.extract): wall
+time to a resident set without timing, then once more under ISSL_GUIDES_TIMING=1 for the stage times (parse on the host;
+upload, count, emit, sort, runs, order, finish on the device) with free HBM sampled for the high-water mark per match.
+The yardstick is `match` + `sort` of the fused build in the same run: it reads the same text twice and sorts a
+comparable number of 64-bit words; the ratio of the device stages behind the upload to it is reported."""
 import argparse
 import filecmp
 import json
@@ -160,7 +166,29 @@ def locate_leg(fa, n_sites, seed):
     return {"open_s": open_s, "n_bases": plain.n_bases, "records": len(plain.records), "queries": res}
 
 
-def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, locate_sites=None):
+def guides_leg(fa, torch):
+    import crackling_amd as ca
+    ca.GuideSet.extract([b">w\n" + b"ACGTTGCAGGTACCAGTAGGCAGG" * 100 + b"\n"]).close()   # code objects
+    t = time.perf_counter()
+    plain = ca.GuideSet.extract([str(fa)])
+    wall = time.perf_counter() - t
+    n_guides, n_unique, n_matches, n_records = plain.n_guides, plain.n_unique, plain.n_matches, len(plain.records)
+    plain.close()
+    os.environ["ISSL_GUIDES_TIMING"] = "1"   # read when the call starts
+    with HbmWatch(torch) as hbm:
+        timed, err = stderr_of(lambda: ca.GuideSet.extract([str(fa)]))
+    os.environ.pop("ISSL_GUIDES_TIMING")
+    resident = hbm.before - torch.cuda.mem_get_info(0)[0]
+    timed.close()
+    line = [ln for ln in err.splitlines() if ln.startswith("[issl guides]")][-1]
+    stages = {m.group(1): float(m.group(2)) for m in re.finditer(r" (\w+) ([0-9.]+) ms", line)}
+    device = sum(v for k, v in stages.items() if k not in ("parse", "upload"))
+    return {"wall_s_to_resident_set": wall, "stages_ms": stages, "device_stages_ms_without_upload": device, "matches": n_matches,
+            "guides": n_guides, "unique": n_unique, "records": n_records, "hbm_high_water_bytes": hbm.peak,
+            "hbm_high_water_per_match": hbm.peak / max(n_matches, 1), "resident_bytes_of_the_set": resident}
+
+
+def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, locate_sites=None, guides=False):
     import torch
     import crackling_amd as ca
     fa = work / f"genome_{kind}_{mbp:g}.fa"
@@ -190,6 +218,12 @@ def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, loc
         res["locate"] = locate_leg(fa, locate_sites, seed)
         res["locate"]["yardstick_match_stage_ms"] = stages.get("match", 0.0) * 1e3
         res["chain"] = "not run with --locate"
+    elif guides:
+        res["guides"] = guides_leg(fa, torch)
+        yard = (stages.get("match", 0.0) + stages.get("sort", 0.0)) * 1e3
+        res["guides"]["yardstick_match_plus_sort_ms"] = yard
+        res["guides"]["device_stages_over_yardstick"] = res["guides"]["device_stages_ms_without_upload"] / max(yard, 1e-9)
+        res["chain"] = "not run with --guides"
     elif mbp <= chain_max_mbp:
         sites = work / "sites.txt"
         chain_issl = work / "chain.issl"
@@ -224,6 +258,7 @@ def main():
     ap.add_argument("--timeout", type=float, default=900.0, help="time limit of each chain process (s)")
     ap.add_argument("--locate", action="store_true", help="locate query sites in the resident genome instead of running the chain")
     ap.add_argument("--locate-sites", type=int, nargs="+", default=[1000, 1000000])
+    ap.add_argument("--guides", action="store_true", help="extract the candidate guides of the genome instead of running the chain")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -235,8 +270,9 @@ def main():
     results = []
     with tempfile.TemporaryDirectory(dir=a.workdir) as tmp:
         for mbp in a.mbp:
-            r = run(mbp, a.kind, a.seed, a.width, pathlib.Path(tmp), 0.0 if a.locate else a.chain_max_mbp, 0.0 if a.locate else a.write_max_mbp, a.timeout,
-                    a.locate_sites if a.locate else None)
+            no_chain = a.locate or a.guides
+            r = run(mbp, a.kind, a.seed, a.width, pathlib.Path(tmp), 0.0 if no_chain else a.chain_max_mbp, 0.0 if no_chain else a.write_max_mbp, a.timeout,
+                    a.locate_sites if a.locate else None, a.guides)
             print(json.dumps(r), flush=True)
             results.append(r)
     if a.out:
