@@ -259,8 +259,10 @@ def markov_sites_fast(n_lines, seed, threads=16, seq_len=20, at_bias=0.62, order
     return np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out])
 
 
-def check_comparisons(ix, guides, prune=None):
-    """Counters of the last call: what the reference would compare, what was planned, what the scan kernel counted."""
+def check_comparisons(ix, guides, prune=None, site_sigs=None, max_dist=None):
+    """Counters of the last call: what the reference would compare, what was planned, what the scan kernel counted.
+    With the index's site signatures and the call's max_dist, a pruned call must have planned exactly the comparisons the
+    layout-free rule of tests/pruned_model.py counts."""
     st = ix.stats()
     expected = ix.count_candidates(guides)
     assert st["reference_comparisons"] == expected
@@ -270,4 +272,7 @@ def check_comparisons(ix, guides, prune=None):
         assert st["candidates"] == expected == st["planned_comparisons"]
     else:   # a group's first and last tile also hold its neighbours' candidates
         assert st["planned_comparisons"] <= st["candidates"]
+        if site_sigs is not None:
+            import pruned_model
+            assert st["planned_comparisons"] == pruned_model.planned_comparisons(site_sigs, guides, max_dist, ix.header["slice_width"])
     return st

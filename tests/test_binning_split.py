@@ -46,7 +46,8 @@ class _Index:
         self.ix.set_option("prune", prune)
         try:
             mit, cfd = self.ix.score(guides, dist, 75.0, "and")
-            st = check_comparisons(self.ix, guides, prune)
+            # (the exact plan where the model takes about a second: up to 10 000 guides)
+            st = check_comparisons(self.ix, guides, prune, self.sigs if len(guides) <= 10_000 else None, dist)
         finally:
             self.ix.set_option("prune", -1)
         if prune == 1:

@@ -270,7 +270,7 @@ def test_config0_scores_match_oracle(config0, method, thr, dist, prune):
     assert np.allclose(mit, omit, rtol=0, atol=FLOAT_TOL) and np.allclose(cfd, ocfd, rtol=0, atol=FLOAT_TOL)
     assert np.array_equal(mit.view(np.uint64), omit.view(np.uint64)), "MIT not bit-identical"
     assert np.array_equal(cfd.view(np.uint64), ocfd.view(np.uint64)), "CFD not bit-identical"
-    check_comparisons(ix, guides, prune)
+    check_comparisons(ix, guides, prune, sigs, dist)
 
 
 @PRUNE
@@ -338,7 +338,7 @@ def test_max_dist_5_takes_the_pruned_scan_too(config0):
             ix.set_option("prune", prune)
             for thr in (0.0, 75.0):
                 mit, cfd = ix.score(guides, 5, thr, "and")
-                st = check_comparisons(ix, guides, prune)
+                st = check_comparisons(ix, guides, prune, sigs, 5)
                 if prune == 1:
                     assert st["pruned"] == 3   # (forced: on a 1 M-site index the planner would not prune)
                 omit, ocfd = oracle.score(guides, 5, thr, "and")
@@ -397,7 +397,7 @@ def test_scheduling_knobs_do_not_change_results(config0):
             assert np.array_equal(got, want), (sched, blocks, prune)
             gm, gc = ix.score(batch, 4, 75.0, "and")
             assert np.array_equal(gm, wm) and np.array_equal(gc, wc), (sched, blocks, prune)
-            st = check_comparisons(ix, batch, prune)
+            st = check_comparisons(ix, batch, prune, sigs, 4)
             assert st["reference_comparisons"] == expected and st["pruned"] == 2 * prune, (sched, blocks, prune)
         ix.set_option("item_guides", 512).set_option("scan_blocks", 1024)
         for slots, prune in ((0, 0), (0, 1), (1, 1), (2, 1), (2, 0)):   # without / with the per-guide hit slots (Workspace::slot_hits), 2: the wide ones
@@ -1116,7 +1116,7 @@ def test_narrow_slices_on_the_sorted_layouts_against_the_oracle(tmp_path, width)
                     hits = ix.dump_hits(guides, dist, thr, "and")
                     assert np.array_equal(hits, ohits), (layout, prune, dist, thr)
                     mit, cfd = ix.score(guides, dist, thr, "and")
-                    st = ix.stats()
+                    st = check_comparisons(ix, guides, prune, sig, dist) if dist <= 5 else ix.stats()
                     assert np.array_equal(mit.view(np.uint64), omit.view(np.uint64)), (layout, prune, dist, thr)
                     assert np.array_equal(cfd.view(np.uint64), ocfd.view(np.uint64)), (layout, prune, dist, thr)
                     if prune == 1:
