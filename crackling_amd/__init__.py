@@ -28,7 +28,17 @@ from .scorer import (  # noqa: F401
     verdicts,
 )
 
+from .consensus import (  # noqa: F401
+    CONSENSUS_DTYPE,
+    Consensus,
+    FOLD_DTYPE,
+    SCAFFOLD,
+    load_sgrnascorer2,
+    read_rnafold_output,
+)
+
 __all__ = [
+    "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",
     "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH",
 ]

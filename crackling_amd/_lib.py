@@ -77,6 +77,13 @@ class Guide(C.Structure):
                 ("seen", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ConsensusConfig(C.Structure):
+    """issl_consensus_config."""
+    _fields_ = [("optimisation", C.c_uint32), ("n", C.c_uint32), ("mm10db", C.c_uint32), ("chopchop", C.c_uint32),
+                ("sgrnascorer2", C.c_uint32), ("n_sv", C.c_uint32), ("sv", C.c_void_p), ("coef", C.c_void_p),
+                ("intercept", C.c_double), ("sgrna_threshold", C.c_double), ("low_energy", C.c_double), ("high_energy", C.c_double)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_guides", C.c_uint64), ("candidates", C.c_uint64), ("hits", C.c_uint64), ("scan_tiles", C.c_uint64),
@@ -166,6 +173,13 @@ _protos = {
     "issl_guides_copy": (C.c_int, [_P, _P, C.c_size_t]),
     "issl_guides_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "issl_guides_close": (C.c_int, [_P]),
+    "issl_consensus_begin": (C.c_int, [_P, C.POINTER(ConsensusConfig), C.POINTER(_P)]),
+    "issl_consensus_fold_list": (C.c_int, [_P, C.POINTER(_P), _u64p]),
+    "issl_consensus_fold_copy": (C.c_int, [_P, _P, C.c_size_t]),
+    "issl_consensus_finish": (C.c_int, [_P, _P, C.c_size_t]),
+    "issl_consensus_copy": (C.c_int, [_P, _P, C.c_size_t]),
+    "issl_consensus_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), _u64p]),
+    "issl_consensus_close": (C.c_int, [_P]),
     "issl_node_create": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "issl_node_score": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P]),
     "issl_node_get_info": (C.c_int, [_P, C.POINTER(NodeInfo)]),

@@ -46,16 +46,11 @@
 #include <vector>
 
 #include "../../include/issl_hip.h"
+#include "issl_guides.hpp"
 #include "issl_host.hpp"
 #include "issl_match.hpp"
 #include "issl_radix.hpp"
 
-struct issl_guide_set {
-    int device = -1;
-    uint64_t n_guides = 0, n_unique = 0, n_matches = 0;
-    issl::DevBuf guides, sigs; // issl_guide[n_guides], uint64_t[n_guides]; null when there is no guide
-    std::vector<issl::FastaRecord> records;
-};
 
 namespace issl {
 namespace {

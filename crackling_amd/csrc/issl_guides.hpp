@@ -1,0 +1,14 @@
+// The guide set behind issl_guides_* (issl_guides.hip makes it) as the stages that work on its rows in place see it
+// (issl_consensus.hip).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "issl_match.hpp"
+
+struct issl_guide_set {
+    int device = -1;
+    uint64_t n_guides = 0, n_unique = 0, n_matches = 0;
+    issl::DevBuf guides, sigs; // issl_guide[n_guides], uint64_t[n_guides]; null when there is no guide
+    std::vector<issl::FastaRecord> records;
+};

@@ -579,15 +579,29 @@ class GuideSet:
             return torch.empty((0, 8), dtype=torch.int32, device=f"cuda:{self.device}")
         return torch.as_tensor(_DeviceArray(self, self._pointers()[0], (self.n_guides, 8), "<i4"), device=f"cuda:{self.device}")
 
-    def score(self, index, max_dist=4, threshold=75.0, method="and", only_unique=True):
+    def consensus(self, config=None, **kw):
+        """The efficiency consensus over this set (Crackling.py:306-598, crackling_amd.Consensus): config is a mapping of
+        Consensus's keywords (optimisation, n, mm10db, chopchop, sgrnascorer2, model, sgrna_threshold, low_energy,
+        high_energy); keywords given directly win."""
+        from .consensus import Consensus
+        return Consensus(self, **{**dict(config or {}), **kw})
+
+    def score(self, index, max_dist=4, threshold=75.0, method="and", only_unique=True, consensus=None):
         """Score the guides against an uploaded IsslIndex without taking them through the host: the rows to score are
-        selected on the device (only_unique: those with seen == 1, the ones the reference scores) and their signatures
+        selected on the device (only_unique: those with seen == 1, the ones the reference scores at optimisation `low`;
+        consensus: a finished Consensus of this set -- its selection, the rows the reference scores at the configured
+        optimisation level, and only_unique is not looked at) and their signatures
         go to index.score_device.  The selection makes the host wait for the device once (torch.nonzero has to learn how
         many rows there are); no guide is copied.  -> (idx, mit, cfd) as numpy arrays: idx = the rows of .guides that
         were scored, ascending."""
         import torch
         sigs = self.sigs_tensor()
-        if only_unique:
+        if consensus is not None:
+            if consensus.guide_set is not self:
+                raise ValueError("the consensus belongs to another guide set")
+            idx = consensus.selected_tensor().to(torch.int64)
+            sigs = sigs[idx]
+        elif only_unique:
             idx = torch.nonzero(self.guides_tensor()[:, 6] == 1).flatten()
             sigs = sigs[idx]
         else:

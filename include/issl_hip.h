@@ -567,6 +567,70 @@ int issl_guides_copy(const issl_guide_set *g, issl_guide *out, size_t cap);
 int issl_guides_device(const issl_guide_set *g, const issl_guide **d_guides, const uint64_t **d_sigs);
 int issl_guides_close(issl_guide_set *g);
 
+/* ---- efficiency consensus: G20, the mm10db filters, sgRNAScorer2 ------------------------------------------------------ */
+/* Counterpart of src/crackling/Crackling.py:306-598 with the filter of :36-149, on the rows of a guide set, in place on the
+ * set's device; no guide is copied to the host and there is no CPU fallback.  The set must stay open while the consensus is.
+ *   filter    every step looks only at the guides filterCandidateGuides yields at that point, for the optimisation level,
+ *             n and the tool flags given; passedBowtie is untested here and rejects nothing
+ *   begin     G20 (:310-323), leading T (:328-343), AT percent (:348-366) and TTTT (:371-384), in that order; at =
+ *             100.0 * count / 20.0 in double over guide[0:20]; the fold list = the rows the reference would write to
+ *             RNAfold's input (:406-422), ascending.  Without mm10db the list is empty
+ *   folds     RNAfold is not part of this library.  The caller folds "G" + guide[1:20] + the scaffold of :395 for every row of
+ *             the list and hands back, per row and in the list's order, the energy, whether the structure matches the pattern
+ *             of :396, and present = 0 where RNAfold's output has no entry under the key guide[1:20] (the reference looks the
+ *             entry up by that key, the last one wins: :439-470)
+ *   finish    once: ss by :476-498 -- error for a guide that starts with T, which the filter lets through only at ultralow and
+ *             low; with the scaffold matched rejected when energy < low_energy, otherwise rejected when energy <=
+ *             high_energy; present == 0 leaves it untested -- then for all rows the mm10db verdict (:518-530: an untested or
+ *             erred sub-test rejects), the sgRNAScorer2 score and verdict for the rows the filter yields (:541-577), the
+ *             count (:586-591) and the selection: the rows the filter yields for the specificity stage, ascending -- what
+ *             goes to issl_score_device
+ *   score     exact.  onehot sets for position p the bits 4p .. 4p + 3 of the reference's encoding, string index 0 first:
+ *             A 0001, C 0010, T 0100, G 1000.  k_i = popcount(sv_i & onehot); score = -((((0.0 + coef[0] * k_0) + coef[1] * k_1)
+ *             ... + coef[n_sv - 1] * k_(n_sv - 1)) + intercept), every product and sum rounded to double on its own: libsvm's
+ *             sum for a linear kernel over 0 / 1 support vectors and sklearn's change of sign.  Rejected when score <
+ *             sgrna_threshold
+ * Errors: ISSL_E_ARG for a NULL pointer, optimisation > 3, sgrnascorer2 != 0 with n_sv == 0, n_folds that differs from the
+ * fold list and cap below what is copied; ISSL_E_UNSUPPORTED for a support-vector entry other than 0 or 1; ISSL_E_STATE for a
+ * second finish and for copy / device ahead of finish.  An empty set gives empty results.  The output is deterministic:
+ * the same bytes on every run.  One consensus is used by one thread at a time. */
+typedef struct issl_consensus issl_consensus; /* opaque; owns device memory */
+typedef struct {
+    uint32_t optimisation;                   /* 0 ultralow, 1 low, 2 medium, 3 high ([general] optimisation) */
+    uint32_t n;                              /* [consensus] n */
+    uint32_t mm10db, chopchop, sgrnascorer2; /* 0 / 1: the tools in the consensus */
+    uint32_t n_sv;                           /* support vectors of the sgRNAScorer2 model */
+    const uint8_t *sv;                       /* n_sv x 80, row-major, every entry 0 or 1 */
+    const double *coef;                      /* n_sv: sklearn's _dual_coef_[0] */
+    double intercept;                        /* sklearn's _intercept_[0] */
+    double sgrna_threshold;                  /* [sgrnascorer2] score-threshold */
+    double low_energy, high_energy;          /* [rnafold] low_energy_threshold, high_energy_threshold */
+} issl_consensus_config;
+typedef struct {
+    double energy;     /* the number in the last parentheses of RNAfold's structure line */
+    uint32_t scaffold; /* 1: the structure matches the pattern of :396 */
+    uint32_t present;  /* 0: no entry for this guide */
+} issl_fold;           /* 16 bytes */
+typedef struct {
+    double sgrna_score, at, ss_energy; /* NaN where the reference leaves '?' */
+    uint8_t g20, lead_t, at_pct, tttt, ss, mm10db, sgrna; /* 0 rejected, 1 accepted, 2 untested '?', 3 error '!' */
+    uint8_t count;                     /* consensusCount, 0..3 */
+} issl_consensus_row;                  /* 32 bytes, no padding */
+
+int issl_consensus_begin(const issl_guide_set *gs, const issl_consensus_config *cfg, issl_consensus **out);
+/* The fold list in the memory of the set's device (NULL when it is empty), valid until the consensus is closed. */
+int issl_consensus_fold_list(const issl_consensus *c, const uint32_t **d_rows, uint64_t *n_fold);
+/* The fold list to host memory; cap below its length: ISSL_E_ARG. */
+int issl_consensus_fold_copy(const issl_consensus *c, uint32_t *rows, size_t cap);
+/* folds: host memory, n_folds = the length of the fold list, fold i belongs to row i of the list; NULL with 0. */
+int issl_consensus_finish(issl_consensus *c, const issl_fold *folds, size_t n_folds);
+/* The rows of all guides of the set to host memory; cap below their number: ISSL_E_ARG. */
+int issl_consensus_copy(const issl_consensus *c, issl_consensus_row *out, size_t cap);
+/* Rows and selection in the memory of the set's device (NULL where empty), valid until the consensus is closed. */
+int issl_consensus_device(const issl_consensus *c, const issl_consensus_row **d_rows, const uint32_t **d_selected,
+                          uint64_t *n_selected);
+int issl_consensus_close(issl_consensus *c);
+
 #ifdef __cplusplus
 }
 #endif
