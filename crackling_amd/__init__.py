@@ -16,6 +16,7 @@ from .scorer import (  # noqa: F401
     IsslNode,
     LOCATION_DTYPE,
     METHODS,
+    OCCURRENCE_DTYPE,
     OFFTARGET_DTYPE,
     PROFILE_DTYPE,
     encode_guides,
@@ -37,7 +38,16 @@ from .consensus import (  # noqa: F401
     read_rnafold_output,
 )
 
+from .bowtie import (  # noqa: F401
+    BOWTIE_PAMS,
+    BowtieStep,
+    bowtie_input,
+    format_columns,
+    read_bowtie_output,
+)
+
 __all__ = [
+    "BOWTIE_PAMS", "BowtieStep", "OCCURRENCE_DTYPE", "bowtie_input", "format_columns", "read_bowtie_output",
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",
     "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH",

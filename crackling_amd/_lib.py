@@ -165,6 +165,8 @@ _protos = {
     "issl_genome_record": (C.c_int, [_P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "issl_genome_locate": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "issl_genome_locate_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_genome_occurrences": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P]),
+    "issl_genome_occurrences_device": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "issl_genome_close": (C.c_int, [_P]),
     "issl_guides_extract": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(_P)]),
     "issl_guides_extract_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(_P)]),

@@ -80,6 +80,7 @@ class Consensus:
         cfg = _lib.ConsensusConfig()
         cfg.optimisation = OPTIMISATIONS[optimisation.lower()] if isinstance(optimisation, str) else int(optimisation)
         cfg.n = int(n)
+        self.optimisation = cfg.optimisation
         cfg.mm10db, cfg.chopchop, cfg.sgrnascorer2 = int(bool(mm10db)), int(bool(chopchop)), int(bool(sgrnascorer2))
         keep = []
         if model is not None:
@@ -167,6 +168,12 @@ class Consensus:
         if self._selected is None:
             self._selected = self.selected_tensor().cpu().numpy().astype(np.uint32)
         return self._selected
+
+    def bowtie(self, genome, page_length=0):
+        """The Bowtie step (Crackling.py:600-725) over the selection of this finished consensus, on `genome` (a
+        crackling_amd.Genome on the same device) -> BowtieStep."""
+        from .bowtie import BowtieStep
+        return BowtieStep(self, genome, page_length)
 
     def close(self):
         if self._h:

@@ -1,0 +1,109 @@
+// What the units on a resident genome share (issl_locate.hip: locations of sites; issl_occur.hip: the Bowtie step): the
+// handle, and the preparation of a piece of query sites -- signatures -> text-order keys, sorted with their query index,
+// runs of equal keys collapsed to ranks, one bit per distinct key in a bitmap -- with the probe the scan of the text
+// asks.  Kernels and device functions live in an anonymous namespace, one copy per translation unit, like issl_match.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "../../include/issl_hip.h"
+#include "issl_match.hpp"
+
+struct issl_genome {
+    int device = -1;
+    uint64_t len = 0;     // bytes of text, separators included
+    uint64_t n_bases = 0; // sum of the records' lengths
+    uint32_t pos_bits = 1; // bits of a text position
+    bool timing = false;  // ISSL_LOCATE_TIMING=1, read when the handle is made: one stderr line per stage of a call
+    issl::DevBuf seq, starts;
+    std::vector<issl::FastaRecord> records;
+};
+
+namespace issl {
+namespace {
+
+constexpr uint32_t kPieceBits = 22;                 // query index inside a piece: key (41 bits) | index fits a word
+constexpr size_t kPieceSites = size_t(1) << kPieceBits;
+constexpr uint64_t kNoKey = 1ull << 40;             // key of a signature with bits above the 20 bases: matches nothing
+constexpr uint64_t kHashMul = 0x9E3779B97F4A7C15ull;
+
+
+// ---- query prep ---------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void k_query_words(const uint64_t *__restrict__ sites, uint32_t n, uint64_t *__restrict__ words)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t sig = sites[i];
+    uint64_t key = 0;
+#pragma unroll
+    for (int p = 0; p < 20; ++p) key |= ((sig >> (2 * p)) & 3ull) << (2 * (19 - p));
+    if (sig >> 40) key = kNoKey;
+    words[i] = (key << kPieceBits) | i;
+}
+
+__global__ __launch_bounds__(256) void k_query_heads(const uint64_t *__restrict__ words, uint32_t n, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const bool head = i < n && (i == 0 || (words[i - 1] >> kPieceBits) != (words[i] >> kPieceBits));
+    const uint64_t heads = __ballot(head);
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = static_cast<uint32_t>(__builtin_popcountll(heads));
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// first[b]: heads ahead of block b.  Every sorted query learns its rank; a head also lists its key and sets its bit.
+__global__ __launch_bounds__(256) void k_query_ranks(const uint64_t *__restrict__ words, uint32_t n, const uint32_t *__restrict__ first,
+                                                     uint64_t *__restrict__ ukeys, uint32_t *__restrict__ qrank,
+                                                     uint32_t *__restrict__ bitmap, uint32_t hash_shift)
+{
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x, wave = threadIdx.x >> 6;
+    const bool valid = i < n;
+    const uint64_t w = valid ? words[i] : 0ull;
+    const uint64_t key = w >> kPieceBits;
+    const bool head = valid && (i == 0 || (words[i - 1] >> kPieceBits) != key);
+    const uint64_t heads = __ballot(head);
+    if ((threadIdx.x & 63) == 0) wave_cnt[wave] = static_cast<uint32_t>(__builtin_popcountll(heads));
+    __syncthreads();
+    uint32_t before = first[blockIdx.x] + lanes_before(heads); // heads ahead of i
+    for (uint32_t v = 0; v < wave; ++v) before += wave_cnt[v];
+    if (!valid) return;
+    const uint32_t rank = head ? before : before - 1;
+    qrank[w & (kPieceSites - 1)] = rank;
+    if (head) {
+        ukeys[rank] = key;
+        const uint32_t h = static_cast<uint32_t>((key * kHashMul) >> hash_shift);
+        atomicOr(&bitmap[h >> 5], 1u << (h & 31));
+    }
+}
+
+// ---- what the scan of the text asks -------------------------------------------------------------------------------
+
+struct Probe {
+    const uint64_t *ukeys;   // distinct query keys, ascending
+    const uint32_t *n_ranks; // how many (device memory: the host never reads it)
+    const uint32_t *bitmap;
+    uint32_t hash_shift;
+};
+
+// Rank of `key` among the query's distinct keys, or -1.  `passed`: the bitmap let it through.
+__device__ __forceinline__ int probe_key(const Probe &q, uint32_t nr, uint64_t key, uint32_t &passed)
+{
+    const uint32_t h = static_cast<uint32_t>((key * kHashMul) >> q.hash_shift);
+    if (!((q.bitmap[h >> 5] >> (h & 31)) & 1u)) return -1;
+    ++passed;
+    uint32_t lo = 0, hi = nr;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (q.ukeys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < nr && q.ukeys[lo] == key ? static_cast<int>(lo) : -1;
+}
+
+} // namespace
+} // namespace issl

@@ -20,6 +20,10 @@ METHODS = {"unknown": 0, "mit": 1, "cfd": 2, "and": 3, "or": 4, "avg": 5}
 OFFTARGET_DTYPE = np.dtype([("site", "<u8"), ("mit", "<f8"), ("cfd", "<f8"), ("guide", "<u4"), ("id", "<u4"), ("occ", "<u4"),
                             ("dist", "<u2"), ("slice", "<u2")])
 LOCATION_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("strand", "<u4")])  # issl_location (16 bytes)
+# issl_occurrence (32 bytes)
+OCCURRENCE_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("n_perfect", "<u4"), ("aligned", "u1"), ("repeated", "u1"),
+                             ("nb", "u1"), ("strand", "u1"), ("owner", "u1"), ("code", "u1"), ("reserved", "u1", (2,)),
+                             ("source", "<u4"), ("reserved2", "<u4")])
 # issl_guide (32 bytes)
 GUIDE_DTYPE = np.dtype([("guide23", "<u8"), ("start", "<u8"), ("record", "<u4"), ("strand", "<u4"), ("seen", "<u4"), ("reserved", "<u4")])
 PROFILE_DTYPE = np.dtype([("sites", "<u4", (_lib.PROFILE_BINS,)), ("pad", "<u4"), ("occurrences", "<u8", (_lib.PROFILE_BINS,))])
@@ -477,6 +481,31 @@ class Genome:
                                             C.c_void_p(stream) if stream else None))
         return n.value
 
+    def occurrences(self, sites, page_length=0):
+        """The Bowtie step (Crackling.py:600-725) as exact counts.  sites: 20-mer strings or a uint64 array of packed
+        signatures, duplicates allowed; page_length: the reference's [bowtie2] page-length (0: one page).  -> structured
+        array (OCCURRENCE_DTYPE), one row per site: which of the eight reads site + AGG, CGG, GGG, TGG, AAG, CAG, GAG, TAG
+        occur in the genome without a mismatch (`aligned`) and which at least twice (`repeated`), `nb` as the reference
+        counts, and the verdict the reference files under this site: `code`, the first occurrence of read 0 (record
+        0xFFFFFFFF when there is none) and `source`, the site whose group of SAM lines set it (include/issl_hip.h)."""
+        if isinstance(sites, np.ndarray):
+            sigs = np.ascontiguousarray(sites, dtype=np.uint64)
+        else:
+            sigs = encode_guides(sites)
+        rows = np.zeros(len(sigs), dtype=OCCURRENCE_DTYPE)
+        check(lib.issl_genome_occurrences(self._h, sigs.ctypes.data if len(sigs) else None, len(sigs), int(page_length),
+                                          rows.ctypes.data if len(sigs) else None))
+        return rows
+
+    def occurrences_device(self, d_sites, d_rows, page_length=0, stream=None):
+        """d_sites: int64 CUDA tensor of packed signatures (left as it is); d_rows: uint8 CUDA tensor of 32 bytes per site
+        (OCCURRENCE_DTYPE).  Returns when the rows are written."""
+        n = d_sites.numel()
+        if d_rows.numel() * d_rows.element_size() < OCCURRENCE_DTYPE.itemsize * n:
+            raise ValueError("d_rows holds fewer than 32 bytes per site")
+        check(lib.issl_genome_occurrences_device(self._h, d_sites.data_ptr() if n else None, n, int(page_length),
+                                                 d_rows.data_ptr() if n else None, C.c_void_p(stream) if stream else None))
+
     def close(self):
         if self._h:
             lib.issl_genome_close(self._h)
@@ -586,11 +615,13 @@ class GuideSet:
         from .consensus import Consensus
         return Consensus(self, **{**dict(config or {}), **kw})
 
-    def score(self, index, max_dist=4, threshold=75.0, method="and", only_unique=True, consensus=None):
+    def score(self, index, max_dist=4, threshold=75.0, method="and", only_unique=True, consensus=None,
+              bowtie=None):
         """Score the guides against an uploaded IsslIndex without taking them through the host: the rows to score are
         selected on the device (only_unique: those with seen == 1, the ones the reference scores at optimisation `low`;
         consensus: a finished Consensus of this set -- its selection, the rows the reference scores at the configured
-        optimisation level, and only_unique is not looked at) and their signatures
+        optimisation level, and only_unique is not looked at; bowtie: a BowtieStep of that consensus -- the selection
+        without the rows Bowtie rejected, as the reference's filter leaves them at medium and high) and their signatures
         go to index.score_device.  The selection makes the host wait for the device once (torch.nonzero has to learn how
         many rows there are); no guide is copied.  -> (idx, mit, cfd) as numpy arrays: idx = the rows of .guides that
         were scored, ascending."""
@@ -599,8 +630,12 @@ class GuideSet:
         if consensus is not None:
             if consensus.guide_set is not self:
                 raise ValueError("the consensus belongs to another guide set")
-            idx = consensus.selected_tensor().to(torch.int64)
+            if bowtie is not None and bowtie.consensus is not consensus:
+                raise ValueError("the Bowtie step belongs to another consensus")
+            idx = (bowtie if bowtie is not None else consensus).selected_tensor().to(torch.int64)
             sigs = sigs[idx]
+        elif bowtie is not None:
+            raise ValueError("bowtie: only together with its consensus")
         elif only_unique:
             idx = torch.nonzero(self.guides_tensor()[:, 6] == 1).flatten()
             sigs = sigs[idx]

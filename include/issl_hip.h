@@ -513,6 +513,60 @@ int issl_genome_locate_device(issl_genome *g, const uint64_t *d_sites, size_t n,
                               size_t cap, size_t *n_total, void *stream);
 int issl_genome_close(issl_genome *g);
 
+/* ---- the Bowtie step: exact occurrences of a guide's eight reads ----------------------------------------------------- */
+/* Counterpart of src/crackling/Crackling.py:600-725 on a genome handle.  For every guide the reference aligns eight reads,
+ * the guide's 20-mer followed by AGG, CGG, GGG, TGG, AAG, CAG, GAG, TAG (variants 0..7), and counts the reads that align
+ * without a mismatch (XM:i:0), once more when a second such alignment exists (XS:i:0).  Here the same figures are exact
+ * counts over the text:
+ *   occurrence  of read r: (record, pos, strand) with seq[pos:pos+23] == r (strand 0) or == the reverse complement of r
+ *               (strand 1); pos is 0-based in the record's sequence as for issl_location, the window lies inside one record
+ *               and holds A, C, G, T only.  One start can be an occurrence on both strands (of different reads)
+ *   sites       n packed 20-mer signatures (issl_encode_guides), duplicates allowed
+ *   page_length the reference works through its guides in pages of this many (Paginator.py; 0: one page); sites are the
+ *               guides in that order
+ *   verdicts    the reference reads Bowtie's output in groups of eight lines, one group per guide, and files the reads of
+ *               a page under their text.  The guide a group speaks about is looked up under the sequence its first line
+ *               prints -- read 0, reverse-complemented when it aligned to strand 1 -- and then under that sequence's
+ *               reverse complement.  So a group names the LAST site of its page with its own 20-mer, except when its
+ *               read 0 first occurs on strand 1 and the 20 characters that start that occurrence (C, C, T and the guide's
+ *               bases 19..3 complemented) are the 20-mer of a site of the page and the last three one of the eight PAMs
+ *               (the guide starts with C and C or T): then it names the last site of the page with THAT 20-mer.  The
+ *               window CCT N{18} NGG, a guide on both strands, is the common case: the group of the strand-1 guide sets
+ *               the verdict of the strand-0 guide.  The named site receives the group's verdict (its nb > 1 rejects),
+ *               chromosome and position; of several groups that name one site the last wins; a site that no group names
+ *               stays untested.  This is kept as the reference does it
+ * rows[k] answers sites[k].  The output is deterministic: the same bytes on every run, and no row depends on how the
+ * call is cut into pieces (of 2^22 sites, each of which scans the text once).  n == 0: ISSL_OK, nothing is written.  NULL
+ * arguments and a signature with bits above its 20 bases: ISSL_E_ARG, checked before any row is written.  More than
+ * 2^32 - 2 sites in one call: ISSL_E_UNSUPPORTED.  No device: ISSL_E_DEVICE (no CPU fallback).  ISSL_LOCATE_TIMING=1
+ * prints one stderr line per piece with the stage times and the counters of the scan, and one for the verdicts.
+ * What a real Bowtie2 run can answer differently: it may miss a second perfect alignment within its effort limits; for a
+ * read 0 without a perfect occurrence it reports its best inexact alignment where record is 0xFFFFFFFF here; among equal
+ * alignments it picks at random where this step reports the least (record, pos, strand). */
+typedef struct {
+    uint64_t pos;          /* first occurrence of read 0 of the source's 20-mer in (record, pos, strand) order -- the site's own
+                              when no group names it: 0-based start; 0 when there is none */
+    uint32_t record;       /* its record; 0xFFFFFFFF when there is none */
+    uint32_t n_perfect;    /* occurrences of all eight reads of the site's 20-mer, saturating */
+    uint8_t aligned;       /* bit v: read v of the site's 20-mer has at least one occurrence */
+    uint8_t repeated;      /* bit v: read v has at least two */
+    uint8_t nb;            /* popcount(aligned) + popcount(repeated): the reference's nb_occurences of the site's own group */
+    uint8_t strand;        /* of the occurrence pos and record name; 0 when there is none */
+    uint8_t owner;         /* 1: a group names this site (source is valid) */
+    uint8_t code;          /* passedBowtie: 2 (untested, '?') when owner == 0; else 0 (rejected) when the source's nb > 1, else 1 */
+    uint8_t reserved[2];   /* 0 */
+    uint32_t source;       /* the site whose group set this verdict: the last one that names this site; 0xFFFFFFFF when none.
+                              source == k, or another site with the same 20-mer, unless the rule above applies */
+    uint32_t reserved2;    /* 0 */
+} issl_occurrence;         /* 32 bytes, no padding */
+
+/* Sites and rows in host memory.  Blocking. */
+int issl_genome_occurrences(issl_genome *g, const uint64_t *sites, size_t n, size_t page_length, issl_occurrence *rows);
+/* Same with sites and rows in the memory of the handle's device, on `stream` (may be NULL); the sites are not copied to
+ * the host and not changed, and the call returns when the rows are written. */
+int issl_genome_occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, size_t page_length, issl_occurrence *d_rows,
+                                   void *stream);
+
 /* ---- candidate guides from FASTA: Crackling's extraction step ------------------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:151-305: the candidate 23-mers of the inputs, on `device`; no CPU fallback.
  *   inputs    files[i]/lens[i]: the bytes of FASTA files, taken in the order given.  Lines end at "\n", "\r\n" or a lone
