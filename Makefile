@@ -1,5 +1,5 @@
 # Build of the MI355X ISSL scorer: libissl_hip.so (C ABI, include/issl_hip.h; libissl_hip.map keeps every other symbol
-# out of its dynamic table), the three drop-in executables, isslReportOfftargets, isslLocateOfftargets, isslIndexFromFasta, cracklingGuides and cracklingBowtie.  hipcc cross-compiles for gfx950 without a GPU present.
+# out of its dynamic table), the three drop-in executables, isslReportOfftargets, isslLocateOfftargets, isslIndexFromFasta, cracklingGuides, cracklingBowtie and countHitTranscripts.  hipcc cross-compiles for gfx950 without a GPU present.
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC     = crackling_amd/csrc
@@ -9,12 +9,12 @@ CXXFLAGS = -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result
 HIPFLAGS = $(CXXFLAGS) --offload-arch=$(ARCH)
 LIB      = crackling_amd/libissl_hip.so
 
-all: $(LIB) bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOfftargets bin/isslCreateIndex bin/extractOfftargets bin/isslIndexFromFasta bin/cracklingGuides bin/cracklingBowtie
+all: $(LIB) bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOfftargets bin/isslCreateIndex bin/extractOfftargets bin/isslIndexFromFasta bin/cracklingGuides bin/cracklingBowtie bin/countHitTranscripts
 
 # The library: one object per source under build/obj/, the same flags for kernels and host code; the header dependencies
 # come from the compiler (-MMD -MP).
 SRCS = issl_kernels.hip issl_bin.hip issl_verify.hip issl_group.hip issl_replay.hip issl_report.hip issl_extract.hip \
-       issl_locate.hip issl_occur.hip issl_guides.hip issl_consensus.hip issl_build.hip issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
+       issl_locate.hip issl_occur.hip issl_guides.hip issl_consensus.hip issl_build.hip issl_transcripts.hip issl_annotation.cpp issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
 OBJDIR = build/obj
 OBJS   = $(addprefix $(OBJDIR)/,$(addsuffix .o,$(basename $(SRCS))))
 COMPILE = $(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<
@@ -54,6 +54,11 @@ bin/cracklingGuides: $(CSRC)/cli_guides.cpp include/issl_hip.h $(LIB)
 
 # the Bowtie step for a list of guides (exact occurrences of their eight reads): host-only, the library through dlopen
 bin/cracklingBowtie: $(CSRC)/cli_bowtie.cpp include/issl_hip.h $(LIB)
+	@mkdir -p bin
+	g++ $(CXXFLAGS) -o $@ $< -ldl
+
+# transcript hit counts for Crackling's output file (countHitTranscripts.py): host-only, the library through dlopen
+bin/countHitTranscripts: $(CSRC)/cli_transcripts.cpp include/issl_hip.h $(LIB)
 	@mkdir -p bin
 	g++ $(CXXFLAGS) -o $@ $< -ldl
 

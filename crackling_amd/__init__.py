@@ -46,7 +46,15 @@ from .bowtie import (  # noqa: F401
     read_bowtie_output,
 )
 
+from .transcripts import (  # noqa: F401
+    TRANSCRIPT_HITS_DTYPE,
+    Annotation,
+    TranscriptHits,
+    format_hits,
+)
+
 __all__ = [
+    "TRANSCRIPT_HITS_DTYPE", "Annotation", "TranscriptHits", "format_hits",
     "BOWTIE_PAMS", "BowtieStep", "OCCURRENCE_DTYPE", "bowtie_input", "format_columns", "read_bowtie_output",
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",
     "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",

@@ -182,6 +182,15 @@ _protos = {
     "issl_consensus_copy": (C.c_int, [_P, _P, C.c_size_t]),
     "issl_consensus_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), _u64p]),
     "issl_consensus_close": (C.c_int, [_P]),
+    "issl_annotation_open": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(_P)]),
+    "issl_annotation_open_file": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
+    "issl_annotation_info": (C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    "issl_annotation_seq": (C.c_int, [_P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "issl_annotation_lookup": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "issl_annotation_hits": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
+    "issl_annotation_hits_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
+    "issl_annotation_hits_occurrences_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
+    "issl_annotation_close": (C.c_int, [_P]),
     "issl_node_create": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "issl_node_score": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P]),
     "issl_node_get_info": (C.c_int, [_P, C.POINTER(NodeInfo)]),

@@ -150,6 +150,12 @@ class BowtieStep:
         """format_columns() of the rows, with the names of the genome's records."""
         return format_columns(self.rows, [name.decode(errors="replace") for name, _ in self.genome.records])
 
+    def transcripts(self, annotation):
+        """The `hits` column of countHitTranscripts.py for the rows of this step (transcripts.TranscriptHits): answered
+        from the rows where they lie, the result stays on the device."""
+        from .transcripts import TranscriptHits
+        return TranscriptHits(self, annotation)
+
     def selected_tensor(self):
         """int32 CUDA tensor: the rows of the guide set the reference's filter passes on to off-target scoring
         (Crackling.py:85-87, :144-146).  At medium and high these are the consensus selection without the rows Bowtie

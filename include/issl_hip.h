@@ -685,6 +685,72 @@ int issl_consensus_device(const issl_consensus *c, const issl_consensus_row **d_
                           uint64_t *n_selected);
 int issl_consensus_close(issl_consensus *c);
 
+/* ---- transcript hit counts: how many transcripts of its gene a located guide cuts ------------------------------------ */
+/* Counterpart of src/crackling/utils/countHitTranscripts.py (loadAnnotation :45-146, countTranscripts :148-193, process
+ * :197-243): a GFF3 annotation is parsed on the host and resolved on `device` into one answer per elementary segment of
+ * every sequence; a query is then a binary search.  No CPU fallback.  The reference's rules, quirks included:
+ *   lines       end at "\n", "\r\n" or a lone "\r"; a line is split on TAB and every field stripped (Python's str.strip() on
+ *               ASCII; bytes above 127 pass through as they stand, where Python decodes them first).  A line that does not
+ *               give exactly 9 fields is skipped: comments and blank lines among them
+ *   names       every '.' of the sequence name becomes '_'; the name a QUERY gives is not changed
+ *   attributes  split on ';'; key = the text ahead of the first '=', value = the text between the first and the second;
+ *               keys are not stripped, a later key overrides an earlier one.  An attribute without '=' -- a trailing ';'
+ *               or an empty column is one -- stops the reference on a line of any type: ISSL_E_FORMAT
+ *   counted     a line counts when it has both ID and Parent and its type is gene, mRNA or exon (a usual gene line has no
+ *               Parent and is skipped).  Sequences are listed in the order they first appear on a counted line
+ *   transcripts of a sequence, in the order they first appear on it: an mRNA line (its ID) or an exon line (its Parent).  The
+ *               same ID on two sequences is two transcripts.  A transcript's ordinal counts first appearances over the whole
+ *               file, so the transcripts of one sequence keep the reference's order
+ *   genes       a transcript's gene is the Parent of the FIRST mRNA line anywhere in the file with its ID; a gene's total
+ *               counts every mRNA line with that Parent, duplicates included
+ *   exons       an exon adds (int(start), int(end)) to its transcript: an optional sign and ASCII digits within int64 here,
+ *               anything else is ISSL_E_FORMAT (Python's int() also takes blanks, underscores, other digits and any size).
+ *               start > end contains nothing
+ *   query       (sequence, start): a transcript is hit when one of its exons has start <= q <= end, and counts once.  No
+ *               hit, a sequence the annotation lacks ('*' is a name like any other) and a negative start: 0/0.  When the hit
+ *               transcripts that have a gene name more than one, the reference raises: '?/?' (status 2).  Otherwise the
+ *               gene is that of the FIRST hit transcript in the sequence's order; when that one never had an mRNA line the
+ *               reference gets a KeyError: '?/?' (status 3).  Otherwise hit / the gene's total, hit counting the transcripts
+ *               without an mRNA line too: 2/1 is possible
+ * Bounds: exon coordinates that can contain a position >= 0 lie in [0, 2^40 - 2] after a negative start is raised to 0 and
+ * an exon that ends below 0 is dropped; fewer than 2^24 sequences; at most 2^32 - 1 (segment, transcript) pairs while the
+ * answers are built.  Beyond: ISSL_E_UNSUPPORTED.  The reference writes <annotation>.p beside the GFF; nothing is written here.
+ * Errors: parsing comes before any device call, so a malformed file is ISSL_E_FORMAT with or without a GPU; then no device:
+ * ISSL_E_DEVICE.  NULL arguments: ISSL_E_ARG; n == 0: ISSL_OK, nothing is written; *out is NULL after a failed open.  An
+ * annotation without a counted line is valid and answers 0/0 everywhere.  The output is deterministic: the same bytes on
+ * every run.  One annotation is used by one thread at a time. */
+typedef struct issl_annotation issl_annotation; /* opaque; owns device and host memory */
+typedef struct { uint32_t hit, total, status, first; } issl_transcript_hits; /* 16 bytes */
+/* status 0: hit/total as counted (0/0 included); 1: untested row ('?/?'); 2: more than one gene ('?/?');
+   3: first hit transcript has no mRNA line ('?/?').  first: ordinal of the first hit transcript among all
+   transcripts of the annotation, 0xFFFFFFFF when none.  hit is filled for status 2 and 3 too; total is 0 there. */
+int issl_annotation_open(const char *gff, size_t len, int device, issl_annotation **out);
+/* Same from a file on disk; a file that cannot be read: ISSL_E_IO. */
+int issl_annotation_open_file(const char *path, int device, issl_annotation **out);
+/* n_exons: exon lines counted; n_segments: the stretches between neighbouring breakpoints of a sequence, summed over the
+ * sequences -- a breakpoint is a start or an end + 1 of a transcript's exons, joined first where they overlap. */
+int issl_annotation_info(const issl_annotation *a, uint64_t *n_seqs, uint64_t *n_transcripts, uint64_t *n_genes,
+                         uint64_t *n_exons, uint64_t *n_segments);
+/* Name of sequence k, '.' already replaced; valid until the annotation is closed, not terminated. */
+int issl_annotation_seq(const issl_annotation *a, uint64_t k, const char **name, size_t *name_len);
+int issl_annotation_lookup(const issl_annotation *a, const char *name, size_t name_len, uint32_t *seq); /* 0xFFFFFFFF: absent; the name is NOT '.'->'_' translated */
+/* seq[i]: index from issl_annotation_lookup (0xFFFFFFFF or any index the annotation lacks: 0/0); start[i]: bowtieStart.
+ * Host memory.  Blocking. */
+int issl_annotation_hits(issl_annotation *a, const uint32_t *seq, const int64_t *start, size_t n, issl_transcript_hits *out);
+/* Same with all arrays in the memory of the annotation's device, enqueued on `stream` (may be NULL); the call does not wait. */
+int issl_annotation_hits_device(issl_annotation *a, const uint32_t *d_seq, const int64_t *d_start, size_t n,
+                                issl_transcript_hits *d_out, void *stream);
+/* The rows of issl_genome_occurrences_device as they lie in device memory: code == 2 is an untested row (status 1).
+ * Otherwise the row is asked as the reference prints it: a record's name up to the first blank, as Bowtie2 names it, with
+ * start = pos + 1; for record 0xFFFFFFFF -- the guide's read 0 does not occur -- the name '*' with start 0 ('*', 0, 22 in
+ * Crackling's output), which hits only when the annotation has a sequence called '*'.  The genome must be on the
+ * annotation's device.  Returns when the answers are written.
+ * ISSL_ANNOTATION_TIMING=1 (read by issl_annotation_open*): one stderr line per open with the host clock around the parse,
+ * the interval merge and the device build, which ends in a synchronise. */
+int issl_annotation_hits_occurrences_device(issl_annotation *a, const issl_genome *g, const issl_occurrence *d_rows,
+                                            size_t n, issl_transcript_hits *d_out, void *stream);
+int issl_annotation_close(issl_annotation *a);
+
 #ifdef __cplusplus
 }
 #endif
