@@ -53,7 +53,15 @@ from .transcripts import (  # noqa: F401
     format_hits,
 )
 
+from .results import (  # noqa: F401
+    ResultTable,
+    read_rnafold_text,
+    repr_f64,
+)
+from . import pipeline  # noqa: F401
+
 __all__ = [
+    "ResultTable", "read_rnafold_text", "repr_f64", "pipeline",
     "TRANSCRIPT_HITS_DTYPE", "Annotation", "TranscriptHits", "format_hits",
     "BOWTIE_PAMS", "BowtieStep", "OCCURRENCE_DTYPE", "bowtie_input", "format_columns", "read_bowtie_output",
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",

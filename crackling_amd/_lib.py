@@ -84,6 +84,16 @@ class ConsensusConfig(C.Structure):
                 ("intercept", C.c_double), ("sgrna_threshold", C.c_double), ("low_energy", C.c_double), ("high_energy", C.c_double)]
 
 
+class ResultsConfig(C.Structure):
+    """issl_results_config."""
+    _fields_ = [("delimiter", C.c_char), ("flags", C.c_uint32), ("method", C.c_char_p), ("threshold", C.c_double)]
+
+
+class TextSpan(C.Structure):
+    """issl_text_span: 16 bytes."""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_guides", C.c_uint64), ("candidates", C.c_uint64), ("hits", C.c_uint64), ("scan_tiles", C.c_uint64),
@@ -191,6 +201,15 @@ _protos = {
     "issl_annotation_hits_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
     "issl_annotation_hits_occurrences_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
     "issl_annotation_close": (C.c_int, [_P]),
+    "issl_results_build": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t,
+                                     C.POINTER(ResultsConfig), C.POINTER(_P)]),
+    "issl_results_info": (C.c_int, [_P, _u64p, _u64p, C.POINTER(C.c_uint32)]),
+    "issl_results_times": (C.c_int, [_P, _f64p, _f64p, _f64p]),
+    "issl_results_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "issl_results_copy": (C.c_int, [_P, _P, C.c_size_t]),
+    "issl_results_write": (C.c_int, [_P, C.c_char_p, C.c_int]),
+    "issl_results_close": (C.c_int, [_P]),
+    "issl_repr_f64_device": (C.c_int, [_P, C.c_size_t, _P, _P, _P]),
     "issl_node_create": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "issl_node_score": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P]),
     "issl_node_get_info": (C.c_int, [_P, C.POINTER(NodeInfo)]),

@@ -751,6 +751,79 @@ int issl_annotation_hits_occurrences_device(issl_annotation *a, const issl_genom
                                             size_t n, issl_transcript_hits *d_out, void *stream);
 int issl_annotation_close(issl_annotation *a);
 
+/* ---- the result table: Crackling's output file from the resident stages ---------------------------------------------- */
+/* Counterpart of src/crackling/Crackling.py:263-268 (the header row) and :842-852 (one CSV row of the 26 columns of
+ * Constants.py:42-70 per candidate guide, csv.writer with dialect 'unix', QUOTE_MINIMAL, quote character '"'): the text is
+ * written on the set's device -- every row measured, the lengths summed, every workgroup's rows assembled in LDS and stored as
+ * one span -- and stays there; no CPU fallback.  One batch is the whole guide set: the reference's file whenever [input]
+ * batch-size is at least the number of guides (smaller batches cut its pages elsewhere and are not modelled).
+ *   rows       those of the guide set, in its order, behind the header row; lines end in "\n"
+ *   seq .. isUnique   the 23-mer; for seen == 1 the record's header line (issl_guides_record), start, start + 23, '+' / '-'
+ *              and 1, otherwise '-' four times and 0 (:292-303)
+ *   codes      of issl_consensus_row: 0, 1, ? (untested), ! (error); consensusCount is the row's count; AT and
+ *              sgrnascorer2score are '?' for NaN, otherwise the double as Python's repr prints it: the shortest decimal that
+ *              reads back as the same double, fixed notation for 1e-4 <= |x| < 1e16 with at least one digit behind the point,
+ *              otherwise d[.ddd]e+XX / e-XX with at least two exponent digits; -0.0, inf, -inf, nan
+ *   ssL1, ssStructure, ssEnergy   text, not numbers (:469-474): three spans of `ss_text` per row of the consensus' fold list,
+ *              in its order; length UINT32_MAX leaves '?'; ss_spans == NULL leaves '?' everywhere
+ *   bowtie     passedBowtie, bowtieChr, bowtieStart, bowtieEnd from issl_occurrence rows aligned with the consensus'
+ *              selection: '?' four times for a row outside it, for code 2 and when d_bowtie is NULL; the code, '*', 0, 22
+ *              without a record; otherwise the code, the genome record's name up to its first blank (space, TAB, LF, VT, FF,
+ *              CR), pos + 1, pos + 23
+ *   scores     mitOfftargetscore, cfdOfftargetscore, passedOffTargetScore for the rows d_scored lists (ascending row
+ *              indices of the set), '?' for the others and when d_scored is NULL.  A score goes through the scorer's text as
+ *              in the reference (:785-786): R = float("%f" % x), exactly (round(x * 10^6) ties to even on the binary value,
+ *              one IEEE division by 10^6; x in [0, 2^32), anything else is taken as it is), printed as repr(R); a score
+ *              `method` does not ask for is -1.0 (matched exactly as the scorer does: "AND" prints -1.0 twice); the verdict
+ *              applies :794-835 to R under the lower-cased, stripped method, and stays '?' when that names no rule
+ *   quoting    header, bowtieChr and the three ss columns are quoted when they contain the delimiter, '"', LF or CR, an
+ *              embedded '"' doubled.  Delimiters: ',', TAB, ';', '|' and ' ' -- none of which a number or a code contains;
+ *              any other: ISSL_E_UNSUPPORTED
+ * Errors: ISSL_E_ARG for NULL pointers, spans outside ss_text, n_folds / n_bowtie that differ from the fold list / the
+ * selection, n_scored above the number of guides, d_bowtie without a genome (or one on another device) and d_scored without both
+ * scores, all before any device call; ISSL_E_STATE for an unfinished consensus; ISSL_E_DEVICE without a device.  An empty set
+ * gives the header row only.  The output is deterministic: the same bytes on every run.  The guide set, the consensus and the
+ * arrays are read while the call runs and not kept. */
+typedef struct issl_results issl_results; /* opaque; owns device memory */
+typedef struct {
+    uint64_t offset;   /* into ss_text */
+    uint32_t length;   /* bytes; 0xFFFFFFFF: no text, the column keeps '?' */
+    uint32_t reserved; /* 0 */
+} issl_text_span;      /* 16 bytes */
+enum {
+    ISSL_RESULTS_DIRECT = 1,  /* every row is stored straight to global memory by its thread (the path rows larger than the
+                                 staging buffer take); same bytes.  Tests and A/B */
+    ISSL_RESULTS_NO_SGRNA = 2 /* sgrnascorer2score is '?' in every row: the A/B that prices its repr (tools/bench_results.py) */
+};
+typedef struct {
+    char delimiter;     /* [output] delimiter */
+    uint32_t flags;     /* ISSL_RESULTS_* */
+    const char *method; /* [offtargetscore] method as configured */
+    double threshold;   /* [offtargetscore] score-threshold */
+} issl_results_config;
+
+int issl_results_build(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
+                       const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
+                       const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
+                       size_t n_scored, const issl_results_config *cfg, issl_results **out);
+/* n_rows: the guides (the header row is not counted); n_bytes: the whole text; rows_per_group: the rows one workgroup
+ * assembles (a property of the build, for tests that place sizes around it).  Any output may be NULL. */
+int issl_results_info(const issl_results *r, uint64_t *n_rows, uint64_t *n_bytes, uint32_t *rows_per_group);
+/* Device time of the build's three launches in milliseconds, by HIP events on their stream (0 for an empty set): the
+ * measuring kernel, the scan of the workgroups' sums, the emitting kernel.  Any output may be NULL. */
+int issl_results_times(const issl_results *r, double *ms_measure, double *ms_scan, double *ms_emit);
+/* The text and the n_rows + 1 row offsets in device memory, valid until close: row k is d_text[d_offsets[k] ..
+ * d_offsets[k + 1]), d_offsets[0] is the length of the header row, d_offsets[n_rows] == n_bytes. */
+int issl_results_device(const issl_results *r, const char **d_text, const uint64_t **d_offsets);
+/* The text to host memory; cap below n_bytes: ISSL_E_ARG. */
+int issl_results_copy(const issl_results *r, char *out, size_t cap);
+/* The text into the file at `path`, appended when append != 0 (the reference opens its file "a+"); ISSL_E_IO. */
+int issl_results_write(const issl_results *r, const char *path, int append);
+int issl_results_close(issl_results *r);
+/* repr() of n doubles in device memory: value i into d_text[32 i .. 32 i + d_len[i]), the rest of its 32 bytes zero (a repr
+ * has at most 24 characters).  Enqueued on `stream` (may be NULL) on the current device; the call does not wait. */
+int issl_repr_f64_device(const double *d_values, size_t n, char *d_text, uint32_t *d_len, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
