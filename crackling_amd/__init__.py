@@ -54,6 +54,7 @@ from .transcripts import (  # noqa: F401
 )
 
 from .results import (  # noqa: F401
+    PackedFolds,
     ResultTable,
     read_rnafold_text,
     repr_f64,
@@ -61,7 +62,7 @@ from .results import (  # noqa: F401
 from . import pipeline  # noqa: F401
 
 __all__ = [
-    "ResultTable", "read_rnafold_text", "repr_f64", "pipeline",
+    "PackedFolds", "ResultTable", "read_rnafold_text", "repr_f64", "pipeline",
     "TRANSCRIPT_HITS_DTYPE", "Annotation", "TranscriptHits", "format_hits",
     "BOWTIE_PAMS", "BowtieStep", "OCCURRENCE_DTYPE", "bowtie_input", "format_columns", "read_bowtie_output",
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",

@@ -177,6 +177,8 @@ _protos = {
     "issl_genome_locate_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "issl_genome_occurrences": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P]),
     "issl_genome_occurrences_device": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
+    "issl_genome_occurrences_paged": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "issl_genome_occurrences_paged_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, _P]),
     "issl_genome_close": (C.c_int, [_P]),
     "issl_guides_extract": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(_P)]),
     "issl_guides_extract_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(_P)]),
@@ -191,6 +193,7 @@ _protos = {
     "issl_consensus_finish": (C.c_int, [_P, _P, C.c_size_t]),
     "issl_consensus_copy": (C.c_int, [_P, _P, C.c_size_t]),
     "issl_consensus_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), _u64p]),
+    "issl_consensus_selection_pages": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(_P), _u64p]),
     "issl_consensus_close": (C.c_int, [_P]),
     "issl_annotation_open": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(_P)]),
     "issl_annotation_open_file": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
@@ -203,6 +206,8 @@ _protos = {
     "issl_annotation_close": (C.c_int, [_P]),
     "issl_results_build": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t,
                                      C.POINTER(ResultsConfig), C.POINTER(_P)]),
+    "issl_results_build_rows": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t,
+                                          C.c_uint64, C.c_uint64, C.POINTER(ResultsConfig), C.POINTER(_P)]),
     "issl_results_info": (C.c_int, [_P, _u64p, _u64p, C.POINTER(C.c_uint32)]),
     "issl_results_times": (C.c_int, [_P, _f64p, _f64p, _f64p]),
     "issl_results_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),

@@ -36,10 +36,12 @@ def bowtie_input(guides23):
     return "".join(g[:20] + pam + "\n" for g in guides23 for pam in BOWTIE_PAMS)
 
 
-def read_bowtie_output(sam_text, guides23, record_names=(), page_length=0):
+def read_bowtie_output(sam_text, guides23, record_names=(), page_length=0, page_starts=None):
     """Bowtie2's SAM output (--reorder --no-hd) as the reference reads it (Crackling.py:659-720) -> OCCURRENCE_DTYPE array,
     one row per guide of `guides23` (distinct 23-mers in the order their reads were written).  sam_text: the output of all
-    pages, one behind the other; page_length: the [bowtie2] page-length of the run (0: one page).
+    pages, one behind the other; page_length: the [bowtie2] page-length of the run (0: one page); page_starts: in its
+    place, the boundaries of pages of any length -- n_pages + 1 positions from 0 to len(guides23), never decreasing --
+    for a run in batches, whose pages start again with every batch (BowtieStep.page_starts).
 
     Per page the reads are filed under their text, a later guide replacing an earlier one with the same 20-mer.  The lines
     come in groups of eight.  A group's guide is looked up under the SEQ of its first line, then under its reverse
@@ -81,7 +83,14 @@ def read_bowtie_output(sam_text, guides23, record_names=(), page_length=0):
         row["source"] = NO_RECORD
         return first[9], row
 
-    for a, b in _pages(len(guides23), page_length):
+    if page_starts is None:
+        pages = _pages(len(guides23), page_length)
+    else:
+        starts = [int(x) for x in page_starts]
+        if not starts or starts[0] != 0 or starts[-1] != len(guides23) or any(a > b for a, b in zip(starts, starts[1:])):
+            raise ValueError(f"page_starts: boundaries from 0 to {len(guides23)} that never decrease")
+        pages = list(zip(starts, starts[1:]))
+    for a, b in pages:
         filed = {}
         for k in range(a, b):
             for pam in BOWTIE_PAMS:
@@ -121,19 +130,25 @@ def format_columns(rows, record_names):
 class BowtieStep:
     """The Bowtie step over the selection of a finished Consensus (Consensus.bowtie).  `rows`: OCCURRENCE_DTYPE array
     aligned with consensus.selected; `columns()`: the reference's four columns; `selected_tensor()`: the rows that go on
-    to off-target scoring.  The signatures are gathered and the rows written on the device."""
+    to off-target scoring.  The signatures are gathered and the rows written on the device.  batch_size: [input]
+    batch-size; above 0 the pages start again with every batch of that many rows of the guide set, and `page_starts` keeps
+    their boundaries in positions of the selection (an int64 CUDA tensor of its own; None for one batch, whose pages are
+    page_length each)."""
 
-    def __init__(self, consensus, genome, page_length=0):
+    def __init__(self, consensus, genome, page_length=0, batch_size=0):
         import torch
         if not consensus.finished:
             raise ValueError("the consensus is not finished")
         self.consensus = consensus
         self.genome = genome
         self.page_length = int(page_length)
+        self.batch_size = int(batch_size)
+        self.page_starts = consensus.selection_pages(self.batch_size, self.page_length).clone() if self.batch_size > 0 else None
         sel = consensus.selected_tensor()
         sigs = consensus.guide_set.sigs_tensor()[sel.to(torch.int64)].contiguous()
         self._d_rows = torch.empty((sigs.numel(), OCCURRENCE_DTYPE.itemsize), dtype=torch.uint8, device=sigs.device)
-        genome.occurrences_device(sigs, self._d_rows, self.page_length, stream=torch.cuda.current_stream(sigs.device).cuda_stream)
+        genome.occurrences_device(sigs, self._d_rows, self.page_length, stream=torch.cuda.current_stream(sigs.device).cuda_stream,
+                                  page_starts=self.page_starts)
         self._rows = None
 
     def rows_tensor(self):

@@ -169,11 +169,22 @@ class Consensus:
             self._selected = self.selected_tensor().cpu().numpy().astype(np.uint32)
         return self._selected
 
-    def bowtie(self, genome, page_length=0):
+    def selection_pages(self, batch_size, page_length):
+        """The reference's pages of the Bowtie step for a run in batches of batch_size rows of the set ([input] batch-size;
+        0: one batch) with [bowtie2] page-length page_length (0: one page per batch): int64 CUDA tensor of n_pages + 1
+        boundaries in positions of the selection, made on the device.  The tensor is valid until the next call or close()."""
+        import torch
+        from .scorer import _DeviceArray
+        d_starts, n_pages = C.c_void_p(), C.c_uint64()
+        check(lib.issl_consensus_selection_pages(self._h, int(batch_size), int(page_length), C.byref(d_starts), C.byref(n_pages)))
+        return torch.as_tensor(_DeviceArray(self, d_starts.value, (n_pages.value + 1,), "<i8"), device=f"cuda:{self.device}")
+
+    def bowtie(self, genome, page_length=0, batch_size=0):
         """The Bowtie step (Crackling.py:600-725) over the selection of this finished consensus, on `genome` (a
-        crackling_amd.Genome on the same device) -> BowtieStep."""
+        crackling_amd.Genome on the same device) -> BowtieStep.  batch_size: [input] batch-size, the pages start again
+        with every batch of that many rows of the set (0: one batch)."""
         from .bowtie import BowtieStep
-        return BowtieStep(self, genome, page_length)
+        return BowtieStep(self, genome, page_length, batch_size)
 
     def close(self):
         if self._h:

@@ -17,7 +17,9 @@
 // A support vector is 24 bytes here (80 mask bits, the coefficient); every lane of a wave reads the same one, so the
 // loads are scalar and a guide costs three popcounts, a conversion, a multiply and an add per support vector.  Products
 // and sums are rounded one by one (__dmul_rn, __dadd_rn: no contraction), as libsvm built without FMA rounds them.
-// The host waits once per list, for its length.
+//   pages    issl_consensus_selection_pages: the reference's Bowtie pages of a run in batches, as boundaries in the
+//            selection (k_pages_edges, k_pages_count, launch_scan, k_pages_fill further down)
+// The host waits once per list, for its length, and once per set of pages, for their number.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -242,6 +244,55 @@ __global__ __launch_bounds__(kThreads) void k_consensus_finish(const ulonglong2 
     count_block(selected, counts);
 }
 
+// ---- the pages of a batched run (issl_consensus_selection_pages) ---------------------------------------------------
+// A batch is rows [b B, min((b + 1) B, n)) of the set, and the reference's pages start again with every batch: its
+// boundaries, in positions of the ascending selection.  k_pages_edges: one lower bound per batch edge; k_pages_count:
+// the pages of every batch; launch_scan: the pages ahead of every batch; k_pages_fill: one thread per PAGE finds its
+// batch in those offsets, so one batch cut into 10^8 pages of one row is no more work per thread than any other.
+
+// edges[e] = selected rows below row min(e * batch, n) of the set, e = 0 .. n_batches.
+__global__ __launch_bounds__(kThreads) void k_pages_edges(const uint32_t *__restrict__ selection, uint32_t n_selected, uint64_t n,
+                                                          uint64_t batch, uint32_t n_batches, uint32_t *__restrict__ edges)
+{
+    const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+    if (e > n_batches) return;
+    const uint64_t row = e == n_batches || e * batch > n ? n : e * batch; // (e * batch < 2^64: e > 0 only with batch < n < 2^32)
+    uint32_t a = 0, b = n_selected; // first position with selection[a] >= row
+    while (a < b) {
+        const uint32_t mid = a + ((b - a) >> 1);
+        if (selection[mid] < row) a = mid + 1;
+        else b = mid;
+    }
+    edges[e] = a;
+}
+
+// counts[b] = pages of batch b: its selected rows in pages of page_length, or one page when it has any (page_length 0).
+__global__ __launch_bounds__(kThreads) void k_pages_count(const uint32_t *__restrict__ edges, uint32_t n_batches, uint64_t page_length,
+                                                          uint32_t *__restrict__ counts)
+{
+    const uint32_t b = blockIdx.x * kThreads + threadIdx.x;
+    if (b >= n_batches) return;
+    const uint64_t rows = edges[b + 1] - edges[b];
+    counts[b] = static_cast<uint32_t>(page_length ? (rows + page_length - 1) / page_length : (rows ? 1u : 0u));
+}
+
+// first[b] = pages ahead of batch b, first[n_batches] = all pages.  starts[p] for p < all pages, starts[all pages] = n_selected;
+// the grid covers `cap`, the host's upper bound of the pages, and one more.
+__global__ __launch_bounds__(kThreads) void k_pages_fill(const uint32_t *__restrict__ edges, const uint32_t *__restrict__ first,
+                                                         uint32_t n_batches, uint64_t page_length, uint32_t n_selected,
+                                                         uint64_t cap, uint64_t *__restrict__ starts)
+{
+    const uint64_t p = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    const uint64_t n_pages = first[n_batches];
+    if (p > n_pages || p > cap) return;
+    if (p == n_pages) {
+        starts[p] = n_selected;
+        return;
+    }
+    const uint32_t b = last_not_above(first, n_batches, p); // behind the batches without a page: first[b] <= p < first[b + 1]
+    starts[p] = edges[b] + (p - first[b]) * page_length;
+}
+
 struct OwnedStream {
     hipStream_t s = nullptr;
     OwnedStream() = default;
@@ -260,6 +311,7 @@ struct issl_consensus {
     issl::Config cfg{};
     issl::OwnedStream stream;             // ahead of the buffers: they are released first
     issl::DevBuf rows, counts, sv, fold_list, selection;
+    issl::DevBuf pages;                   // the boundaries of the last issl_consensus_selection_pages
     uint64_t n_fold = 0, n_selected = 0;
     bool finished = false;
 };
@@ -370,6 +422,51 @@ int consensus_finish(issl_consensus *c, const issl_fold *folds)
     return ISSL_OK;
 }
 
+int consensus_selection_pages(issl_consensus *c, uint64_t batch_size, uint64_t page_length, const uint64_t **d_page_starts,
+                              uint64_t *n_pages)
+{
+    if (int rc = use_device(c->device)) return rc;
+    c->pages.release();
+    const uint64_t n = c->n;
+    const uint32_t n_selected = static_cast<uint32_t>(c->n_selected);
+    if (n == 0) { // no batch: no page, and the one boundary that ends them
+        EX_HIP_TRY(hipMalloc(&c->pages.p, 8));
+        EX_HIP_TRY(hipMemset(c->pages.p, 0, 8));
+        *d_page_starts = static_cast<const uint64_t *>(c->pages.p);
+        *n_pages = 0;
+        return ISSL_OK;
+    }
+    hipStream_t stream = c->stream.s;
+    const uint32_t n_batches = batch_size == 0 || batch_size >= n ? 1u : static_cast<uint32_t>((n + batch_size - 1) / batch_size);
+    // a batch with r selected rows has at most r / page_length + 1 pages and none without a row
+    const uint64_t by_length = page_length ? n_selected / page_length + n_batches : n_batches;
+    const uint64_t cap = by_length < n_selected ? by_length : n_selected;
+    Arena work;
+    const size_t o_edges = work.reserve(4 * (n_batches + 1ull)), o_counts = work.reserve(4 * scan_words(n_batches + 1ull));
+    EX_HIP_TRY(hipMalloc(&work.buf.p, work.size));
+    EX_HIP_TRY(hipMalloc(&c->pages.p, 8 * (cap + 1)));
+    uint32_t *edges = work.at<uint32_t>(o_edges), *counts = work.at<uint32_t>(o_counts);
+    uint64_t *starts = static_cast<uint64_t *>(c->pages.p);
+    EX_HIP_TRY(hipMemsetAsync(counts + n_batches, 0, 4, stream));
+    hipLaunchKernelGGL(k_pages_edges, dim3(static_cast<uint32_t>((n_batches + 1ull + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
+                       static_cast<const uint32_t *>(c->selection.p), n_selected, n, batch_size, n_batches, edges);
+    hipLaunchKernelGGL(k_pages_count, dim3(blocks_of(n_batches)), dim3(kThreads), 0, stream, edges, n_batches, page_length, counts);
+    launch_scan(counts, n_batches + 1ull, stream);
+    hipLaunchKernelGGL(k_pages_fill, dim3(static_cast<uint32_t>((cap + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, edges,
+                       counts, n_batches, page_length, n_selected, cap, starts);
+    EX_HIP_TRY(hipGetLastError());
+    uint32_t total = 0;
+    EX_HIP_TRY(hipMemcpyAsync(&total, counts + n_batches, 4, hipMemcpyDeviceToHost, stream));
+    EX_HIP_TRY(hipStreamSynchronize(stream)); // the one wait: the boundaries are written and the work buffers may go
+    if (total > cap) {
+        set_error("pages on the device: " + std::to_string(total) + ", at most " + std::to_string(cap) + " expected");
+        return ISSL_E_DEVICE;
+    }
+    *d_page_starts = starts;
+    *n_pages = total;
+    return ISSL_OK;
+}
+
 int copy_from_device(const issl_consensus *c, void *out, const void *src, size_t bytes)
 {
     EX_HIP_TRY(hipSetDevice(c->device));
@@ -443,6 +540,16 @@ int issl_consensus_device(const issl_consensus *c, const issl_consensus_row **d_
     *d_selected = static_cast<const uint32_t *>(c->selection.p);
     *n_selected = c->n_selected;
     return ISSL_OK;
+}
+
+int issl_consensus_selection_pages(issl_consensus *c, uint64_t batch_size, uint64_t page_length, const uint64_t **d_page_starts,
+                                   uint64_t *n_pages)
+{
+    if (!c || !d_page_starts || !n_pages) return issl::fail(ISSL_E_ARG, "null argument");
+    *d_page_starts = nullptr;
+    *n_pages = 0;
+    if (!c->finished) return issl::fail(ISSL_E_STATE, "the consensus is not finished");
+    return issl::abi_call([&] { return issl::consensus_selection_pages(c, batch_size, page_length, d_page_starts, n_pages); });
 }
 
 int issl_consensus_close(issl_consensus *c)

@@ -21,7 +21,10 @@
 //   targets      k_occur_target: the query whose verdict a query's group of eight SAM lines sets, as the reference looks it
 //                up (issl_hip.h: "verdicts"): the last query of the page with a given key, found by a binary search in
 //                the sorted words of the pieces the page runs over.  Of the groups that name a query the last one wins:
-//                an atomic maximum of group index + 1, which commutes
+//                an atomic maximum of group index + 1, which commutes.  A page is i / page_length, or, with explicit
+//                boundaries (issl_genome_occurrences_paged*: the pages of a batched run start again with every batch),
+//                the page whose [starts[p], starts[p + 1]) holds i, found by a binary search (k_occur_target_paged);
+//                k_occur_pages_check refuses boundaries that do not tile [0, n) before any row is written
 //   verdicts     k_occur_verdict: one thread per query completes its row from the word of its source
 // Pieces and pages change no row: a rank's state depends on the text and its key alone, and a page's queries are looked up
 // wherever they lie.  The host waits for the signature check, once per piece before its buffers are released, and at the end.
@@ -90,6 +93,16 @@ __global__ __launch_bounds__(256) void k_occur_check(const uint64_t *__restrict_
 {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i < n && (sites[i] >> 40)) *bad = 1u;
+}
+
+// *bad != 0: starts[0 .. n_pages] is not 0 = starts[0] <= starts[1] <= ... <= starts[n_pages] = n.
+__global__ __launch_bounds__(256) void k_occur_pages_check(const uint64_t *__restrict__ starts, uint64_t n_pages, uint64_t n,
+                                                           uint32_t *__restrict__ bad)
+{
+    const uint64_t p = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (p > n_pages) return;
+    const uint64_t at = starts[p];
+    if ((p == 0 && at != 0) || (p == n_pages ? at != n : starts[p + 1] < at)) *bad = 1u;
 }
 
 // ---- the scan of the text ----------------------------------------------------------------------------------------
@@ -206,15 +219,11 @@ __device__ __forceinline__ uint64_t last_with_key(const Pages &pg, uint64_t key,
     }
 }
 
-// src[t]: 1 + the last query whose group names query t, 0 when none does.
-__global__ __launch_bounds__(256) void k_occur_target(const uint64_t *__restrict__ sites, const unsigned long long *__restrict__ own,
-                                                      Pages pg, uint32_t *__restrict__ src)
+// src[t]: 1 + the last query whose group names query t, 0 when none does.  [lo, hi): the page of query i.
+__device__ __forceinline__ void note_target(const uint64_t *__restrict__ sites, const unsigned long long *__restrict__ own,
+                                            const Pages &pg, uint32_t *__restrict__ src, uint64_t i, uint64_t lo, uint64_t hi)
 {
-    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= pg.n) return;
     const uint64_t sig = sites[i];
-    const uint64_t lo = pg.page_length ? i / pg.page_length * pg.page_length : 0;
-    const uint64_t hi = pg.page_length && pg.n - lo > pg.page_length ? lo + pg.page_length : pg.n;
     uint64_t key = 0;
 #pragma unroll
     for (int p = 0; p < 20; ++p) key |= ((sig >> (2 * p)) & 3ull) << (2 * (19 - p));
@@ -231,6 +240,34 @@ __global__ __launch_bounds__(256) void k_occur_target(const uint64_t *__restrict
     }
     if (t == ~0ull) t = last_with_key(pg, key, lo, hi); // i itself at the least
     if (t != ~0ull) atomicMax(&src[t], static_cast<uint32_t>(i) + 1u);
+}
+
+__global__ __launch_bounds__(256) void k_occur_target(const uint64_t *__restrict__ sites, const unsigned long long *__restrict__ own,
+                                                      Pages pg, uint32_t *__restrict__ src)
+{
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= pg.n) return;
+    const uint64_t lo = pg.page_length ? i / pg.page_length * pg.page_length : 0;
+    const uint64_t hi = pg.page_length && pg.n - lo > pg.page_length ? lo + pg.page_length : pg.n;
+    note_target(sites, own, pg, src, i, lo, hi);
+}
+
+// The same for pages given by their boundaries (checked by k_occur_pages_check): the page of query i is the last p with
+// starts[p] <= i -- behind any empty page that starts there too -- and starts[n_pages] = n lies above every query.
+__global__ __launch_bounds__(256) void k_occur_target_paged(const uint64_t *__restrict__ sites,
+                                                            const unsigned long long *__restrict__ own, Pages pg,
+                                                            const uint64_t *__restrict__ starts, uint64_t n_pages,
+                                                            uint32_t *__restrict__ src)
+{
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= pg.n) return;
+    uint64_t a = 0, b = n_pages; // first p in [0, n_pages] with starts[p] > i: at least 1, starts[0] is 0
+    while (a < b) {
+        const uint64_t mid = (a + b) >> 1;
+        if (starts[mid] <= i) a = mid + 1;
+        else b = mid;
+    }
+    note_target(sites, own, pg, src, i, starts[a - 1], starts[a]);
 }
 
 // Row t: owner, code, source, and the first occurrence of read 0 of its source (its own when no group names it).
@@ -326,39 +363,63 @@ int occur_piece(const issl_genome *g, const uint64_t *d_all, size_t at, size_t n
     return ISSL_OK;
 }
 
-int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, size_t page_length, issl_occurrence *d_rows,
+// The pages of a call: page_length (0: one page), or, when d_starts is not null, n_pages + 1 boundaries in device memory.
+struct PageSpec {
+    size_t page_length;
+    const uint64_t *d_starts;
+    size_t n_pages;
+};
+
+int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const PageSpec &pages, issl_occurrence *d_rows,
                        hipStream_t stream)
 {
     EX_HIP_TRY(hipSetDevice(g->device));
-    if (n == 0) return ISSL_OK;
+    if (n == 0 && !(pages.d_starts && pages.n_pages)) return ISSL_OK;
     if (n >= 0xFFFFFFFFull) { // a row names its source in 32 bits
         set_error("more than 2^32 - 2 sites in one call: split the query at a page boundary");
         return ISSL_E_UNSUPPORTED;
     }
+    if (pages.d_starts && pages.n_pages >= (size_t(1) << 39)) { // (2^31 - 1 workgroups of 256; n allows no more that hold a site)
+        set_error("more than 2^39 pages in one call");
+        return ISSL_E_UNSUPPORTED;
+    }
     Arena all;
-    const size_t o_sorted = all.reserve(8 * n), o_own = all.reserve(8 * n), o_src = all.reserve(4 * n), o_bad = all.reserve(4);
+    const size_t o_sorted = all.reserve(8 * n), o_own = all.reserve(8 * n), o_src = all.reserve(4 * n), o_bad = all.reserve(8);
     EX_HIP_TRY(hipMalloc(&all.buf.p, all.size));
     uint64_t *sorted_all = all.at<uint64_t>(o_sorted);
     unsigned long long *own_all = all.at<unsigned long long>(o_own);
-    uint32_t *src = all.at<uint32_t>(o_src), *bad = all.at<uint32_t>(o_bad);
+    uint32_t *src = all.at<uint32_t>(o_src), *bad = all.at<uint32_t>(o_bad); // bad[0]: signatures, bad[1]: boundaries
     const uint32_t blocks = static_cast<uint32_t>((n + 255) / 256);
-    EX_HIP_TRY(hipMemsetAsync(bad, 0, 4, stream));
-    hipLaunchKernelGGL(k_occur_check, dim3(blocks), dim3(256), 0, stream, d_sites, static_cast<uint64_t>(n), bad);
+    EX_HIP_TRY(hipMemsetAsync(bad, 0, 8, stream));
+    if (n) hipLaunchKernelGGL(k_occur_check, dim3(blocks), dim3(256), 0, stream, d_sites, static_cast<uint64_t>(n), bad);
+    if (pages.d_starts)
+        hipLaunchKernelGGL(k_occur_pages_check, dim3(static_cast<uint32_t>(pages.n_pages / 256 + 1)), dim3(256), 0, stream,
+                           pages.d_starts, static_cast<uint64_t>(pages.n_pages), static_cast<uint64_t>(n), bad + 1);
     EX_HIP_TRY(hipGetLastError());
-    uint32_t is_bad = 0;
-    EX_HIP_TRY(hipMemcpyAsync(&is_bad, bad, 4, hipMemcpyDeviceToHost, stream));
+    uint32_t is_bad[2] = {};
+    EX_HIP_TRY(hipMemcpyAsync(is_bad, bad, 8, hipMemcpyDeviceToHost, stream));
     EX_HIP_TRY(hipStreamSynchronize(stream));
-    if (is_bad) {
+    if (is_bad[0]) {
         set_error("a signature carries bits above its 20 bases");
         return ISSL_E_ARG;
     }
+    if (is_bad[1]) {
+        set_error("page_starts: " + std::to_string(pages.n_pages + 1) + " boundaries that start at 0, never decrease and end at " +
+                  std::to_string(n));
+        return ISSL_E_ARG;
+    }
+    if (n == 0) return ISSL_OK;
     for (size_t at = 0; at < n; at += kPieceSites)
         if (int rc = occur_piece(g, d_sites, at, std::min(kPieceSites, n - at), sorted_all, own_all, d_rows, stream)) return rc;
     // -- verdicts
     StageTimer clock(g->timing, stream);
     EX_HIP_TRY(hipMemsetAsync(src, 0, 4 * n, stream));
-    const Pages pg{sorted_all, n, page_length};
-    hipLaunchKernelGGL(k_occur_target, dim3(blocks), dim3(256), 0, stream, d_sites, own_all, pg, src);
+    const Pages pg{sorted_all, n, pages.d_starts ? 0 : pages.page_length};
+    if (pages.d_starts)
+        hipLaunchKernelGGL(k_occur_target_paged, dim3(blocks), dim3(256), 0, stream, d_sites, own_all, pg, pages.d_starts,
+                           static_cast<uint64_t>(pages.n_pages), src);
+    else
+        hipLaunchKernelGGL(k_occur_target, dim3(blocks), dim3(256), 0, stream, d_sites, own_all, pg, src);
     EX_HIP_TRY(hipGetLastError());
     const uint64_t *starts = static_cast<const uint64_t *>(g->starts.p);
     const uint32_t n_records = static_cast<uint32_t>(g->records.size());
@@ -375,19 +436,27 @@ int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, size_t
     return ISSL_OK;
 }
 
-int occurrences_host(issl_genome *g, const uint64_t *sites, size_t n, size_t page_length, issl_occurrence *rows)
+// pages.d_starts: HOST memory here.
+int occurrences_host(issl_genome *g, const uint64_t *sites, size_t n, PageSpec pages, issl_occurrence *rows)
 {
     EX_HIP_TRY(hipSetDevice(g->device));
-    if (n == 0) return ISSL_OK;
+    if (n == 0 && !(pages.d_starts && pages.n_pages)) return ISSL_OK;
     // a page may run over several pieces and its verdicts are looked up in all of them: all queries at once
-    DevBuf d_sites, d_rows;
-    EX_HIP_TRY(hipMalloc(&d_sites.p, 8 * n));
-    EX_HIP_TRY(hipMalloc(&d_rows.p, sizeof(issl_occurrence) * n));
-    EX_HIP_TRY(hipMemcpy(d_sites.p, sites, 8 * n, hipMemcpyHostToDevice));
-    if (int rc = occurrences_device(g, static_cast<const uint64_t *>(d_sites.p), n, page_length,
-                                    static_cast<issl_occurrence *>(d_rows.p), nullptr))
+    DevBuf d_sites, d_rows, d_starts;
+    if (n) {
+        EX_HIP_TRY(hipMalloc(&d_sites.p, 8 * n));
+        EX_HIP_TRY(hipMalloc(&d_rows.p, sizeof(issl_occurrence) * n));
+        EX_HIP_TRY(hipMemcpy(d_sites.p, sites, 8 * n, hipMemcpyHostToDevice));
+    }
+    if (pages.d_starts) {
+        EX_HIP_TRY(hipMalloc(&d_starts.p, 8 * (pages.n_pages + 1)));
+        EX_HIP_TRY(hipMemcpy(d_starts.p, pages.d_starts, 8 * (pages.n_pages + 1), hipMemcpyHostToDevice));
+        pages.d_starts = static_cast<const uint64_t *>(d_starts.p);
+    }
+    if (int rc = occurrences_device(g, static_cast<const uint64_t *>(d_sites.p), n, pages, static_cast<issl_occurrence *>(d_rows.p),
+                                    nullptr))
         return rc;
-    EX_HIP_TRY(hipMemcpy(rows, d_rows.p, sizeof(issl_occurrence) * n, hipMemcpyDeviceToHost));
+    if (n) EX_HIP_TRY(hipMemcpy(rows, d_rows.p, sizeof(issl_occurrence) * n, hipMemcpyDeviceToHost));
     return ISSL_OK;
 }
 
@@ -402,7 +471,7 @@ int issl_genome_occurrences(issl_genome *g, const uint64_t *sites, size_t n, siz
         issl::set_error("null argument");
         return ISSL_E_ARG;
     }
-    return issl::abi_call([&] { return issl::occurrences_host(g, sites, n, page_length, rows); });
+    return issl::abi_call([&] { return issl::occurrences_host(g, sites, n, issl::PageSpec{page_length, nullptr, 0}, rows); });
 }
 
 int issl_genome_occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, size_t page_length, issl_occurrence *d_rows,
@@ -412,8 +481,32 @@ int issl_genome_occurrences_device(issl_genome *g, const uint64_t *d_sites, size
         issl::set_error("null argument");
         return ISSL_E_ARG;
     }
-    return issl::abi_call(
-        [&] { return issl::occurrences_device(g, d_sites, n, page_length, d_rows, static_cast<hipStream_t>(stream)); });
+    return issl::abi_call([&] {
+        return issl::occurrences_device(g, d_sites, n, issl::PageSpec{page_length, nullptr, 0}, d_rows, static_cast<hipStream_t>(stream));
+    });
+}
+
+int issl_genome_occurrences_paged(issl_genome *g, const uint64_t *sites, size_t n, const uint64_t *page_starts, size_t n_pages,
+                                  issl_occurrence *rows)
+{
+    if (!g || (n && (!sites || !rows)) || (!page_starts && (n || n_pages))) {
+        issl::set_error("null argument");
+        return ISSL_E_ARG;
+    }
+    return issl::abi_call([&] { return issl::occurrences_host(g, sites, n, issl::PageSpec{0, page_starts, n_pages}, rows); });
+}
+
+int issl_genome_occurrences_paged_device(issl_genome *g, const uint64_t *d_sites, size_t n, const uint64_t *d_page_starts,
+                                         size_t n_pages, issl_occurrence *d_rows, void *stream)
+{
+    if (!g || (n && (!d_sites || !d_rows)) || (!d_page_starts && (n || n_pages))) {
+        issl::set_error("null argument");
+        return ISSL_E_ARG;
+    }
+    return issl::abi_call([&] {
+        return issl::occurrences_device(g, d_sites, n, issl::PageSpec{0, d_page_starts, n_pages}, d_rows,
+                                        static_cast<hipStream_t>(stream));
+    });
 }
 
 } // extern "C"

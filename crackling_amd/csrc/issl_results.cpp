@@ -49,6 +49,7 @@ struct Inputs {
     const double *d_mit, *d_cfd;
     size_t n_scored;
     const issl_results_config *cfg;
+    uint64_t first_row, n_rows; // the rows of the set the text holds
 };
 
 // The method as the scorer matches it (exactly) and as the caller reads it (stripped, lower case): issl_verdicts.
@@ -131,20 +132,21 @@ int results_build(const Inputs &in, issl_results **out)
     ResultPool pool;
     std::vector<issl_text_span> headers, ss, chr;
     if (int rc = prepare_text(in, pool, headers, ss, chr)) return rc;
-    const std::string header_row = results_header_row(in.cfg->delimiter);
+    const std::string header_row = (in.cfg->flags & ISSL_RESULTS_NO_HEADER) ? std::string() : results_header_row(in.cfg->delimiter);
 
     if (int rc = use_device(in.gs->device)) return rc;
     std::unique_ptr<issl_results> r(new issl_results());
     r->device = in.gs->device;
-    r->n_rows = in.gs->n_guides;
-    const uint32_t n = static_cast<uint32_t>(in.gs->n_guides); // (a set has at most 2^32 - 1 matches)
+    r->n_rows = in.n_rows;
+    const uint32_t n_set = static_cast<uint32_t>(in.gs->n_guides); // (a set has at most 2^32 - 1 matches)
+    const uint32_t n = static_cast<uint32_t>(in.n_rows);           // the rows of the text: [first_row, first_row + n) of the set
     hipStream_t stream = nullptr; // the null stream: behind whatever the caller's streams have enqueued for the inputs
     EX_HIP_TRY(hipMalloc(&r->offsets.p, 8ull * (n + 1ull)));
     if (n == 0) {
         r->n_bytes = header_row.size();
         const uint64_t first = header_row.size();
-        EX_HIP_TRY(hipMalloc(&r->text.p, (r->n_bytes + 15) & ~15ull));
-        EX_HIP_TRY(hipMemcpy(r->text.p, header_row.data(), header_row.size(), hipMemcpyHostToDevice));
+        EX_HIP_TRY(hipMalloc(&r->text.p, ((r->n_bytes + 15) & ~15ull) + 16));
+        if (!header_row.empty()) EX_HIP_TRY(hipMemcpy(r->text.p, header_row.data(), header_row.size(), hipMemcpyHostToDevice));
         EX_HIP_TRY(hipMemcpy(r->offsets.p, &first, 8, hipMemcpyHostToDevice));
         *out = r.release();
         return ISSL_OK;
@@ -167,17 +169,18 @@ int results_build(const Inputs &in, issl_results **out)
     ResultArgs a{};
     a.guides = static_cast<const issl_guide *>(in.gs->guides.p);
     a.rows = in.d_rows;
+    a.first = static_cast<uint32_t>(in.first_row);
     a.n = n;
     a.headers = static_cast<const issl_text_span *>(d_headers.p);
     a.n_headers = static_cast<uint32_t>(headers.size());
     if (in.ss_spans && in.n_fold) {
-        if (int rc = invert(fold_of, in.d_fold, in.n_fold, n, stream)) return rc;
+        if (int rc = invert(fold_of, in.d_fold, in.n_fold, n_set, stream)) return rc;
         a.fold_of = static_cast<const uint32_t *>(fold_of.p);
         a.ss = static_cast<const issl_text_span *>(d_ss.p);
         a.n_fold = static_cast<uint32_t>(in.n_fold);
     }
     if (in.d_bowtie && in.n_selected) {
-        if (int rc = invert(sel_of, in.d_selected, in.n_selected, n, stream)) return rc;
+        if (int rc = invert(sel_of, in.d_selected, in.n_selected, n_set, stream)) return rc;
         a.sel_of = static_cast<const uint32_t *>(sel_of.p);
         a.occ = in.d_bowtie;
         a.n_sel = static_cast<uint32_t>(in.n_selected);
@@ -185,7 +188,7 @@ int results_build(const Inputs &in, issl_results **out)
         a.n_chr = static_cast<uint32_t>(chr.size());
     }
     if (in.d_scored && in.n_scored) {
-        if (int rc = invert(score_of, in.d_scored, in.n_scored, n, stream)) return rc;
+        if (int rc = invert(score_of, in.d_scored, in.n_scored, n_set, stream)) return rc;
         a.score_of = static_cast<const uint32_t *>(score_of.p);
         a.mit = in.d_mit;
         a.cfd = in.d_cfd;
@@ -218,7 +221,8 @@ int results_build(const Inputs &in, issl_results **out)
     }
     r->n_bytes = total;
     EX_HIP_TRY(hipMalloc(&r->text.p, (total + 15) & ~15ull));
-    EX_HIP_TRY(hipMemcpyAsync(r->text.p, header_row.data(), header_row.size(), hipMemcpyHostToDevice, stream));
+    if (!header_row.empty())
+        EX_HIP_TRY(hipMemcpyAsync(r->text.p, header_row.data(), header_row.size(), hipMemcpyHostToDevice, stream));
     EX_HIP_TRY(hipEventRecord(ev.e[3], stream));
     launch_results_emit(a, offsets, static_cast<const uint64_t *>(sums.p), static_cast<char *>(r->text.p),
                         (in.cfg->flags & ISSL_RESULTS_DIRECT) != 0, stream);
@@ -262,10 +266,37 @@ int results_write(const issl_results *r, const char *path, int append)
 
 extern "C" {
 
+static int build_range(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
+                                    const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
+                                    const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
+                                    size_t n_scored, const uint64_t *range, const issl_results_config *cfg, issl_results **out);
+
 int issl_results_build(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
                        const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
                        const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
                        size_t n_scored, const issl_results_config *cfg, issl_results **out)
+{
+    return build_range(gs, c, ss_text, ss_len, ss_spans, n_folds, d_bowtie, n_bowtie, genome, d_scored, d_mit, d_cfd,
+                                    n_scored, nullptr, cfg, out);
+}
+
+int issl_results_build_rows(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
+                            const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
+                            const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
+                            size_t n_scored, uint64_t first_row, uint64_t n_rows, const issl_results_config *cfg,
+                            issl_results **out)
+{
+    const uint64_t range[2] = {first_row, n_rows};
+    return build_range(gs, c, ss_text, ss_len, ss_spans, n_folds, d_bowtie, n_bowtie, genome, d_scored, d_mit, d_cfd,
+                                    n_scored, range, cfg, out);
+}
+
+/* range: {first row, rows}, or NULL for the whole set.  The checks in the order of the header's list, every one of them
+   ahead of any device call. */
+static int build_range(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
+                                    const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
+                                    const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
+                                    size_t n_scored, const uint64_t *range, const issl_results_config *cfg, issl_results **out)
 {
     if (out) *out = nullptr;
     if (!gs || !c || !cfg || !out || !cfg->method) return issl::fail(ISSL_E_ARG, "null argument");
@@ -274,6 +305,13 @@ int issl_results_build(const issl_guide_set *gs, const issl_consensus *c, const 
     issl::Inputs in{};
     in.gs = gs;
     in.cfg = cfg;
+    in.first_row = range ? range[0] : 0;
+    in.n_rows = range ? range[1] : gs->n_guides;
+    if (in.first_row > gs->n_guides || in.n_rows > gs->n_guides - in.first_row) {
+        issl::set_error("rows " + std::to_string(in.first_row) + " and the " + std::to_string(in.n_rows) + " behind it of a set of " +
+                        std::to_string(gs->n_guides) + " guides");
+        return ISSL_E_ARG;
+    }
     if (int rc = issl_consensus_device(c, &in.d_rows, &in.d_selected, &in.n_selected)) return rc; // (ISSL_E_STATE: not finished)
     if (int rc = issl_consensus_fold_list(c, &in.d_fold, &in.n_fold)) return rc;
     if (ss_spans) {

@@ -9,6 +9,8 @@
 //            that alone is larger than the buffer (a header name has no bound) is stored by its thread straight to global
 //            memory, as every row is with ISSL_RESULTS_DIRECT.  Both ways run the same field code, so what was measured
 //            is what is written.
+// A table may hold a run of rows of the set (issl_results_build_rows: the text leaves the device a batch at a time): row j of
+// the text is row a.first + j of the set in measure and emit; the three inversions stay those of the whole set.
 // Numbers are formatted in registers (issl_repr.hpp: digits as four-bit fields of a word, no per-thread array); a row
 // costs two shortest-digit conversions per float it prints, one to measure and one to write.
 #include <hip/hip_runtime.h>
@@ -53,7 +55,7 @@ template <class Sink> __device__ __forceinline__ void put_float(Sink &s, double 
     else put_repr(s, v, issl_repr_pow10);
 }
 
-// Row j: the 26 columns of Constants.py:42-70 in their order, and the line end.
+// Row j of the set: the 26 columns of Constants.py:42-70 in their order, and the line end.
 template <class Sink> __device__ void put_row(Sink &s, const ResultArgs &a, uint32_t j)
 {
     const issl_guide g = a.guides[j];
@@ -171,9 +173,9 @@ __global__ __launch_bounds__(kResultRows) void k_results_measure(ResultArgs a, u
                                                                  uint64_t *__restrict__ sums)
 {
     __shared__ uint64_t lds[256];
-    const uint32_t j = blockIdx.x * kResultRows + threadIdx.x;
+    const uint32_t j = blockIdx.x * kResultRows + threadIdx.x; // row a.first + j of the set is row j of the text
     CountSink s;
-    if (j < a.n) put_row(s, a, j);
+    if (j < a.n) put_row(s, a, a.first + j);
     uint64_t total;
     const uint64_t at = block_exclusive_scan(s.n, lds, &total);
     if (j < a.n) offsets[j] = at;
@@ -215,7 +217,7 @@ __global__ __launch_bounds__(kResultRows) void k_results_emit(ResultArgs a, uint
     if (direct) {
         if (j < a.n) {
             WriteSink s{text + base + my_start};
-            put_row(s, a, j);
+            put_row(s, a, a.first + j);
         }
         return;
     }
@@ -233,7 +235,7 @@ __global__ __launch_bounds__(kResultRows) void k_results_emit(ResultArgs a, uint
         if (last == first) { // this row alone is larger than the buffer
             if (t == first && j < a.n) {
                 WriteSink s{text + base + my_start};
-                put_row(s, a, j);
+                put_row(s, a, a.first + j);
             }
             first += 1;
             continue;
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(kResultRows) void k_results_emit(ResultArgs a, uint
         const uint32_t shift = static_cast<uint32_t>(base + w0) & 15u; // the text pointer is 256-byte aligned
         if (t >= first && t < last && j < a.n) {
             WriteSink s{stage + shift + (my_start - w0)};
-            put_row(s, a, j);
+            put_row(s, a, a.first + j);
         }
         __syncthreads();
         const uint32_t bytes = static_cast<uint32_t>(s_off[last] - w0);

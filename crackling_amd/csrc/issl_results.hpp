@@ -18,9 +18,9 @@ enum ResultRule : uint32_t { kRuleNone, kRuleMit, kRuleCfd, kRuleAnd, kRuleOr, k
 struct ResultArgs {
     const issl_guide *guides;
     const issl_consensus_row *rows;
-    uint32_t n;
+    uint32_t first, n;              // the rows of the set the text holds: [first, first + n)
     const issl_text_span *headers;  // per record of the guide set
-    const uint32_t *fold_of;        // per guide: its place in the fold list / the selection / the scored rows, or kNoRow;
+    const uint32_t *fold_of;        // per guide of the whole set: its place in the fold list / the selection / the scored rows, or kNoRow;
     const uint32_t *sel_of;         // null: no such stage
     const uint32_t *score_of;
     const issl_text_span *ss;       // three per fold

@@ -3,8 +3,9 @@ Crackling.py:263-268 and one CSV row of the 26 columns of Constants.py:42-70 per
 GPU from the guide set, the finished consensus, the Bowtie step's rows and the off-target scores where they lie.
 
 `ResultTable(consensus, ...)` builds the text in device memory; `to_bytes()` and `write()` bring it out, `text_tensor()`
-and `row_offsets_tensor()` leave it there.  One batch is the whole guide set (the reference's file whenever [input]
-batch-size is at least the number of guides); five delimiters; no CPU fallback.
+and `row_offsets_tensor()` leave it there.  `rows=(first, count)` and `header=False` build a run of rows, so that the text
+can leave the device a batch at a time (crackling_amd.pipeline.batches); a row's text does not know its batch -- what
+[input] batch-size changes comes in with the Bowtie step's rows and RNAfold's answers.  Five delimiters; no CPU fallback.
 """
 import ctypes as C
 import os
@@ -21,7 +22,7 @@ COLUMNS = ("seq", "sgrnascorer2score", "header", "start", "end", "strand", "isUn
 DELIMITERS = (",", "\t", ";", "|", " ")
 TEXT_SPAN_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u4"), ("reserved", "<u4")])  # issl_text_span
 NO_TEXT = 0xFFFFFFFF
-DIRECT, NO_SGRNA = 1, 2  # ISSL_RESULTS_DIRECT, ISSL_RESULTS_NO_SGRNA
+DIRECT, NO_SGRNA, NO_HEADER = 1, 2, 4  # ISSL_RESULTS_DIRECT, ISSL_RESULTS_NO_SGRNA, ISSL_RESULTS_NO_HEADER
 
 
 def read_rnafold_text(text, guides):
@@ -70,17 +71,52 @@ def _pack_text(folds_text):
     return b"".join(parts), spans
 
 
+class PackedFolds:
+    """The entries of read_rnafold_text packed once for several tables: ResultTable takes it in place of the list.
+    `piece(lo, hi)` keeps the texts of rows [lo, hi) of the fold list only -- the others read as '?', which a table of
+    other rows never prints -- so that a table of a run of rows uploads its own texts and no more."""
+
+    def __init__(self, folds_text):
+        self.blob, self.spans = _pack_text(folds_text)
+        self.n = len(folds_text)
+
+    def __len__(self):
+        return self.n
+
+    def piece(self, lo, hi):
+        out = PackedFolds.__new__(PackedFolds)
+        out.n = self.n
+        out.spans = np.zeros(3 * self.n, dtype=TEXT_SPAN_DTYPE)
+        out.spans["length"] = NO_TEXT
+        part = self.spans[3 * lo:3 * hi].copy()
+        have = part["length"] != NO_TEXT
+        first = last = 0
+        if have.any():  # (the texts lie in the blob in the order of the list)
+            first = int(part["offset"][have][0])
+            last = int(part["offset"][have][-1]) + int(part["length"][have][-1])
+            part["offset"][have] -= np.uint64(first)
+        out.spans[3 * lo:3 * hi] = part
+        out.blob = self.blob[first:last]
+        return out
+
+
 class ResultTable:
     """The result file of one run, in device memory.
       consensus   a finished Consensus; its guide set gives the rows
-      folds_text  read_rnafold_text(text, consensus.fold_guides()): one entry per row of the fold list; None: '?' everywhere
+      folds_text  read_rnafold_text(text, consensus.fold_guides()): one entry per row of the fold list, or a PackedFolds of
+                  them; None: '?' everywhere
       bowtie      the BowtieStep of this consensus, or None: '?' in its four columns
       scores      (rows, mit, cfd) as CUDA tensors: the rows of the guide set that were scored, ascending (int32 or int64),
                   and their float64 scores as the scorer returns them; or None
       delimiter, method, threshold   [output] delimiter, [offtargetscore] method and score-threshold
+      rows        None: every row of the set; (first, count): these rows only -- the other arguments stay those of the whole
+                  set -- and row k of this table is row first + k of the set
+      header      False: the text starts with its first row (row_offsets_tensor()[0] == 0).  The header row, then
+                  header=False tables of consecutive runs of rows that cover the set, are the whole table's bytes
     `flags` is for tests and measurements (DIRECT, NO_SGRNA)."""
 
-    def __init__(self, consensus, folds_text=None, bowtie=None, scores=None, delimiter=",", method="and", threshold=75.0, flags=0):
+    def __init__(self, consensus, folds_text=None, bowtie=None, scores=None, delimiter=",", method="and", threshold=75.0, flags=0,
+                 rows=None, header=True):
         import torch
         self._h = None
         if not consensus.finished:
@@ -93,7 +129,10 @@ class ResultTable:
         self.device = gs.device
         cfg = _lib.ResultsConfig()
         cfg.delimiter = delimiter.encode()
-        cfg.flags = int(flags)
+        cfg.flags = int(flags) | (0 if header else NO_HEADER)
+        first_row, n_rows = (0, gs.n_guides) if rows is None else (int(rows[0]), int(rows[1]))
+        if first_row < 0 or n_rows < 0:
+            raise ValueError("rows: (first, count), neither below 0")
         method_b = str(method).encode()
         cfg.method = method_b
         cfg.threshold = float(threshold)
@@ -101,38 +140,43 @@ class ResultTable:
         if folds_text is not None:
             if len(folds_text) != consensus.n_fold:
                 raise ValueError(f"{len(folds_text)} fold texts for a fold list of {consensus.n_fold}")
-            blob, spans = _pack_text(folds_text)
+            packed = folds_text if isinstance(folds_text, PackedFolds) else PackedFolds(folds_text)
+            blob, spans = packed.blob, packed.spans
             n_folds = len(folds_text)
         d_bowtie, n_bowtie, genome = None, 0, None
         if bowtie is not None:
-            rows = bowtie.rows_tensor()
-            d_bowtie, n_bowtie, genome = rows.data_ptr() if rows.numel() else None, rows.shape[0], bowtie.genome._h
+            b_rows = bowtie.rows_tensor()
+            d_bowtie, n_bowtie, genome = b_rows.data_ptr() if b_rows.numel() else None, b_rows.shape[0], bowtie.genome._h
             if d_bowtie is None:
                 genome = None
         d_scored = d_mit = d_cfd = None
         n_scored = 0
         keep = []
         if scores is not None:
-            rows, mit, cfd = scores
-            rows = rows.to(device=f"cuda:{self.device}", dtype=torch.int32).contiguous()
+            s_rows, mit, cfd = scores
+            s_rows = s_rows.to(device=f"cuda:{self.device}", dtype=torch.int32).contiguous()
             mit = mit.to(device=f"cuda:{self.device}", dtype=torch.float64).contiguous()
             cfd = cfd.to(device=f"cuda:{self.device}", dtype=torch.float64).contiguous()
-            if not (rows.numel() == mit.numel() == cfd.numel()):
+            if not (s_rows.numel() == mit.numel() == cfd.numel()):
                 raise ValueError("scores: rows, mit and cfd of one length")
-            keep = [rows, mit, cfd]
-            n_scored = rows.numel()
+            keep = [s_rows, mit, cfd]
+            n_scored = s_rows.numel()
             if n_scored:
-                d_scored, d_mit, d_cfd = rows.data_ptr(), mit.data_ptr(), cfd.data_ptr()
+                d_scored, d_mit, d_cfd = s_rows.data_ptr(), mit.data_ptr(), cfd.data_ptr()
         torch.cuda.current_stream(self.device).synchronize()  # the inputs are complete before the library reads them
         h = C.c_void_p()
-        check(lib.issl_results_build(gs._h, consensus._h, blob, len(blob) if blob is not None else 0,
-                                     spans.ctypes.data if spans is not None else None, n_folds, d_bowtie, n_bowtie, genome,
-                                     d_scored, d_mit, d_cfd, n_scored, C.byref(cfg), C.byref(h)))
+        args = (gs._h, consensus._h, blob, len(blob) if blob is not None else 0, spans.ctypes.data if spans is not None else None,
+                n_folds, d_bowtie, n_bowtie, genome, d_scored, d_mit, d_cfd, n_scored)
+        if rows is None and header:
+            check(lib.issl_results_build(*args, C.byref(cfg), C.byref(h)))
+        else:
+            check(lib.issl_results_build_rows(*args, first_row, n_rows, C.byref(cfg), C.byref(h)))
         del keep
         self._h = h
-        n_rows, n_bytes, per_group = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        n_rows, n_bytes, per_group = C.c_uint64(), C.c_uint64(), C.c_uint32()  # (of the table: the rows asked for)
         check(lib.issl_results_info(self._h, C.byref(n_rows), C.byref(n_bytes), C.byref(per_group)))
         self.n_rows, self.n_bytes, self.rows_per_group = n_rows.value, n_bytes.value, per_group.value
+        self.first_row = first_row
 
     def _device(self):
         d_text, d_off = C.c_void_p(), C.c_void_p()
@@ -147,7 +191,7 @@ class ResultTable:
 
     def row_offsets_tensor(self):
         """int64 CUDA tensor of n_rows + 1 offsets: row k is text[offsets[k]:offsets[k + 1]], offsets[0] is the length of
-        the header row."""
+        the header row (0 without one)."""
         import torch
         from .scorer import _DeviceArray
         return torch.as_tensor(_DeviceArray(self, self._device()[1], (self.n_rows + 1,), "<i8"), device=f"cuda:{self.device}")

@@ -481,30 +481,47 @@ class Genome:
                                             C.c_void_p(stream) if stream else None))
         return n.value
 
-    def occurrences(self, sites, page_length=0):
+    def occurrences(self, sites, page_length=0, page_starts=None):
         """The Bowtie step (Crackling.py:600-725) as exact counts.  sites: 20-mer strings or a uint64 array of packed
         signatures, duplicates allowed; page_length: the reference's [bowtie2] page-length (0: one page).  -> structured
         array (OCCURRENCE_DTYPE), one row per site: which of the eight reads site + AGG, CGG, GGG, TGG, AAG, CAG, GAG, TAG
         occur in the genome without a mismatch (`aligned`) and which at least twice (`repeated`), `nb` as the reference
         counts, and the verdict the reference files under this site: `code`, the first occurrence of read 0 (record
-        0xFFFFFFFF when there is none) and `source`, the site whose group of SAM lines set it (include/issl_hip.h)."""
+        0xFFFFFFFF when there is none) and `source`, the site whose group of SAM lines set it (include/issl_hip.h).
+        page_starts: pages of any length in place of page_length, as the pages of a run in batches are -- n_pages + 1
+        boundaries from 0 to len(sites), never decreasing; page p is sites[page_starts[p]:page_starts[p + 1]]."""
         if isinstance(sites, np.ndarray):
             sigs = np.ascontiguousarray(sites, dtype=np.uint64)
         else:
             sigs = encode_guides(sites)
         rows = np.zeros(len(sigs), dtype=OCCURRENCE_DTYPE)
+        if page_starts is not None:
+            starts = np.ascontiguousarray(page_starts, dtype=np.uint64)
+            if starts.ndim != 1 or len(starts) == 0:
+                raise ValueError("page_starts: n_pages + 1 boundaries")
+            check(lib.issl_genome_occurrences_paged(self._h, sigs.ctypes.data if len(sigs) else None, len(sigs), starts.ctypes.data,
+                                                    len(starts) - 1, rows.ctypes.data if len(sigs) else None))
+            return rows
         check(lib.issl_genome_occurrences(self._h, sigs.ctypes.data if len(sigs) else None, len(sigs), int(page_length),
                                           rows.ctypes.data if len(sigs) else None))
         return rows
 
-    def occurrences_device(self, d_sites, d_rows, page_length=0, stream=None):
+    def occurrences_device(self, d_sites, d_rows, page_length=0, stream=None, page_starts=None):
         """d_sites: int64 CUDA tensor of packed signatures (left as it is); d_rows: uint8 CUDA tensor of 32 bytes per site
-        (OCCURRENCE_DTYPE).  Returns when the rows are written."""
+        (OCCURRENCE_DTYPE); page_starts: None, or a 64-bit integer CUDA tensor of n_pages + 1 boundaries in place of
+        page_length.  Returns when the rows are written."""
         n = d_sites.numel()
         if d_rows.numel() * d_rows.element_size() < OCCURRENCE_DTYPE.itemsize * n:
             raise ValueError("d_rows holds fewer than 32 bytes per site")
+        stream = C.c_void_p(stream) if stream else None
+        if page_starts is not None:
+            if page_starts.dim() != 1 or page_starts.numel() == 0 or page_starts.element_size() != 8 or not page_starts.is_contiguous():
+                raise ValueError("page_starts: a contiguous tensor of n_pages + 1 64-bit boundaries")
+            check(lib.issl_genome_occurrences_paged_device(self._h, d_sites.data_ptr() if n else None, n, page_starts.data_ptr(),
+                                                           page_starts.numel() - 1, d_rows.data_ptr() if n else None, stream))
+            return
         check(lib.issl_genome_occurrences_device(self._h, d_sites.data_ptr() if n else None, n, int(page_length),
-                                                 d_rows.data_ptr() if n else None, C.c_void_p(stream) if stream else None))
+                                                 d_rows.data_ptr() if n else None, stream))
 
     def close(self):
         if self._h:

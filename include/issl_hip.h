@@ -566,6 +566,17 @@ int issl_genome_occurrences(issl_genome *g, const uint64_t *sites, size_t n, siz
  * the host and not changed, and the call returns when the rows are written. */
 int issl_genome_occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, size_t page_length, issl_occurrence *d_rows,
                                    void *stream);
+/* The same two calls for pages that are not all of one length: the pages of a run in batches ([input] batch-size) start
+ * again with every batch (issl_consensus_selection_pages makes them).  page_starts has n_pages + 1 entries, page p is sites
+ * [page_starts[p], page_starts[p + 1]): page_starts[0] == 0, page_starts[n_pages] == n, no entry below the one before it;
+ * equal neighbours are an empty page.  The boundaries are checked on the device before any row is written: ISSL_E_ARG
+ * otherwise, as for a NULL page_starts unless n and n_pages are both 0, which is ISSL_OK.  The boundaries of a uniform
+ * page_length give the bytes of the calls above; pieces and pages still change no row but through `source` and what
+ * comes from it.  page_starts is host memory in the first call and device memory in the second. */
+int issl_genome_occurrences_paged(issl_genome *g, const uint64_t *sites, size_t n, const uint64_t *page_starts, size_t n_pages,
+                                  issl_occurrence *rows);
+int issl_genome_occurrences_paged_device(issl_genome *g, const uint64_t *d_sites, size_t n, const uint64_t *d_page_starts,
+                                         size_t n_pages, issl_occurrence *d_rows, void *stream);
 
 /* ---- candidate guides from FASTA: Crackling's extraction step ------------------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:151-305: the candidate 23-mers of the inputs, on `device`; no CPU fallback.
@@ -683,6 +694,15 @@ int issl_consensus_copy(const issl_consensus *c, issl_consensus_row *out, size_t
 /* Rows and selection in the memory of the set's device (NULL where empty), valid until the consensus is closed. */
 int issl_consensus_device(const issl_consensus *c, const issl_consensus_row **d_rows, const uint32_t **d_selected,
                           uint64_t *n_selected);
+/* The reference's pages of the Bowtie step for a run in batches, made on the device from the selection where it lies: a
+ * batch is batch_size consecutive rows of the set ([input] batch-size; Batchinator.py records every distinct guide once, in
+ * first-seen order; 0: one batch), and every batch cuts its selected rows into pages of page_length ([bowtie2] page-length;
+ * 0: one page per batch that has a selected row).  *d_page_starts: *n_pages + 1 boundaries in positions of the selection,
+ * for issl_genome_occurrences_paged_device: device memory owned by the consensus, valid until the next such call or close.
+ * No page is empty; an empty selection gives 0 pages and the one boundary 0.  ISSL_E_STATE before finish.  The host waits
+ * once, for *n_pages. */
+int issl_consensus_selection_pages(issl_consensus *c, uint64_t batch_size, uint64_t page_length, const uint64_t **d_page_starts,
+                                   uint64_t *n_pages);
 int issl_consensus_close(issl_consensus *c);
 
 /* ---- transcript hit counts: how many transcripts of its gene a located guide cuts ------------------------------------ */
@@ -755,8 +775,14 @@ int issl_annotation_close(issl_annotation *a);
 /* Counterpart of src/crackling/Crackling.py:263-268 (the header row) and :842-852 (one CSV row of the 26 columns of
  * Constants.py:42-70 per candidate guide, csv.writer with dialect 'unix', QUOTE_MINIMAL, quote character '"'): the text is
  * written on the set's device -- every row measured, the lengths summed, every workgroup's rows assembled in LDS and stored as
- * one span -- and stays there; no CPU fallback.  One batch is the whole guide set: the reference's file whenever [input]
- * batch-size is at least the number of guides (smaller batches cut its pages elsewhere and are not modelled).
+ * one span -- and stays there; no CPU fallback.  The reference works through the guides in batches of [input] batch-size and
+ * appends every batch's rows to the file.  A row's text does not know its batch: what a batch changes are the pages of the
+ * Bowtie step and of RNAfold, which start again with every batch, and both come in through the arguments -- d_bowtie from
+ * issl_genome_occurrences_paged_device over issl_consensus_selection_pages, the folds and ss spans read page by page
+ * (crackling_amd.pipeline).  With [rnafold] page-length = 0 the reference tests no guide (Paginator.py:29-30 hands out the
+ * filter's generator, Crackling.py:420 consumes it, :458 sees nothing): folds with present == 0 and spans without text say
+ * that.  issl_results_build_rows writes a run of rows, so that the text can leave the device a batch at a time.  Not
+ * modelled: the RNAfold and Bowtie2 programs themselves, delimiters beyond the five, a CPU fallback.
  *   rows       those of the guide set, in its order, behind the header row; lines end in "\n"
  *   seq .. isUnique   the 23-mer; for seen == 1 the record's header line (issl_guides_record), start, start + 23, '+' / '-'
  *              and 1, otherwise '-' four times and 0 (:292-303)
@@ -793,7 +819,8 @@ typedef struct {
 enum {
     ISSL_RESULTS_DIRECT = 1,  /* every row is stored straight to global memory by its thread (the path rows larger than the
                                  staging buffer take); same bytes.  Tests and A/B */
-    ISSL_RESULTS_NO_SGRNA = 2 /* sgrnascorer2score is '?' in every row: the A/B that prices its repr (tools/bench_results.py) */
+    ISSL_RESULTS_NO_SGRNA = 2, /* sgrnascorer2score is '?' in every row: the A/B that prices its repr (tools/bench_results.py) */
+    ISSL_RESULTS_NO_HEADER = 4 /* the text starts with its first row: no header row, d_offsets[0] == 0 */
 };
 typedef struct {
     char delimiter;     /* [output] delimiter */
@@ -806,6 +833,17 @@ int issl_results_build(const issl_guide_set *gs, const issl_consensus *c, const 
                        const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
                        const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
                        size_t n_scored, const issl_results_config *cfg, issl_results **out);
+/* The same for rows [first_row, first_row + n_rows) of the set: the header row (unless ISSL_RESULTS_NO_HEADER) and these
+ * rows.  Every other argument keeps its meaning for the WHOLE set: d_bowtie is aligned with the whole selection, d_scored
+ * lists rows of the whole set, the spans belong to the whole fold list.  The header row, or a build with n_rows == 0, followed
+ * by ISSL_RESULTS_NO_HEADER builds of consecutive ranges that cover the set is byte for byte the text of issl_results_build;
+ * row k of the text is row first_row + k of the set (issl_results_info, issl_results_device).  A range that does not lie in
+ * the set: ISSL_E_ARG.  An empty range gives the header row, or no byte with the flag. */
+int issl_results_build_rows(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
+                            const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
+                            const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
+                            size_t n_scored, uint64_t first_row, uint64_t n_rows, const issl_results_config *cfg,
+                            issl_results **out);
 /* n_rows: the guides (the header row is not counted); n_bytes: the whole text; rows_per_group: the rows one workgroup
  * assembles (a property of the build, for tests that place sizes around it).  Any output may be NULL. */
 int issl_results_info(const issl_results *r, uint64_t *n_rows, uint64_t *n_bytes, uint32_t *rows_per_group);
