@@ -215,6 +215,22 @@ _protos = {
     "issl_results_write": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "issl_results_close": (C.c_int, [_P]),
     "issl_repr_f64_device": (C.c_int, [_P, C.c_size_t, _P, _P, _P]),
+    "issl_folds_open": (C.c_int, [_P, C.POINTER(_P)]),
+    "issl_folds_info": (C.c_int, [_P, _u64p, _u64p, _u64p, C.POINTER(C.c_uint32)]),
+    "issl_folds_times": (C.c_int, [_P, _f64p, _f64p]),
+    "issl_folds_input": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(_P), _u64p]),
+    "issl_folds_input_copy": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_size_t]),
+    "issl_folds_input_write": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_char_p]),
+    "issl_folds_read": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t]),
+    "issl_folds_read_file": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_char_p]),
+    "issl_folds_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "issl_folds_text_device": (C.c_int, [_P, C.POINTER(_P), _u64p]),
+    "issl_folds_copy": (C.c_int, [_P, _P, _P, C.c_size_t]),
+    "issl_folds_text_copy": (C.c_int, [_P, C.c_uint64, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_folds_close": (C.c_int, [_P]),
+    "issl_consensus_finish_folds": (C.c_int, [_P, _P]),
+    "issl_results_build_rows_folds": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_uint64,
+                                                C.POINTER(ResultsConfig), C.POINTER(_P)]),
     "issl_node_create": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "issl_node_score": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P]),
     "issl_node_get_info": (C.c_int, [_P, C.POINTER(NodeInfo)]),

@@ -122,10 +122,18 @@ class Consensus:
         """The lines the reference hands RNAfold (Crackling.py:421), one per row of the fold list."""
         return "".join(f"G{g[1:20]}{SCAFFOLD}\n" for g in self.fold_guides())
 
+    def folds(self):
+        """A crackling_amd.Folds for this consensus: RNAfold's input written and its answers read on the device."""
+        from .folds import Folds
+        return Folds(self)
+
     def finish(self, folds=None):
-        """folds: FOLD_DTYPE array aligned with fold_rows (read_rnafold_output(text, self.fold_guides())); None when the fold
-        list is empty.  Once."""
-        if folds is None:
+        """folds: FOLD_DTYPE array aligned with fold_rows (read_rnafold_output(text, self.fold_guides())), or the Folds of
+        this consensus, whose rows are taken where they lie on the device; None when the fold list is empty.  Once."""
+        from .folds import Folds
+        if isinstance(folds, Folds):
+            check(lib.issl_consensus_finish_folds(self._h, folds._h))
+        elif folds is None:
             check(lib.issl_consensus_finish(self._h, None, 0))
         else:
             folds = np.ascontiguousarray(folds, dtype=FOLD_DTYPE)

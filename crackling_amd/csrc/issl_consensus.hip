@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/issl_hip.h"
+#include "issl_folds.hpp"
 #include "issl_guides.hpp"
 #include "issl_host.hpp"
 #include "issl_match.hpp"
@@ -395,7 +396,8 @@ int consensus_begin(const issl_guide_set *gs, const issl_consensus_config *cfg, 
     return ISSL_OK;
 }
 
-int consensus_finish(issl_consensus *c, const issl_fold *folds)
+// folds: host memory, or with on_device the rows where issl_folds_read left them.
+int consensus_finish(issl_consensus *c, const issl_fold *folds, bool on_device = false)
 {
     if (c->n) {
         EX_HIP_TRY(hipSetDevice(c->device));
@@ -404,10 +406,12 @@ int consensus_finish(issl_consensus *c, const issl_fold *folds)
         DevBuf d_folds;
         if (c->n_fold) {
             const uint32_t n_fold = static_cast<uint32_t>(c->n_fold);
-            EX_HIP_TRY(hipMalloc(&d_folds.p, 16ull * n_fold));
-            EX_HIP_TRY(hipMemcpyAsync(d_folds.p, folds, 16ull * n_fold, hipMemcpyHostToDevice, stream));
+            if (!on_device) {
+                EX_HIP_TRY(hipMalloc(&d_folds.p, 16ull * n_fold));
+                EX_HIP_TRY(hipMemcpyAsync(d_folds.p, folds, 16ull * n_fold, hipMemcpyHostToDevice, stream));
+            }
             hipLaunchKernelGGL(k_consensus_fold, dim3(blocks_of(n_fold)), dim3(kThreads), 0, stream, c->guides, c->n, c->cfg,
-                               static_cast<const uint32_t *>(c->fold_list.p), static_cast<const issl_fold *>(d_folds.p), n_fold,
+                               static_cast<const uint32_t *>(c->fold_list.p), on_device ? folds : static_cast<const issl_fold *>(d_folds.p), n_fold,
                                static_cast<issl_consensus_row *>(c->rows.p));
             EX_HIP_TRY(hipGetLastError());
         }
@@ -475,6 +479,12 @@ int copy_from_device(const issl_consensus *c, void *out, const void *src, size_t
 }
 
 } // namespace
+
+FoldSource consensus_fold_source(const issl_consensus *c)
+{
+    return FoldSource{c->device, c->guides, c->n, static_cast<const uint32_t *>(c->fold_list.p), c->n_fold};
+}
+
 } // namespace issl
 
 extern "C" {
@@ -518,6 +528,14 @@ int issl_consensus_finish(issl_consensus *c, const issl_fold *folds, size_t n_fo
     }
     if (!folds && n_folds) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] { return issl::consensus_finish(c, folds); });
+}
+
+int issl_consensus_finish_folds(issl_consensus *c, const issl_folds *f)
+{
+    if (!c || !f) return issl::fail(ISSL_E_ARG, "null argument");
+    if (f->consensus != c) return issl::fail(ISSL_E_ARG, "the folds belong to another consensus");
+    if (c->finished) return issl::fail(ISSL_E_STATE, "the consensus is finished already");
+    return issl::abi_call([&] { return issl::consensus_finish(c, static_cast<const issl_fold *>(f->folds.p), true); });
 }
 
 int issl_consensus_copy(const issl_consensus *c, issl_consensus_row *out, size_t cap)

@@ -12,6 +12,8 @@
 #include <vector>
 
 #include "../../include/issl_hip.h"
+#include "issl_folds.hpp"
+#include "issl_folds_text.hpp"
 #include "issl_genome_handle.hpp"
 #include "issl_guides.hpp"
 #include "issl_host.hpp"
@@ -43,6 +45,7 @@ struct Inputs {
     const char *ss_text;
     size_t ss_len;
     const issl_text_span *ss_spans;
+    const issl_folds *folds;      // in place of the three above: the spans and their text where issl_folds_read left them
     const issl_occurrence *d_bowtie;
     const issl_genome *genome;
     const uint32_t *d_scored;
@@ -173,10 +176,12 @@ int results_build(const Inputs &in, issl_results **out)
     a.n = n;
     a.headers = static_cast<const issl_text_span *>(d_headers.p);
     a.n_headers = static_cast<uint32_t>(headers.size());
-    if (in.ss_spans && in.n_fold) {
+    if ((in.ss_spans || in.folds) && in.n_fold) {
         if (int rc = invert(fold_of, in.d_fold, in.n_fold, n_set, stream)) return rc;
         a.fold_of = static_cast<const uint32_t *>(fold_of.p);
-        a.ss = static_cast<const issl_text_span *>(d_ss.p);
+        a.ss = in.folds ? static_cast<const issl_text_span *>(in.folds->spans.p) : static_cast<const issl_text_span *>(d_ss.p);
+        a.fold_text = in.folds ? static_cast<const char *>(in.folds->text.p) : nullptr; // (null before any read: every span is '?')
+        a.fold_quote = folds_text::quote_bit(static_cast<uint8_t>(in.cfg->delimiter)) | folds_text::quote_bit('"');
         a.n_fold = static_cast<uint32_t>(in.n_fold);
     }
     if (in.d_bowtie && in.n_selected) {
@@ -269,7 +274,8 @@ extern "C" {
 static int build_range(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
                                     const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
                                     const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
-                                    size_t n_scored, const uint64_t *range, const issl_results_config *cfg, issl_results **out);
+                                    size_t n_scored, const uint64_t *range, const issl_results_config *cfg, issl_results **out,
+                                    const issl_folds *folds = nullptr);
 
 int issl_results_build(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
                        const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
@@ -291,12 +297,24 @@ int issl_results_build_rows(const issl_guide_set *gs, const issl_consensus *c, c
                                     n_scored, range, cfg, out);
 }
 
+int issl_results_build_rows_folds(const issl_guide_set *gs, const issl_consensus *c, const issl_folds *f,
+                                  const issl_occurrence *d_bowtie, size_t n_bowtie, const issl_genome *genome,
+                                  const uint32_t *d_scored, const double *d_mit, const double *d_cfd, size_t n_scored,
+                                  uint64_t first_row, uint64_t n_rows, const issl_results_config *cfg, issl_results **out)
+{
+    if (out) *out = nullptr;
+    if (!f) return issl::fail(ISSL_E_ARG, "null argument");
+    const uint64_t range[2] = {first_row, n_rows};
+    return build_range(gs, c, nullptr, 0, nullptr, 0, d_bowtie, n_bowtie, genome, d_scored, d_mit, d_cfd, n_scored, range, cfg, out, f);
+}
+
 /* range: {first row, rows}, or NULL for the whole set.  The checks in the order of the header's list, every one of them
    ahead of any device call. */
 static int build_range(const issl_guide_set *gs, const issl_consensus *c, const char *ss_text, size_t ss_len,
                                     const issl_text_span *ss_spans, size_t n_folds, const issl_occurrence *d_bowtie, size_t n_bowtie,
                                     const issl_genome *genome, const uint32_t *d_scored, const double *d_mit, const double *d_cfd,
-                                    size_t n_scored, const uint64_t *range, const issl_results_config *cfg, issl_results **out)
+                                    size_t n_scored, const uint64_t *range, const issl_results_config *cfg, issl_results **out,
+                                    const issl_folds *folds)
 {
     if (out) *out = nullptr;
     if (!gs || !c || !cfg || !out || !cfg->method) return issl::fail(ISSL_E_ARG, "null argument");
@@ -314,6 +332,10 @@ static int build_range(const issl_guide_set *gs, const issl_consensus *c, const 
     }
     if (int rc = issl_consensus_device(c, &in.d_rows, &in.d_selected, &in.n_selected)) return rc; // (ISSL_E_STATE: not finished)
     if (int rc = issl_consensus_fold_list(c, &in.d_fold, &in.n_fold)) return rc;
+    if (folds) {
+        if (folds->consensus != c) return issl::fail(ISSL_E_ARG, "the folds belong to another consensus");
+        in.folds = folds;
+    }
     if (ss_spans) {
         if (!ss_text && ss_len) return issl::fail(ISSL_E_ARG, "null argument");
         if (n_folds != in.n_fold) {

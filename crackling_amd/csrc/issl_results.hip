@@ -44,6 +44,29 @@ template <class Sink> __device__ __forceinline__ void put_span(Sink &s, const Re
     else put_text(s, a.pool + t.offset, t.length);
 }
 
+// A span of an issl_folds' text, or '?': RNAfold's bytes as they stand, quoted here as csv_append (issl_results_text.hpp)
+// quotes on the host -- with the delimiter, '"', LF or CR inside, an embedded '"' doubled.  Whether it has one of them the
+// read has noted in the span (issl_folds_text.hpp, quote_bits): a field without -- every one of RNAfold's under ',' -- is
+// measured without a look at its text and copied in one pass.
+template <class Sink> __device__ __forceinline__ void put_fold_span(Sink &s, const ResultArgs &a, const issl_text_span &t)
+{
+    if (t.length == 0xFFFFFFFFu) {
+        s.put('?');
+        return;
+    }
+    const char *src = a.fold_text + t.offset;
+    if (!(t.reserved & a.fold_quote)) {
+        put_text(s, src, t.length);
+        return;
+    }
+    s.put('"');
+    for (uint32_t i = 0; i < t.length; ++i) {
+        if (src[i] == '"') s.put('"');
+        s.put(src[i]);
+    }
+    s.put('"');
+}
+
 template <class Sink> __device__ __forceinline__ void put_code(Sink &s, uint32_t code)
 {
     s.put(static_cast<char>(0x213F3130u >> (8 * (code & 3u)))); // 0 1 ? !
@@ -94,6 +117,7 @@ template <class Sink> __device__ void put_row(Sink &s, const ResultArgs &a, uint
     if (f >= a.n_fold) f = kNoRow;
     for (uint32_t k = 0; k < 3; ++k) {
         if (f == kNoRow) s.put('?');
+        else if (a.fold_text) put_fold_span(s, a, a.ss[3ull * f + k]);
         else put_span(s, a, a.ss[3ull * f + k]);
         s.put(d);
     }

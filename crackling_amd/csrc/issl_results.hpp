@@ -28,9 +28,12 @@ struct ResultArgs {
     const issl_text_span *chr;      // per record of the genome
     const double *mit, *cfd;        // per scored row
     const char *pool;
+    const char *fold_text;          // null: the spans of `ss` lie in pool.  Otherwise they lie here, in the text of an issl_folds
+                                    // as RNAfold printed it, and a row quotes what it copies (issl_results_build_rows_folds)
     double threshold;
     uint32_t n_headers, n_fold, n_sel, n_chr, n_scored; // the tables' lengths: an index beyond its table reads as '?'
     uint32_t rule, print_mit, print_cfd, no_sgrna;
+    uint32_t fold_quote;            // with fold_text: the bits of a span's `reserved` (issl_folds_text.hpp) that ask for quotes under `delimiter`
     char delimiter;
 };
 

@@ -8,6 +8,8 @@ whole-set (the Bowtie step scans the genome once per 2^22 sites, not once per ba
 is data: the pages of the Bowtie step and of RNAfold start again with every batch.  The text leaves the device one
 piece at a time (`batches`, `run_to_file`); `run` joins the pieces.
 """
+import contextlib
+
 import numpy as np
 
 from .consensus import FOLD_DTYPE, SCAFFOLD, Consensus, read_rnafold_output
@@ -48,10 +50,28 @@ def _fold(c, config, rnafold):
     return np.concatenate(folds), texts
 
 
+def _fold_device(c, config, rnafold):
+    """The same on the device -> the Folds of c, read: RNAfold's input comes from Folds.input(), its answer goes to
+    Folds.read(), one page at a time; the page logic is that of _fold."""
+    folds = c.folds()
+    try:
+        page_length = config.get("rnafold_page_length")
+        if page_length is None:
+            folds.read(rnafold(folds.input().decode()))
+        elif int(page_length) != 0:
+            for a, b in _fold_pages(c.fold_rows, c.n_guides, int(config.get("batch_size", 0)), int(page_length)):
+                folds.read(rnafold(folds.input(a, b - a).decode()), a, b - a)
+    except BaseException:
+        folds.close()
+        raise
+    return folds
+
+
 def batches(inputs, genome, index, config, rnafold):
     """inputs: the FASTA inputs of GuideSet.extract (bytes blobs or paths); genome: a Genome (the Bowtie step's text) and
     index: an uploaded IsslIndex, both on the device the guides go to, or None when config["offtargetscore"] is false;
-    rnafold: a callable that takes RNAfold's input (the lines of Consensus.fold_input()) and returns what RNAfold printed.
+    rnafold: a callable that takes RNAfold's input (the lines of Consensus.fold_input(), a str) and returns what RNAfold
+    printed, as str or bytes.
     config: a mapping with the keywords of Consensus (CONSENSUS_KEYS) and, all optional,
       offtargetscore  run the Bowtie step and the scoring ([offtargetscore] enabled; default True)
       batch_size      [input] batch-size: the pages of the Bowtie step and of RNAfold start again with every batch of this
@@ -65,6 +85,14 @@ def batches(inputs, genome, index, config, rnafold):
                       nothing.  `rnafold` is not called then -- its answer would never be read -- and every row of the
                       fold list keeps '?' in passedSecondaryStructure and the three ss columns
       max_distance, score_threshold, method   [offtargetscore] max-distance (4), score-threshold (75), method ("and")
+      rnafold_reader  "device" (the default): RNAfold's input is written and its answers are read on the GPU
+                      (crackling_amd.Folds); folds and texts stay there for the consensus and the table.  "host": the Python
+                      helpers fold_input, read_rnafold_output and read_rnafold_text.  The two differ in two places.  An answer
+                      that holds VT, FF, 0x1c-0x1e or non-ASCII bytes: there the helpers (str.splitlines()) split lines the
+                      reference, and the device with it, does not.  And the number in the parentheses: the helpers take
+                      what float(x.strip()) takes -- 1e2, inf, 1_0, any count of digits, VT, FF or 0x1c-0x1f around it --
+                      where the device takes plain decimals of up to 15 digits with blanks and TABs around them and refuses
+                      the rest (IsslError -3 or -4).  RNAfold prints none of these
       delimiter       [output] delimiter (",")
       device          the GPU (0)
     -> a generator of the bytes of the reference's output file for these inputs, in pieces: the header row, then one piece
@@ -75,9 +103,17 @@ def batches(inputs, genome, index, config, rnafold):
     method = str(config.get("method", "and"))
     threshold = float(config.get("score_threshold", 75.0))
     batch_size = int(config.get("batch_size", 0))
-    with GuideSet.extract(inputs, device) as gs, Consensus(gs, **{k: config[k] for k in CONSENSUS_KEYS if k in config}) as c:
-        folds_text = None
-        if c.n_fold:
+    reader = str(config.get("rnafold_reader", "device"))
+    if reader not in ("device", "host"):
+        raise ValueError('rnafold_reader: "device" or "host"')
+    with GuideSet.extract(inputs, device) as gs, Consensus(gs, **{k: config[k] for k in CONSENSUS_KEYS if k in config}) as c, \
+            contextlib.ExitStack() as stack:
+        folds_text = device_folds = None
+        if c.n_fold and reader == "device":
+            device_folds = _fold_device(c, config, rnafold)
+            stack.callback(device_folds.close)  # (ahead of the consensus it belongs to)
+            c.finish(device_folds)
+        elif c.n_fold:
             folds, folds_text = _fold(c, config, rnafold)
             c.finish(folds)
             folds_text = PackedFolds(folds_text)
@@ -100,7 +136,7 @@ def batches(inputs, genome, index, config, rnafold):
             piece = table.to_bytes()
         yield piece
         for a, b in _row_pieces(gs.n_guides, batch_size):
-            texts = None
+            texts = device_folds
             if folds_text is not None:
                 lo, hi = np.searchsorted(c.fold_rows, (a, b))
                 texts = folds_text.piece(int(lo), int(hi))

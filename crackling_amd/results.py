@@ -104,7 +104,8 @@ class ResultTable:
     """The result file of one run, in device memory.
       consensus   a finished Consensus; its guide set gives the rows
       folds_text  read_rnafold_text(text, consensus.fold_guides()): one entry per row of the fold list, or a PackedFolds of
-                  them; None: '?' everywhere
+                  them, or the Folds of this consensus, whose texts stay on the device and are quoted there; None: '?'
+                  everywhere
       bowtie      the BowtieStep of this consensus, or None: '?' in its four columns
       scores      (rows, mit, cfd) as CUDA tensors: the rows of the guide set that were scored, ascending (int32 or int64),
                   and their float64 scores as the scorer returns them; or None
@@ -137,7 +138,12 @@ class ResultTable:
         cfg.method = method_b
         cfg.threshold = float(threshold)
         blob, spans, n_folds = None, None, 0
-        if folds_text is not None:
+        from .folds import Folds
+        device_folds = folds_text if isinstance(folds_text, Folds) else None
+        if device_folds is not None:
+            if device_folds.consensus is not consensus:
+                raise ValueError("the folds belong to another consensus")
+        elif folds_text is not None:
             if len(folds_text) != consensus.n_fold:
                 raise ValueError(f"{len(folds_text)} fold texts for a fold list of {consensus.n_fold}")
             packed = folds_text if isinstance(folds_text, PackedFolds) else PackedFolds(folds_text)
@@ -167,7 +173,10 @@ class ResultTable:
         h = C.c_void_p()
         args = (gs._h, consensus._h, blob, len(blob) if blob is not None else 0, spans.ctypes.data if spans is not None else None,
                 n_folds, d_bowtie, n_bowtie, genome, d_scored, d_mit, d_cfd, n_scored)
-        if rows is None and header:
+        if device_folds is not None:
+            check(lib.issl_results_build_rows_folds(gs._h, consensus._h, device_folds._h, *args[6:], first_row, n_rows, C.byref(cfg),
+                                                    C.byref(h)))
+        elif rows is None and header:
             check(lib.issl_results_build(*args, C.byref(cfg), C.byref(h)))
         else:
             check(lib.issl_results_build_rows(*args, first_row, n_rows, C.byref(cfg), C.byref(h)))

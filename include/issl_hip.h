@@ -862,6 +862,81 @@ int issl_results_close(issl_results *r);
  * has at most 24 characters).  Enqueued on `stream` (may be NULL) on the current device; the call does not wait. */
 int issl_repr_f64_device(const double *d_values, size_t n, char *d_text, uint32_t *d_len, void *stream);
 
+/* ---- RNAfold's exchange: its input written, its answers read, on the device ------------------------------------------ */
+/* Counterpart of src/crackling/Crackling.py:406-497 around the RNAfold program, which stays outside this library: the line
+ * written per guide (:421), the dictionary of line pairs (:439-455), the lookup by guide[1:20] (:458-467), the three text
+ * columns (:469-474), the two regular expressions of :396-397 and the number behind them (:481-497).  An issl_folds belongs
+ * to one consensus and holds, for every row of its fold list, one issl_fold and the three spans ssL1, ssStructure, ssEnergy,
+ * in device memory, where issl_consensus_finish_folds and issl_results_build_rows_folds read them.  A C caller runs
+ *     issl_folds_input_write(f, first, n, "in");   RNAfold --noPS -jN -i in -o out;   issl_folds_read_file(f, first, n, "out");
+ * once per page; RNAfold's two files are the only host-side text of a run.
+ *   input     row r of the fold list is the 101 bytes 'G' + guide[1:20] + the 80 characters of the scaffold (:395) + LF
+ *   pages     a page is a run [first, first + n) of the fold list read with its own text: the reference builds one dictionary
+ *             per page (:439), so a pair that stands only in another page's text is not found.  Rows never read keep
+ *             present == 0 and no text ([rnafold] page-length = 0 reads nothing).  Reading a row twice: ISSL_E_STATE.  A read
+ *             that fails keeps nothing, and its rows can be read again
+ *   lines     as the reference's text-mode file gives them: a line ends at LF, at CR LF (once) or at a lone CR, and at nothing
+ *             else (str.splitlines(), which the package's Python helpers use, also splits at VT, FF and 0x1C-0x1E).  Empty
+ *             lines count; a last line without terminator counts when it is not empty.  Lines 2p and 2p + 1 are pair p; a
+ *             last line without partner is dropped.  A page may have any number of lines
+ *   strip     rstrip() removes trailing bytes of {0x09-0x0D, 0x1C-0x1F, 0x20}; \s is the same set; bytes >= 0x80 are ordinary
+ *   key       bytes [1, 20) of the stripped first line, U read as T; a key shorter than that or with a byte outside ACGT
+ *             matches no guide.  Among pairs with one key the last one in the text wins
+ *   texts     ssL1: the stripped first line.  ssStructure: the stripped second line up to its first 0x20.  ssEnergy: the
+ *             word between the first and the second 0x20 (or the line's end) without its first and last byte, empty (length
+ *             0, not '?') for a word of fewer than 3 bytes.  A second line without 0x20, for a pair a guide of the page
+ *             looks up: ISSL_E_FORMAT (IndexError in the reference)
+ *   :396      with z the last ')' of the stripped second line: the leftmost s with bytes [s + 28, s + 47) equal to
+ *             "((((....))))...))))", [s + 68, s + 100) equal to "((((....))))(((((((...)))))))...", byte s + 100 in \s, byte
+ *             s + 101 '(' and z >= s + 103; the number is [s + 102, z) and scaffold = 1
+ *   :397      otherwise the leftmost p with byte p in \s, byte p + 1 '(' and z >= p + 3; the number is [p + 2, z).  With
+ *             neither the row keeps present == 0 (all 16 bytes zero) and its three texts
+ *   number    blanks and TABs around it, an optional sign, digits[.digits] or .digits with at least one digit; the value is
+ *             the digit string as an integer divided by 10^(fraction digits), one IEEE division: correctly rounded for up to
+ *             15 digits (leading zeros of the integer part not counted); more: ISSL_E_UNSUPPORTED.  Anything else -- an
+ *             exponent, an underscore, inf, a blank behind the sign -- is ISSL_E_FORMAT.  Only pairs a guide of the page
+ *             looks up are judged, as in the reference; the message names the lowest refused row of the fold list
+ * Memory: the pages' text stays on the device until issl_folds_close, for the spans to point into: about 211 bytes per
+ * folded guide (RNAfold's two lines), next to the 64 bytes of its fold and spans.  A line of 2^32 - 1 bytes or more in a
+ * looked-up pair: ISSL_E_UNSUPPORTED.  ISSL_E_ARG for NULL pointers, a range outside the fold list, a cap that is too small
+ * and folds of another consensus; ISSL_E_IO for a file.  The output is deterministic.  The consensus must outlive the
+ * folds; one issl_folds is used by one thread at a time.  The host waits once per read. */
+typedef struct issl_folds issl_folds; /* RNAfold's answers for the fold list of one consensus; owns device memory */
+int issl_folds_open(const issl_consensus *c, issl_folds **out);
+/* n_fold: rows of the fold list; n_read: rows read so far; text_bytes: bytes of the pages' text kept; bytes_per_group: the
+ * bytes whose line ends one thread marks (for tests that place line ends around it).  Any output may be NULL. */
+int issl_folds_info(const issl_folds *f, uint64_t *n_fold, uint64_t *n_read, uint64_t *text_bytes, uint32_t *bytes_per_group);
+/* Device time of the last input and the last read in milliseconds, by HIP events on their stream. */
+int issl_folds_times(const issl_folds *f, double *ms_input, double *ms_read);
+/* RNAfold's input for rows [first, first + n) of the fold list (:421) in device memory, *n_bytes = 101 n; valid until the
+ * next input call on this object or close. */
+int issl_folds_input(issl_folds *f, uint64_t first, uint64_t n, const char **d_text, uint64_t *n_bytes);
+int issl_folds_input_copy(issl_folds *f, uint64_t first, uint64_t n, char *out, size_t cap);
+/* The same into the file at `path`, created or truncated (the reference opens it 'w+'). */
+int issl_folds_input_write(issl_folds *f, uint64_t first, uint64_t n, const char *path);
+/* One page: what RNAfold printed for (a superset of) rows [first, first + n), len bytes of host memory. */
+int issl_folds_read(issl_folds *f, uint64_t first, uint64_t n, const char *text, size_t len);
+int issl_folds_read_file(issl_folds *f, uint64_t first, uint64_t n, const char *path);
+/* n_fold folds and 3 n_fold spans in device memory (NULL for an empty list), valid until close.  A span's offset counts
+ * from *d_text of issl_folds_text_device, whose pointer is valid until the next read; its `reserved` word is the library's
+ * own: which of ',' TAB ';' '|' ' ' (bits 0 .. 4) and of '"', CR, LF (bit 5) the text holds, for the table's quoting. */
+int issl_folds_device(const issl_folds *f, const issl_fold **d_folds, const issl_text_span **d_spans);
+int issl_folds_text_device(const issl_folds *f, const char **d_text, uint64_t *n_bytes);
+/* To host memory; cap: rows there is room for; folds or spans may be NULL. */
+int issl_folds_copy(const issl_folds *f, issl_fold *folds, issl_text_span *spans, size_t cap);
+/* Column `which` (0 ssL1, 1 ssStructure, 2 ssEnergy) of one row to host memory: *len its bytes, (size_t)-1 for a column
+ * without text.  For tests and small callers: one copy from the device per call. */
+int issl_folds_text_copy(const issl_folds *f, uint64_t fold_row, int which, char *out, size_t cap, size_t *len);
+int issl_folds_close(issl_folds *f);
+/* issl_consensus_finish with the folds where they lie; ISSL_E_STATE as there. */
+int issl_consensus_finish_folds(issl_consensus *c, const issl_folds *f);
+/* issl_results_build_rows with the three ss columns from f's spans and text; the fields are quoted on the device, the same
+ * bytes as issl_results_build_rows gives for the same texts. */
+int issl_results_build_rows_folds(const issl_guide_set *gs, const issl_consensus *c, const issl_folds *f,
+                                  const issl_occurrence *d_bowtie, size_t n_bowtie, const issl_genome *genome,
+                                  const uint32_t *d_scored, const double *d_mit, const double *d_cfd, size_t n_scored,
+                                  uint64_t first_row, uint64_t n_rows, const issl_results_config *cfg, issl_results **out);
+
 #ifdef __cplusplus
 }
 #endif
