@@ -14,7 +14,7 @@ all: $(LIB) bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOffta
 # The library: one object per source under build/obj/, the same flags for kernels and host code; the header dependencies
 # come from the compiler (-MMD -MP).
 SRCS = issl_kernels.hip issl_bin.hip issl_verify.hip issl_group.hip issl_replay.hip issl_report.hip issl_extract.hip \
-       issl_locate.hip issl_occur.hip issl_guides.hip issl_consensus.hip issl_build.hip issl_transcripts.hip issl_results.hip issl_results.cpp issl_folds.hip issl_folds.cpp issl_annotation.cpp issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
+       issl_locate.hip issl_occur.hip issl_guides.hip issl_consensus.hip issl_build.hip issl_transcripts.hip issl_results.hip issl_results.cpp issl_folds.hip issl_folds.cpp issl_runlog.hip issl_annotation.cpp issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
 OBJDIR = build/obj
 OBJS   = $(addprefix $(OBJDIR)/,$(addsuffix .o,$(SRCS)))  # (the suffix stays in the name: issl_results.hip and issl_results.cpp)
 COMPILE = $(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<

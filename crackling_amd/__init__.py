@@ -60,10 +60,11 @@ from .results import (  # noqa: F401
     repr_f64,
 )
 from .folds import Folds  # noqa: F401
+from .runlog import BATCH_DTYPE, BatchCounts, RunLog  # noqa: F401
 from . import pipeline  # noqa: F401
 
 __all__ = [
-    "Folds", "PackedFolds", "ResultTable", "read_rnafold_text", "repr_f64", "pipeline",
+    "BATCH_DTYPE", "BatchCounts", "RunLog", "Folds", "PackedFolds", "ResultTable", "read_rnafold_text", "repr_f64", "pipeline",
     "TRANSCRIPT_HITS_DTYPE", "Annotation", "TranscriptHits", "format_hits",
     "BOWTIE_PAMS", "BowtieStep", "OCCURRENCE_DTYPE", "bowtie_input", "format_columns", "read_bowtie_output",
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",

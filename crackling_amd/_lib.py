@@ -179,11 +179,14 @@ _protos = {
     "issl_genome_occurrences_device": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "issl_genome_occurrences_paged": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P]),
     "issl_genome_occurrences_paged_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, _P]),
+    "issl_genome_occurrences_paged_events_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P]),
     "issl_genome_close": (C.c_int, [_P]),
     "issl_guides_extract": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(_P)]),
     "issl_guides_extract_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(_P)]),
     "issl_guides_info": (C.c_int, [_P, _u64p, _u64p, _u64p, _u64p]),
     "issl_guides_record": (C.c_int, [_P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "issl_guides_file_counts": (C.c_int, [_P, C.c_uint64, _P]),
+    "issl_guides_files": (C.c_int, [_P, _u64p]),
     "issl_guides_copy": (C.c_int, [_P, _P, C.c_size_t]),
     "issl_guides_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "issl_guides_close": (C.c_int, [_P]),
@@ -231,6 +234,11 @@ _protos = {
     "issl_consensus_finish_folds": (C.c_int, [_P, _P]),
     "issl_results_build_rows_folds": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_uint64,
                                                 C.POINTER(ResultsConfig), C.POINTER(_P)]),
+    "issl_runlog_batches": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, C.c_size_t, C.c_double, C.c_char_p, C.c_uint64, C.c_uint64,
+                                      C.POINTER(_P)]),
+    "issl_runlog_info": (C.c_int, [_P, _u64p, _u64p, _u64p, _f64p]),
+    "issl_runlog_copy": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t]),
+    "issl_runlog_close": (C.c_int, [_P]),
     "issl_node_create": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "issl_node_score": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P]),
     "issl_node_get_info": (C.c_int, [_P, C.POINTER(NodeInfo)]),

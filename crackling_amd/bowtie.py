@@ -133,9 +133,12 @@ class BowtieStep:
     to off-target scoring.  The signatures are gathered and the rows written on the device.  batch_size: [input]
     batch-size; above 0 the pages start again with every batch of that many rows of the guide set, and `page_starts` keeps
     their boundaries in positions of the selection (an int64 CUDA tensor of its own; None for one batch, whose pages are
-    page_length each)."""
+    page_length each).  events: the pages' boundaries are made in every case and `page_events` (an int32 CUDA tensor, one
+    word per page) receives the figure the reference's log prints as the step's `failed` (Crackling.py:709-717): the groups
+    of the page that reject the site they name while it is not rejected -- events, not rows (include/issl_hip.h,
+    issl_genome_occurrences_paged_events_device).  The rows are the same bytes with and without."""
 
-    def __init__(self, consensus, genome, page_length=0, batch_size=0):
+    def __init__(self, consensus, genome, page_length=0, batch_size=0, events=False):
         import torch
         if not consensus.finished:
             raise ValueError("the consensus is not finished")
@@ -143,13 +146,24 @@ class BowtieStep:
         self.genome = genome
         self.page_length = int(page_length)
         self.batch_size = int(batch_size)
-        self.page_starts = consensus.selection_pages(self.batch_size, self.page_length).clone() if self.batch_size > 0 else None
+        paged = self.batch_size > 0 or events
+        self.page_starts = consensus.selection_pages(self.batch_size, self.page_length).clone() if paged else None
+        self.page_events = torch.zeros(self.page_starts.numel() - 1, dtype=torch.int32, device=self.page_starts.device) if events else None
         sel = consensus.selected_tensor()
         sigs = consensus.guide_set.sigs_tensor()[sel.to(torch.int64)].contiguous()
         self._d_rows = torch.empty((sigs.numel(), OCCURRENCE_DTYPE.itemsize), dtype=torch.uint8, device=sigs.device)
         genome.occurrences_device(sigs, self._d_rows, self.page_length, stream=torch.cuda.current_stream(sigs.device).cuda_stream,
-                                  page_starts=self.page_starts)
+                                  page_starts=self.page_starts, page_events=self.page_events)
         self._rows = None
+
+    def batch_events(self, batches):
+        """The step's `failed` figure of every batch: the events of the pages that start in the batch's share of the
+        selection.  batches: runlog.BATCH_DTYPE entries (selected_first, selected_end).  Two small copies from the device,
+        one word per page each."""
+        if self.page_events is None:
+            raise ValueError("the step was made without events")
+        starts, events = self.page_starts.cpu().numpy()[:-1], self.page_events.cpu().numpy()
+        return [int(events[(starts >= int(b["selected_first"])) & (starts < int(b["selected_end"]))].sum()) for b in batches]
 
     def rows_tensor(self):
         """uint8 CUDA tensor [n_selected, 32]: the rows in device memory."""

@@ -34,6 +34,7 @@
 #include "issl_host.hpp"
 #include "issl_match.hpp"
 #include "issl_radix.hpp"
+#include "issl_runlog.hpp"
 
 namespace issl {
 namespace {
@@ -483,6 +484,13 @@ int copy_from_device(const issl_consensus *c, void *out, const void *src, size_t
 FoldSource consensus_fold_source(const issl_consensus *c)
 {
     return FoldSource{c->device, c->guides, c->n, static_cast<const uint32_t *>(c->fold_list.p), c->n_fold};
+}
+
+RunlogSource consensus_runlog_source(const issl_consensus *c)
+{
+    return RunlogSource{c->device, c->finished, c->n, c->cfg.n, static_cast<const issl_consensus_row *>(c->rows.p),
+                        static_cast<const uint32_t *>(c->fold_list.p), c->n_fold, static_cast<const uint32_t *>(c->selection.p),
+                        c->n_selected};
 }
 
 } // namespace issl

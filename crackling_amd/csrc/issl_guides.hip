@@ -25,6 +25,12 @@
 //   runs     k_guide_gather lines the full guides up in sorted order; k_guide_heads counts run heads per workgroup,
 //            launch_scan ranks them; k_guide_ranks: a head writes where its run starts and its ordinal -- the least of
 //            the run; k_guide_runs: one word per distinct guide, least ordinal << 32 | run length
+//   files    k_guide_files, one thread per match in sorted order: the input of a match is found from its place in the
+//            text, and the k-th word of a run is the guide's k-th occurrence in the reference's walk (ordinals ascend
+//            inside a run).  Per input: its matches, those behind their run's head (they met a guide seen before), the
+//            second words of runs (a guide becomes a repeated one here) and the heads (a new guide).  What the reference's
+//            log prints per file (Crackling.py:254-258); the runs are gone once the call returns, so it is counted here.
+//            Sums in LDS for the first kLdsFiles inputs, one global atomic per counter and workgroup
 //   order    four passes over the ordinal half: distinct guides in first-seen order
 //   finish   k_guide_finish: one thread per guide: guide and place through the ordinal, the record by a search in the
 //            start table (in LDS up to 4096 records), one 32-byte record and the 40-bit signature of guide[0:20]
@@ -327,6 +333,42 @@ __global__ __launch_bounds__(256) void k_guide_finish(const uint64_t *__restrict
     }
 }
 
+struct FileEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~FileEvents()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+// counts[4 f ..]: matches, duplicates, second occurrences, first occurrences of input f (see "files" above).
+constexpr uint32_t kLdsFiles = 256;
+__global__ __launch_bounds__(256) void k_guide_files(const uint64_t *__restrict__ perm, const uint64_t *__restrict__ sorted_keys,
+                                                     const uint64_t *__restrict__ places, uint32_t n,
+                                                     const uint64_t *__restrict__ file_starts, uint32_t n_files,
+                                                     uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t local[4 * kLdsFiles];
+    const uint32_t n_local = n_files < kLdsFiles ? n_files : kLdsFiles;
+    for (uint32_t c = threadIdx.x; c < 4 * n_local; c += 256) local[c] = 0;
+    __syncthreads();
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n) {
+        const uint64_t ord = perm[k] & 0xFFFFFFFFull, key = sorted_keys[k];
+        const uint32_t file = last_not_above(file_starts, n_files, places[ord < n ? ord : 0] >> 1);
+        const bool head = k == 0 || sorted_keys[k - 1] != key;
+        const bool second = !head && (k == 1 || sorted_keys[k - 2] != key);
+        uint32_t *to = file < kLdsFiles ? local + 4 * file : counts + 4ull * file;
+        atomicAdd(to, 1u);
+        atomicAdd(to + (head ? 3 : 1), 1u);
+        if (second) atomicAdd(to + 2, 1u);
+    }
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < 4 * n_local; c += 256)
+        if (local[c]) atomicAdd(counts + c, local[c]);
+}
+
 // ---- host: the FASTA pass ------------------------------------------------------------------------------------------
 
 // What str.strip() removes from ASCII text (py_blank of issl_extract.hip).
@@ -438,8 +480,8 @@ struct OwnStream {
 };
 
 // text and its records -> the set on `device`.  parse_ms: the host pass, for the timing line.
-int extract_guides(const std::string &text, std::vector<FastaRecord> &records, int device, bool timing, double parse_ms,
-                   issl_guide_set **out)
+int extract_guides(const std::string &text, std::vector<FastaRecord> &records, std::vector<uint64_t> &file_starts, int device,
+                   bool timing, double parse_ms, issl_guide_set **out)
 {
     if (int rc = use_device(device)) return rc;
     const uint64_t len = text.size();
@@ -453,6 +495,9 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, i
     }
     std::unique_ptr<issl_guide_set> g(new issl_guide_set());
     g->device = device;
+    const uint32_t n_files = static_cast<uint32_t>(file_starts.size());
+    file_starts.push_back(len);
+    g->file_counts.assign(4ull * n_files, 0u);
     const uint32_t n_records = static_cast<uint32_t>(records.size());
     OwnStream own; // ahead of the arenas: they are released first
     EX_HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
@@ -534,13 +579,36 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, i
                 return ISSL_E_DEVICE;
             }
             Arena ra;
-            const size_t o_rs = ra.reserve(4 * (n_runs + 1ull)), o_ro = ra.reserve(4ull * n_runs);
+            const size_t o_rs = ra.reserve(4 * (n_runs + 1ull)), o_ro = ra.reserve(4ull * n_runs), o_fs = ra.reserve(8ull * n_files),
+                         o_fc = ra.reserve(16ull * n_files);
             EX_HIP_TRY(hipMalloc(&ra.buf.p, ra.size));
             EX_HIP_TRY(hipMalloc(&g->guides.p, 32ull * n_runs));
             EX_HIP_TRY(hipMalloc(&g->sigs.p, 8ull * n_runs));
             uint32_t *run_start = ra.at<uint32_t>(o_rs), *run_ord = ra.at<uint32_t>(o_ro);
             hipLaunchKernelGGL(k_guide_ranks, dim3(n_blocks), dim3(256), 0, stream, sorted_keys, perm, n32, first, n_runs, run_start,
                                run_ord);
+            // -- per input, while the runs are there (in the arena of the runs: no allocation of its own)
+            EX_HIP_TRY(hipMemcpyAsync(ra.at<uint64_t>(o_fs), file_starts.data(), 8ull * n_files, hipMemcpyHostToDevice, stream));
+            EX_HIP_TRY(hipMemsetAsync(ra.at<uint32_t>(o_fc), 0, 16ull * n_files, stream));
+            FileEvents fe;
+            if (timing) { // the kernel alone by HIP events, for the timing line
+                EX_HIP_TRY(hipEventCreate(&fe.a));
+                EX_HIP_TRY(hipEventCreate(&fe.b));
+                EX_HIP_TRY(hipEventRecord(fe.a, stream));
+            }
+            hipLaunchKernelGGL(k_guide_files, dim3(n_blocks), dim3(256), 0, stream, perm, sorted_keys, places, n32, ra.at<uint64_t>(o_fs),
+                               n_files, ra.at<uint32_t>(o_fc));
+            if (timing) EX_HIP_TRY(hipEventRecord(fe.b, stream));
+            EX_HIP_TRY(hipMemcpyAsync(g->file_counts.data(), ra.at<uint32_t>(o_fc), 16ull * n_files, hipMemcpyDeviceToHost, stream));
+            EX_HIP_TRY(hipGetLastError());
+            clock.note("files");
+            if (timing) {
+                float ms = 0;
+                EX_HIP_TRY(hipEventElapsedTime(&ms, fe.a, fe.b)); // (note() synchronised the stream)
+                char buf[64];
+                std::snprintf(buf, sizeof buf, " (k_guide_files %.4f ms by events)", ms);
+                clock.line += buf;
+            }
             // perm and sorted_keys are read no more: the run words and the scratch of their sort take the two buffers
             const dim3 run_grid((n_runs + 255) / 256);
             hipLaunchKernelGGL(k_guide_runs, run_grid, dim3(256), 0, stream, run_start, run_ord, n_runs, wa);
@@ -572,6 +640,7 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, i
     g->n_guides = n_runs;
     g->n_unique = ctr[1];
     g->records = std::move(records);
+    g->file_starts = std::move(file_starts);
     *out = g.release();
     return ISSL_OK;
 }
@@ -612,9 +681,12 @@ int issl_guides_extract(const char *const *files, const size_t *lens, int n_file
         std::string text;
         std::vector<issl::FastaRecord> records;
         std::unordered_set<std::string> recorded;
-        for (int f = 0; f < n_files; ++f)
+        std::vector<uint64_t> file_starts;
+        for (int f = 0; f < n_files; ++f) {
+            file_starts.push_back(text.size());
             if (int rc = issl::append_guide_records(files[f], lens[f], "input " + std::to_string(f), recorded, text, records)) return rc;
-        return issl::extract_guides(text, records, device, timing, issl::StageTimer::now_ms() - t0, out);
+        }
+        return issl::extract_guides(text, records, file_starts, device, timing, issl::StageTimer::now_ms() - t0, out);
     });
 }
 
@@ -639,12 +711,14 @@ int issl_guides_extract_files(const char *const *paths, int n_paths, int device,
         std::vector<issl::FastaRecord> records;
         std::unordered_set<std::string> recorded;
         std::vector<char> buf;
+        std::vector<uint64_t> file_starts;
         for (const auto &path : inputs) {
+            file_starts.push_back(text.size());
             if (int rc = issl::read_file(path, buf)) return rc;
             if (int rc = issl::append_guide_records(buf.data(), buf.size(), "'" + path + "'", recorded, text, records)) return rc;
         }
         buf = std::vector<char>();
-        return issl::extract_guides(text, records, device, timing, issl::StageTimer::now_ms() - t0, out);
+        return issl::extract_guides(text, records, file_starts, device, timing, issl::StageTimer::now_ms() - t0, out);
     });
 }
 
@@ -674,6 +748,31 @@ int issl_guides_record(const issl_guide_set *g, uint64_t r, const char **name, s
     *name = g->records[r].name.data();
     *name_len = g->records[r].name.size();
     *length = g->records[r].length;
+    return ISSL_OK;
+}
+
+int issl_guides_files(const issl_guide_set *g, uint64_t *n_files)
+{
+    if (!g || !n_files) {
+        issl::set_error("null argument");
+        return ISSL_E_ARG;
+    }
+    *n_files = g->file_counts.size() / 4;
+    return ISSL_OK;
+}
+
+int issl_guides_file_counts(const issl_guide_set *g, uint64_t file, issl_guides_file *out)
+{
+    if (!g || !out) {
+        issl::set_error("null argument");
+        return ISSL_E_ARG;
+    }
+    if (file >= g->file_counts.size() / 4) {
+        issl::set_error("input " + std::to_string(file) + " of " + std::to_string(g->file_counts.size() / 4));
+        return ISSL_E_ARG;
+    }
+    const uint32_t *c = g->file_counts.data() + 4 * file;
+    *out = issl_guides_file{c[0], c[1], c[2], c[3]};
     return ISSL_OK;
 }
 

@@ -11,4 +11,7 @@ struct issl_guide_set {
     uint64_t n_guides = 0, n_unique = 0, n_matches = 0;
     issl::DevBuf guides, sigs; // issl_guide[n_guides], uint64_t[n_guides]; null when there is no guide
     std::vector<issl::FastaRecord> records;
+    std::vector<uint64_t> file_starts;  // where every input's records start in the text, and the text's length
+    std::vector<uint32_t> file_counts;  // per input: matches, those that met a guide seen before, guides met here for the
+                                        // second time, guides met here first (issl_guides_file_counts)
 };

@@ -26,6 +26,12 @@
 //                the page whose [starts[p], starts[p + 1]) holds i, found by a binary search (k_occur_target_paged);
 //                k_occur_pages_check refuses boundaries that do not tile [0, n) before any row is written
 //   verdicts     k_occur_verdict: one thread per query completes its row from the word of its source
+//   events       only for issl_genome_occurrences_paged_events_device: the reference's `failed` figure (Crackling.py:709-717)
+//                counts, per page, the groups that reject the query they name while it is not rejected -- the groups are
+//                walked in page order, and of a query named reject, accept, reject the rows know the last group only.
+//                k_occur_target* leaves (named query << 32 | group) per group; a stable radix sort on the named query puts
+//                every query's groups side by side in the order they are walked; k_occur_events counts a rejecting group
+//                whose predecessor names another query or does not reject.  An output beside the rows: they do not change
 // Pieces and pages change no row: a rank's state depends on the text and its key alone, and a page's queries are looked up
 // wherever they lie.  The host waits for the signature check, once per piece before its buffers are released, and at the end.
 #include <hip/hip_runtime.h>
@@ -219,9 +225,11 @@ __device__ __forceinline__ uint64_t last_with_key(const Pages &pg, uint64_t key,
     }
 }
 
-// src[t]: 1 + the last query whose group names query t, 0 when none does.  [lo, hi): the page of query i.
+// src[t]: 1 + the last query whose group names query t, 0 when none does.  [lo, hi): the page of query i.  named (may be
+// null): named[i] = t << 32 | i, for the events.
 __device__ __forceinline__ void note_target(const uint64_t *__restrict__ sites, const unsigned long long *__restrict__ own,
-                                            const Pages &pg, uint32_t *__restrict__ src, uint64_t i, uint64_t lo, uint64_t hi)
+                                            const Pages &pg, uint32_t *__restrict__ src, uint64_t *__restrict__ named, uint64_t i,
+                                            uint64_t lo, uint64_t hi)
 {
     const uint64_t sig = sites[i];
     uint64_t key = 0;
@@ -240,6 +248,7 @@ __device__ __forceinline__ void note_target(const uint64_t *__restrict__ sites, 
     }
     if (t == ~0ull) t = last_with_key(pg, key, lo, hi); // i itself at the least
     if (t != ~0ull) atomicMax(&src[t], static_cast<uint32_t>(i) + 1u);
+    if (named) named[i] = (t << 32) | i; // (t == ~0: behind every query, and k_occur_events passes it over)
 }
 
 __global__ __launch_bounds__(256) void k_occur_target(const uint64_t *__restrict__ sites, const unsigned long long *__restrict__ own,
@@ -249,7 +258,19 @@ __global__ __launch_bounds__(256) void k_occur_target(const uint64_t *__restrict
     if (i >= pg.n) return;
     const uint64_t lo = pg.page_length ? i / pg.page_length * pg.page_length : 0;
     const uint64_t hi = pg.page_length && pg.n - lo > pg.page_length ? lo + pg.page_length : pg.n;
-    note_target(sites, own, pg, src, i, lo, hi);
+    note_target(sites, own, pg, src, nullptr, i, lo, hi);
+}
+
+// First p in [0, n_pages] with starts[p] > i: at least 1, as starts[0] is 0.  The page of query i is p - 1.
+__device__ __forceinline__ uint64_t page_above(const uint64_t *__restrict__ starts, uint64_t n_pages, uint64_t i)
+{
+    uint64_t a = 0, b = n_pages;
+    while (a < b) {
+        const uint64_t mid = (a + b) >> 1;
+        if (starts[mid] <= i) a = mid + 1;
+        else b = mid;
+    }
+    return a;
 }
 
 // The same for pages given by their boundaries (checked by k_occur_pages_check): the page of query i is the last p with
@@ -257,17 +278,41 @@ __global__ __launch_bounds__(256) void k_occur_target(const uint64_t *__restrict
 __global__ __launch_bounds__(256) void k_occur_target_paged(const uint64_t *__restrict__ sites,
                                                             const unsigned long long *__restrict__ own, Pages pg,
                                                             const uint64_t *__restrict__ starts, uint64_t n_pages,
-                                                            uint32_t *__restrict__ src)
+                                                            uint32_t *__restrict__ src, uint64_t *__restrict__ named)
 {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= pg.n) return;
-    uint64_t a = 0, b = n_pages; // first p in [0, n_pages] with starts[p] > i: at least 1, starts[0] is 0
-    while (a < b) {
-        const uint64_t mid = (a + b) >> 1;
-        if (starts[mid] <= i) a = mid + 1;
-        else b = mid;
+    const uint64_t a = page_above(starts, n_pages, i);
+    note_target(sites, own, pg, src, named, i, starts[a - 1], starts[a]);
+}
+
+// named: the words of k_occur_target_paged, sorted by the query they name and, under one query, by group.  Group k counts
+// for its page when it rejects and the group before it names another query or does not reject: the named query is not
+// rejected at that moment.  One atomic per wave whose counting lanes share a page, else one per lane.
+__global__ __launch_bounds__(256) void k_occur_events(const uint64_t *__restrict__ named, const unsigned long long *__restrict__ own,
+                                                      uint64_t n, const uint64_t *__restrict__ starts, uint64_t n_pages,
+                                                      uint32_t *__restrict__ events)
+{
+    const uint64_t k = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+    bool counts = false;
+    uint64_t page = 0;
+    if (k < n) {
+        const uint64_t x = named[k], i = x & 0xFFFFFFFFull;
+        counts = (x >> 32) != 0xFFFFFFFFull && (own[i] >> kOwnNbShift) > 1u;
+        if (counts && k) {
+            const uint64_t y = named[k - 1];
+            if ((y >> 32) == (x >> 32) && (own[y & 0xFFFFFFFFull] >> kOwnNbShift) > 1u) counts = false;
+        }
+        if (counts) page = page_above(starts, n_pages, i) - 1;
     }
-    note_target(sites, own, pg, src, i, starts[a - 1], starts[a]);
+    const uint64_t m = __ballot(counts);
+    if (!m) return;
+    const uint64_t page0 = __shfl(static_cast<unsigned long long>(page), __builtin_ctzll(m));
+    if (__all(!counts || page == page0)) {
+        if (lanes_before(m) == 0 && counts && page < n_pages) atomicAdd(&events[page], static_cast<uint32_t>(__popcll(m)));
+    } else if (counts && page < n_pages) {
+        atomicAdd(&events[page], 1u);
+    }
 }
 
 // Row t: owner, code, source, and the first occurrence of read 0 of its source (its own when no group names it).
@@ -368,6 +413,7 @@ struct PageSpec {
     size_t page_length;
     const uint64_t *d_starts;
     size_t n_pages;
+    uint32_t *d_events = nullptr; // with d_starts: n_pages words, the events of every page
 };
 
 int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const PageSpec &pages, issl_occurrence *d_rows,
@@ -385,7 +431,11 @@ int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const 
     }
     Arena all;
     const size_t o_sorted = all.reserve(8 * n), o_own = all.reserve(8 * n), o_src = all.reserve(4 * n), o_bad = all.reserve(8);
+    const bool events = pages.d_events && pages.d_starts;
+    const size_t o_named = all.reserve(events ? 8 * n : 0), o_named_tmp = all.reserve(events ? 8 * n : 0),
+                 o_named_hist = all.reserve(events ? 4 * radix_hist_words(radix_sort_blocks(n)) : 0);
     EX_HIP_TRY(hipMalloc(&all.buf.p, all.size));
+    if (events && pages.n_pages) EX_HIP_TRY(hipMemsetAsync(pages.d_events, 0, 4 * pages.n_pages, stream));
     uint64_t *sorted_all = all.at<uint64_t>(o_sorted);
     unsigned long long *own_all = all.at<unsigned long long>(o_own);
     uint32_t *src = all.at<uint32_t>(o_src), *bad = all.at<uint32_t>(o_bad); // bad[0]: signatures, bad[1]: boundaries
@@ -417,7 +467,7 @@ int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const 
     const Pages pg{sorted_all, n, pages.d_starts ? 0 : pages.page_length};
     if (pages.d_starts)
         hipLaunchKernelGGL(k_occur_target_paged, dim3(blocks), dim3(256), 0, stream, d_sites, own_all, pg, pages.d_starts,
-                           static_cast<uint64_t>(pages.n_pages), src);
+                           static_cast<uint64_t>(pages.n_pages), src, events ? all.at<uint64_t>(o_named) : nullptr);
     else
         hipLaunchKernelGGL(k_occur_target, dim3(blocks), dim3(256), 0, stream, d_sites, own_all, pg, src);
     EX_HIP_TRY(hipGetLastError());
@@ -430,8 +480,33 @@ int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const 
         hipLaunchKernelGGL(k_occur_verdict<false>, dim3(blocks), dim3(256), 0, stream, own_all, src, static_cast<uint64_t>(n), starts,
                            n_records, reinterpret_cast<ulonglong2 *>(d_rows));
     EX_HIP_TRY(hipGetLastError());
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    if (events) { // (the words lie in group order: a stable sort on the named query alone)
+        clock.note("verdicts");
+        if (g->timing) { // the sort and the count by HIP events, for the timing line
+            EX_HIP_TRY(hipEventCreate(&ev_a));
+            EX_HIP_TRY(hipEventCreate(&ev_b));
+            EX_HIP_TRY(hipEventRecord(ev_a, stream));
+        }
+        const uint64_t *named = radix_sort_async(all.at<uint64_t>(o_named), all.at<uint64_t>(o_named_tmp), n, 32, 64,
+                                                 all.at<uint32_t>(o_named_hist), stream);
+        hipLaunchKernelGGL(k_occur_events, dim3(blocks), dim3(256), 0, stream, named, own_all, static_cast<uint64_t>(n), pages.d_starts,
+                           static_cast<uint64_t>(pages.n_pages), pages.d_events);
+        EX_HIP_TRY(hipGetLastError());
+        if (ev_b) EX_HIP_TRY(hipEventRecord(ev_b, stream));
+    }
     EX_HIP_TRY(hipStreamSynchronize(stream));
-    clock.note("verdicts");
+    clock.note(events ? "events" : "verdicts");
+    if (ev_b) {
+        float ms = 0;
+        const hipError_t e = hipEventElapsedTime(&ms, ev_a, ev_b);
+        (void)hipEventDestroy(ev_a);
+        (void)hipEventDestroy(ev_b);
+        EX_HIP_TRY(e);
+        char buf[64];
+        std::snprintf(buf, sizeof buf, " (sort and k_occur_events %.4f ms by events)", ms);
+        clock.line += buf;
+    }
     if (g->timing) std::fprintf(stderr, "[issl occurrences]%s\n", clock.line.c_str());
     return ISSL_OK;
 }
@@ -505,6 +580,19 @@ int issl_genome_occurrences_paged_device(issl_genome *g, const uint64_t *d_sites
     }
     return issl::abi_call([&] {
         return issl::occurrences_device(g, d_sites, n, issl::PageSpec{0, d_page_starts, n_pages}, d_rows,
+                                        static_cast<hipStream_t>(stream));
+    });
+}
+
+int issl_genome_occurrences_paged_events_device(issl_genome *g, const uint64_t *d_sites, size_t n, const uint64_t *d_page_starts,
+                                                size_t n_pages, issl_occurrence *d_rows, uint32_t *d_page_events, void *stream)
+{
+    if (!g || (n && (!d_sites || !d_rows)) || (!d_page_starts && (n || n_pages)) || (!d_page_events && n_pages)) {
+        issl::set_error("null argument");
+        return ISSL_E_ARG;
+    }
+    return issl::abi_call([&] {
+        return issl::occurrences_device(g, d_sites, n, issl::PageSpec{0, d_page_starts, n_pages, d_page_events}, d_rows,
                                         static_cast<hipStream_t>(stream));
     });
 }

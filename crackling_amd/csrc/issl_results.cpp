@@ -55,6 +55,8 @@ struct Inputs {
     uint64_t first_row, n_rows; // the rows of the set the text holds
 };
 
+} // namespace
+
 // The method as the scorer matches it (exactly) and as the caller reads it (stripped, lower case): issl_verdicts.
 void method_rules(const char *method, ResultArgs &a)
 {
@@ -75,6 +77,8 @@ void method_rules(const char *method, ResultArgs &a)
     default: a.rule = kRuleNone; break;
     }
 }
+
+namespace {
 
 // Host text -> pool and span tables.  No device call.
 int prepare_text(const Inputs &in, ResultPool &pool, std::vector<issl_text_span> &headers, std::vector<issl_text_span> &ss,

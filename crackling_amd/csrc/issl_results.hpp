@@ -37,6 +37,9 @@ struct ResultArgs {
     char delimiter;
 };
 
+// rule, print_mit and print_cfd of `a` from [offtargetscore] method as configured (issl_results.cpp; issl_runlog.hip counts by it).
+void method_rules(const char *method, ResultArgs &a);
+
 inline uint32_t result_groups(uint32_t n) { return (n + kResultRows - 1) / kResultRows; }
 
 // inverse[list[i]] = i for i < n_list (inverse is n words of kNoRow before).

@@ -9,9 +9,11 @@ is data: the pages of the Bowtie step and of RNAfold start again with every batc
 piece at a time (`batches`, `run_to_file`); `run` joins the pieces.
 """
 import contextlib
+import os
 
 import numpy as np
 
+from .bowtie import BowtieStep
 from .consensus import FOLD_DTYPE, SCAFFOLD, Consensus, read_rnafold_output
 from .results import PackedFolds, ResultTable, read_rnafold_text
 from .scorer import GuideSet
@@ -52,22 +54,74 @@ def _fold(c, config, rnafold):
 
 def _fold_device(c, config, rnafold):
     """The same on the device -> the Folds of c, read: RNAfold's input comes from Folds.input(), its answer goes to
-    Folds.read(), one page at a time; the page logic is that of _fold."""
+    Folds.read(), one page at a time; the page logic is that of _fold.  An `rnafold` with a method fold_page(folds, first,
+    n) is handed the page itself (the driver's: RNAfold's two files are written and read by the library)."""
     folds = c.folds()
+
+    def page(a, n):
+        if hasattr(rnafold, "fold_page"):
+            rnafold.fold_page(folds, a, n)
+        else:
+            folds.read(rnafold(folds.input(a, n).decode()), a, n)
+
     try:
         page_length = config.get("rnafold_page_length")
         if page_length is None:
-            folds.read(rnafold(folds.input().decode()))
+            page(0, c.n_fold)
         elif int(page_length) != 0:
             for a, b in _fold_pages(c.fold_rows, c.n_guides, int(config.get("batch_size", 0)), int(page_length)):
-                folds.read(rnafold(folds.input(a, b - a).decode()), a, b - a)
+                page(a, b - a)
     except BaseException:
         folds.close()
         raise
     return folds
 
 
-def batches(inputs, genome, index, config, rnafold):
+def _input_files(inputs):
+    """(name, bytes) of every input as GuideSet.extract reads them, for the log: a path stands for itself, a lone
+    directory for its top-level files in reverse sorted name order, a blob is 'input <k>'."""
+    inputs = list(inputs)
+    if not all(isinstance(x, (str, os.PathLike)) for x in inputs):
+        return [(f"input {k}", len(x)) for k, x in enumerate(inputs)]
+    paths = [os.fspath(x) for x in inputs]
+    if len(paths) == 1 and os.path.isdir(paths[0]):
+        paths = [os.path.join(paths[0], f) for f in sorted(os.listdir(paths[0]), reverse=True) if os.path.isfile(os.path.join(paths[0], f))]
+    return [(p, os.path.getsize(p)) for p in paths]
+
+
+def _log_inputs(log, gs, inputs):
+    """The extraction block of the log (Crackling.py:171-261).  An input without a match stops the reference with a
+    ZeroDivisionError at :254, before it has written anything: refused here, by name."""
+    files, counts = _input_files(inputs), gs.file_counts
+    if len(files) != len(counts):
+        raise ValueError(f"{len(files)} inputs, counts of {len(counts)}")
+    for (name, _), c in zip(files, counts):
+        if int(c[0]) == 0:
+            raise ValueError(f"no candidate guide in {name}: the reference stops there (division by zero, Crackling.py:254)")
+    log.begin()
+    total, done, repeated, distinct = sum(size for _, size in files), 0, 0, 0
+    for (name, size), c in zip(files, counts):
+        done, repeated, distinct = done + size, repeated + int(c[2]), distinct + int(c[3])
+        log.input_file(name, int(c[0]), repeated, int(c[1]), distinct, done / total * 100.0)
+
+
+def _not_found_guides(c, gs, positions):
+    """(position in the fold list, 20-mer) for the positions given, gathered on the device."""
+    import ctypes as C
+    import torch
+    from ._lib import lib, check
+    from .scorer import _DeviceArray, decode_guides
+    if not len(positions):
+        return []
+    d_rows, n_fold = C.c_void_p(), C.c_uint64()
+    check(lib.issl_consensus_fold_list(c._h, C.byref(d_rows), C.byref(n_fold)))
+    fold = torch.as_tensor(_DeviceArray(c, d_rows.value, (n_fold.value,), "<i4"), device=f"cuda:{c.device}")
+    at = torch.from_numpy(np.asarray(positions, dtype=np.int64)).to(fold.device)
+    sigs = gs.sigs_tensor()[fold[at].to(torch.int64)].cpu().numpy().astype(np.uint64)
+    return list(zip((int(p) for p in positions), decode_guides(sigs, 20)))
+
+
+def batches(inputs, genome, index, config, rnafold, log=None):
     """inputs: the FASTA inputs of GuideSet.extract (bytes blobs or paths); genome: a Genome (the Bowtie step's text) and
     index: an uploaded IsslIndex, both on the device the guides go to, or None when config["offtargetscore"] is false;
     rnafold: a callable that takes RNAfold's input (the lines of Consensus.fold_input(), a str) and returns what RNAfold
@@ -95,6 +149,12 @@ def batches(inputs, genome, index, config, rnafold):
                       the rest (IsslError -3 or -4).  RNAfold prints none of these
       delimiter       [output] delimiter (",")
       device          the GPU (0)
+      offtarget_page_length   [offtargetscore] page-length: read only for `log`, whose off-target block prints one figure per
+                      page; no byte of the file depends on it here (absent: 5000000, the reference's own)
+    log: None, or a crackling_amd.RunLog: the stages feed it the reference's log -- the extraction block from the counts the
+    extraction keeps per input, a batch's blocks from the counts made on the device over the resident rows
+    (crackling_amd.runlog.BatchCounts, the Bowtie step's events per page) ahead of the batch's piece.  Needs the device
+    reader.  Without it the call does exactly what it did before.
     -> a generator of the bytes of the reference's output file for these inputs, in pieces: the header row, then one piece
     per batch (pieces of at most SCORE_CHUNK rows when the run is one batch).  One piece's text is alive at a time, on the
     device and on the host; the stages stay open until the generator is exhausted or closed."""
@@ -106,8 +166,12 @@ def batches(inputs, genome, index, config, rnafold):
     reader = str(config.get("rnafold_reader", "device"))
     if reader not in ("device", "host"):
         raise ValueError('rnafold_reader: "device" or "host"')
+    if log is not None and reader != "device":
+        raise ValueError("log: needs rnafold_reader 'device'")
     with GuideSet.extract(inputs, device) as gs, Consensus(gs, **{k: config[k] for k in CONSENSUS_KEYS if k in config}) as c, \
             contextlib.ExitStack() as stack:
+        if log is not None:
+            _log_inputs(log, gs, inputs)
         folds_text = device_folds = None
         if c.n_fold and reader == "device":
             device_folds = _fold_device(c, config, rnafold)
@@ -121,7 +185,7 @@ def batches(inputs, genome, index, config, rnafold):
             c.finish()
         bowtie = scores = None
         if config.get("offtargetscore", True):
-            bowtie = c.bowtie(genome, int(config.get("page_length", 0)), batch_size)
+            bowtie = BowtieStep(c, genome, int(config.get("page_length", 0)), batch_size, events=log is not None)
             rows = bowtie.selected_tensor()
             sigs = gs.sigs_tensor()[rows.to(torch.int64)].contiguous()
             mit = torch.empty(sigs.numel(), dtype=torch.float64, device=sigs.device)
@@ -132,10 +196,26 @@ def batches(inputs, genome, index, config, rnafold):
                 index.score_device(sigs[a:b], mit[a:b], cfd[a:b], int(config.get("max_distance", 4)), threshold, method, stream=stream)
             scores = (rows, mit, cfd)
         common = (bowtie, scores, config.get("delimiter", ","), method, threshold)
+        counts = None
+        if log is not None:
+            from .runlog import DEFAULT_PAGE_LENGTH, BatchCounts
+            page = config.get("offtarget_page_length")
+            counts = BatchCounts(c, device_folds, bowtie, scores, threshold, method, batch_size,
+                                 DEFAULT_PAGE_LENGTH if page is None else int(page))
+            events = bowtie.batch_events(counts.batches) if bowtie is not None else [0] * len(counts.batches)
+            # (under [rnafold] page-length 0 every row is not found and the log prints none of them)
+            fold_page = config.get("rnafold_page_length")
+            missing = _not_found_guides(c, gs, counts.not_found) if fold_page is None or int(fold_page) > 0 else []
+            batch_rows = batch_size if 0 < batch_size < gs.n_guides else 0
         with ResultTable(c, None, *common, rows=(0, 0)) as table:
             piece = table.to_bytes()
         yield piece
         for a, b in _row_pieces(gs.n_guides, batch_size):
+            if counts is not None and (batch_rows or a == 0):
+                k = a // batch_rows if batch_rows else 0
+                row = counts.batches[k]
+                log.batch(k, len(counts.batches), row, counts.page_failed[row["page_first"]:row["page_end"]],
+                          [m for m in missing if row["fold_first"] <= m[0] < row["fold_end"]], events[k])
             texts = device_folds
             if folds_text is not None:
                 lo, hi = np.searchsorted(c.fold_rows, (a, b))
@@ -143,19 +223,25 @@ def batches(inputs, genome, index, config, rnafold):
             with ResultTable(c, texts, *common, rows=(a, b - a), header=False) as table:
                 piece = table.to_bytes()
             yield piece
+        if log is not None:
+            log.end()
 
 
-def run(inputs, genome, index, config, rnafold):
+def run(inputs, genome, index, config, rnafold, log=None):
     """The arguments of `batches` -> the bytes of the reference's output file for these inputs."""
-    return b"".join(batches(inputs, genome, index, config, rnafold))
+    return b"".join(batches(inputs, genome, index, config, rnafold, log=log))
 
 
-def run_to_file(path, inputs, genome, index, config, rnafold):
+def run_to_file(path, inputs, genome, index, config, rnafold, log=None):
     """The same, appended to the file at `path` piece by piece, as the reference, which opens its file with 'a+', adds
     to what is there.  -> the number of bytes written."""
     written = 0
-    with open(path, "ab") as out:
-        for piece in batches(inputs, genome, index, config, rnafold):
+    with contextlib.ExitStack() as stack:
+        # with a log a run can be refused before its first piece (an input without a match) and then leaves no file
+        out = None if log is not None else stack.enter_context(open(path, "ab"))
+        for piece in batches(inputs, genome, index, config, rnafold, log=log):
+            if out is None:
+                out = stack.enter_context(open(path, "ab"))
             out.write(piece)
             written += len(piece)
     return written

@@ -506,10 +506,11 @@ class Genome:
                                           rows.ctypes.data if len(sigs) else None))
         return rows
 
-    def occurrences_device(self, d_sites, d_rows, page_length=0, stream=None, page_starts=None):
+    def occurrences_device(self, d_sites, d_rows, page_length=0, stream=None, page_starts=None, page_events=None):
         """d_sites: int64 CUDA tensor of packed signatures (left as it is); d_rows: uint8 CUDA tensor of 32 bytes per site
         (OCCURRENCE_DTYPE); page_starts: None, or a 64-bit integer CUDA tensor of n_pages + 1 boundaries in place of
-        page_length.  Returns when the rows are written."""
+        page_length; page_events: with page_starts, an int32 CUDA tensor of n_pages words that receives the step's `failed`
+        figure of every page (issl_genome_occurrences_paged_events_device).  Returns when the rows are written."""
         n = d_sites.numel()
         if d_rows.numel() * d_rows.element_size() < OCCURRENCE_DTYPE.itemsize * n:
             raise ValueError("d_rows holds fewer than 32 bytes per site")
@@ -517,9 +518,18 @@ class Genome:
         if page_starts is not None:
             if page_starts.dim() != 1 or page_starts.numel() == 0 or page_starts.element_size() != 8 or not page_starts.is_contiguous():
                 raise ValueError("page_starts: a contiguous tensor of n_pages + 1 64-bit boundaries")
+            if page_events is not None:
+                if page_events.numel() != page_starts.numel() - 1 or page_events.element_size() != 4 or not page_events.is_contiguous():
+                    raise ValueError("page_events: a contiguous tensor of n_pages 32-bit words")
+                check(lib.issl_genome_occurrences_paged_events_device(
+                    self._h, d_sites.data_ptr() if n else None, n, page_starts.data_ptr(), page_starts.numel() - 1,
+                    d_rows.data_ptr() if n else None, page_events.data_ptr() if page_events.numel() else None, stream))
+                return
             check(lib.issl_genome_occurrences_paged_device(self._h, d_sites.data_ptr() if n else None, n, page_starts.data_ptr(),
                                                            page_starts.numel() - 1, d_rows.data_ptr() if n else None, stream))
             return
+        if page_events is not None:
+            raise ValueError("page_events needs page_starts")
         check(lib.issl_genome_occurrences_device(self._h, d_sites.data_ptr() if n else None, n, int(page_length),
                                                  d_rows.data_ptr() if n else None, stream))
 
@@ -567,7 +577,7 @@ class GuideSet:
         for r in range(n_rec.value):
             check(lib.issl_guides_record(self._h, r, C.byref(name), C.byref(name_len), C.byref(length)))
             self.records.append((C.string_at(name, name_len.value) if name_len.value else b"", length.value))
-        self._guides = None
+        self._guides = self._file_counts = None
 
     @classmethod
     def extract(cls, inputs, device=0):
@@ -599,6 +609,21 @@ class GuideSet:
             check(lib.issl_guides_copy(self._h, out.ctypes.data, len(out)))
             self._guides = out
         return self._guides
+
+    @property
+    def file_counts(self):
+        """uint32 array [n_inputs, 4], counted during the extraction (issl_guides_file_counts): per input, in the order the
+        inputs were read, its matches, those of them that met a guide seen before, the guides whose second occurrence lies
+        in it and the guides whose first occurrence lies in it.  What the reference's log prints per file
+        (Crackling.py:254-258): its two running figures are the sums of the last two columns over the inputs so far."""
+        if self._file_counts is None:
+            n, out, rows = C.c_uint64(), (C.c_uint32 * 4)(), []
+            check(lib.issl_guides_files(self._h, C.byref(n)))
+            for f in range(n.value):
+                check(lib.issl_guides_file_counts(self._h, f, out))
+                rows.append(list(out))
+            self._file_counts = np.array(rows, dtype=np.uint32).reshape(-1, 4)
+        return self._file_counts
 
     def strings(self):
         """The 23-mers as str, in first-seen order."""

@@ -577,6 +577,15 @@ int issl_genome_occurrences_paged(issl_genome *g, const uint64_t *sites, size_t 
                                   issl_occurrence *rows);
 int issl_genome_occurrences_paged_device(issl_genome *g, const uint64_t *d_sites, size_t n, const uint64_t *d_page_starts,
                                          size_t n_pages, issl_occurrence *d_rows, void *stream);
+/* The same rows, byte for byte, and beside them the figure the reference's log prints for the step (:709-717, `failed`):
+ * d_page_events[p], n_pages words of device memory, = the groups of page p that reject the site they name while that site is
+ * not rejected.  The groups of a page are walked in the order of its sites, and several can name one site -- sites of a page
+ * that share a 20-mer name the last of them, and a strand-1 guide can name the strand-0 guide of its window (above) -- so this
+ * is a count of events, not of rows: a site named reject, accept counts once and ends accepted; named reject, accept, reject
+ * it counts twice; the rows know the last group only.  The figure of a batch is the sum over its pages.  A NULL
+ * d_page_events with n_pages above 0: ISSL_E_ARG. */
+int issl_genome_occurrences_paged_events_device(issl_genome *g, const uint64_t *d_sites, size_t n, const uint64_t *d_page_starts,
+                                                size_t n_pages, issl_occurrence *d_rows, uint32_t *d_page_events, void *stream);
 
 /* ---- candidate guides from FASTA: Crackling's extraction step ------------------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:151-305: the candidate 23-mers of the inputs, on `device`; no CPU fallback.
@@ -626,6 +635,19 @@ int issl_guides_extract_files(const char *const *paths, int n_paths, int device,
 /* n_matches: all occurrences (the sum of `seen`); n_unique: guides with seen == 1. */
 int issl_guides_info(const issl_guide_set *g, uint64_t *n_guides, uint64_t *n_unique, uint64_t *n_matches, uint64_t *n_records);
 int issl_guides_record(const issl_guide_set *g, uint64_t r, const char **name, size_t *name_len, uint64_t *length);
+/* What the reference's log prints per input (Crackling.py:254-258), counted during the extraction, where the sorted runs
+ * of equal guides still exist: input `file` in the order the inputs were read (a directory's files as they were expanded).
+ * The running figures of the log are sums over the inputs so far: distinct guides = the sum of first_seen, guides that are
+ * not unique (seen twice or more) = the sum of second_seen.  An input beyond the last: ISSL_E_ARG. */
+typedef struct {
+    uint32_t identified;  /* matches of this input */
+    uint32_t duplicates;  /* those of them that met a guide seen before, in this input or an earlier one */
+    uint32_t second_seen; /* guides whose second occurrence lies in this input */
+    uint32_t first_seen;  /* guides whose first occurrence lies in this input */
+} issl_guides_file;       /* 16 bytes */
+int issl_guides_file_counts(const issl_guide_set *g, uint64_t file, issl_guides_file *out);
+/* The number of inputs the set was extracted from (a directory counts by its files). */
+int issl_guides_files(const issl_guide_set *g, uint64_t *n_files);
 /* The guides to host memory, first-seen order; cap < n_guides: ISSL_E_ARG. */
 int issl_guides_copy(const issl_guide_set *g, issl_guide *out, size_t cap);
 /* The guides and their signatures in the memory of the set's device, n_guides each, valid until the set is closed. */
@@ -936,6 +958,60 @@ int issl_results_build_rows_folds(const issl_guide_set *gs, const issl_consensus
                                   const issl_occurrence *d_bowtie, size_t n_bowtie, const issl_genome *genome,
                                   const uint32_t *d_scored, const double *d_mit, const double *d_cfd, size_t n_scored,
                                   uint64_t first_row, uint64_t n_rows, const issl_results_config *cfg, issl_results **out);
+
+/* ---- the run's log: what every batch's stages saw and failed ---------------------------------------------------------- */
+/* Counterpart of the figures src/crackling/Crackling.py:305-598 and :727-837 print into the run's log, counted on the device
+ * over the rows the stages left there; nothing per row crosses to the host and there is no CPU fallback.  (The name is not
+ * issl_stats: that is the scorer's.)  A batch is batch_size consecutive rows of the guide set ([input] batch-size; 0, or a
+ * size of at least the set: one batch); an empty set has no batch.  Per batch, with the codes of issl_consensus_row
+ * (0 rejected, 1 accepted, 2 untested, 3 error):
+ *   loaded      (:305) rows of the batch
+ *   g20, lead_t, at, tttt   (:310-384) tested = rows whose code is 0 or 1, failed = code 0
+ *   ss          (:390-507) over the batch's rows of the fold list: tested = code 0 or 1, failed = code 0, erred = code 3,
+ *               not_found = rows without an answer: present == 0 in the folds, or code 2 when no folds are given (the
+ *               consensus leaves exactly the rows with present == 0 untested).  The not-found rows of all batches, as
+ *               positions in the fold list, ascending, are kept as well (the reference prints a line for each)
+ *   mm10db      (:513-534) accepted = code 1, failed = every other row of the batch
+ *   sgrna       (:541-577) tested = code 0 or 1, failed = code 0
+ *   consensus   (:582-598) tested = rows of the batch, failed = count < [consensus] n
+ *   positions   fold, selected, scored: the batch's share [first, end) of the fold list, of the selection and of d_scored
+ *               -- all three ascending row lists -- from which the host derives every page's number of guides
+ *   bowtie_rejected   rows of the batch's share of the selection whose issl_occurrence ends with code 0 (0 without d_bowtie).
+ *               NOT the Bowtie step's `failed` figure (:709-717), which counts events, not rows
+ *   pages       (:727-837) the batch's scored rows in pages of offtarget_page_length ([offtargetscore] page-length): pages
+ *               [page_first, page_end) of the page array; page_failed[p] = rows of page p that `method` and `threshold`
+ *               reject, by the rule of issl_verdicts on the scores read through the scorer's "%f" text.  A page length of 0
+ *               is one page per batch, also for a batch without a scored row; above 0 a batch without one has no page
+ *               (Paginator.py).  A method that names no rule rejects nothing
+ * Every count is an integer sum: the result is the same on every run.  d_bowtie (aligned with the selection, may be NULL
+ * with n_bowtie == 0), d_scored, d_mit, d_cfd (n_scored each; all NULL with 0) are device memory on the consensus' device
+ * and must be complete when the call is made; the call returns when the counts are.  f may be NULL.
+ * Errors: ISSL_E_ARG for NULL c, method or out, folds of another consensus, n_bowtie that differs from the selection,
+ * d_scored without both scores and n_scored above the number of guides; ISSL_E_STATE for an unfinished consensus;
+ * ISSL_E_DEVICE without a device; *out is NULL after a failure. */
+typedef struct issl_runlog issl_runlog; /* opaque; owns device memory */
+typedef struct {
+    uint32_t loaded;
+    uint32_t g20_tested, g20_failed, lead_t_tested, lead_t_failed, at_tested, at_failed, tttt_tested, tttt_failed;
+    uint32_t ss_tested, ss_failed, ss_erred, ss_not_found;
+    uint32_t mm10db_accepted, mm10db_failed;
+    uint32_t sgrna_tested, sgrna_failed;
+    uint32_t consensus_tested, consensus_failed;
+    uint32_t fold_first, fold_end, selected_first, selected_end, scored_first, scored_end;
+    uint32_t page_first, page_end;
+    uint32_t bowtie_rejected;
+} issl_runlog_batch; /* 112 bytes, no padding */
+
+int issl_runlog_batches(const issl_consensus *c, const issl_folds *f, const issl_occurrence *d_bowtie, size_t n_bowtie,
+                        const uint32_t *d_scored, const double *d_mit, const double *d_cfd, size_t n_scored, double threshold,
+                        const char *method, uint64_t batch_size, uint64_t offtarget_page_length, issl_runlog **out);
+/* n_batches; n_pages: the off-target pages of all batches; n_not_found: fold-list rows without an answer; ms: device time
+ * of the counting launches by HIP events on their stream.  Any output may be NULL. */
+int issl_runlog_info(const issl_runlog *r, uint64_t *n_batches, uint64_t *n_pages, uint64_t *n_not_found, double *ms);
+/* To host memory: every array that is not NULL is copied whole; its cap below the number there is: ISSL_E_ARG. */
+int issl_runlog_copy(const issl_runlog *r, issl_runlog_batch *batches, size_t cap_batches, uint32_t *page_failed,
+                     size_t cap_pages, uint32_t *not_found, size_t cap_not_found);
+int issl_runlog_close(issl_runlog *r);
 
 #ifdef __cplusplus
 }
