@@ -11,6 +11,7 @@ import pytest
 
 import crackling_amd as ca
 import guides_util as gu
+import many_records_util as mr
 
 pytestmark = pytest.mark.gpu
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -161,6 +162,15 @@ def test_more_records_than_the_start_table_in_lds():
     fasta = b"".join(parts)
     records, want = _extract_checked([fasta], [fasta])
     assert len(records) == 4300 and len(want) > 2000 and int(want["record"].max()) > 4200
+    k = mr.switch()  # and at the switch itself: k records are the largest table of the LDS fill loop, k + 1 the first in global memory
+    assert k < 4300
+    for n_records in (k, k + 1):
+        fasta, planted = mr.fasta(n_records)
+        records, want = _extract_checked([fasta], [fasta])
+        assert len(records) == n_records and len(want) > 2000 and int(want["record"].max()) == n_records - 1
+        ends = want[want["record"] == n_records - 1]
+        assert {planted["first"].encode(), planted["last"].encode()} <= set(ends["guide23"].tolist())
+        assert {0, len(records[-1][1]) - 23} <= set(ends["start"].tolist())
 
 
 # ---- a random genome ------------------------------------------------------------------------------------------------------
