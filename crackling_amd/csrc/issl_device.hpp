@@ -282,11 +282,17 @@ struct ScanItem {
                          // group): a unit is 2048 consecutive candidates of the bucket from there on -- whole tiles for
                          // bucket-level items, a window that may straddle two tiles for the pruned scan's
     uint32_t window;     // candidates of the item: from offset (window & 0xFFFF) of its first unit up to (not including)
-                         // offset (window >> 16) of its last unit; the rest are padding or a neighbouring group's
+                         // offset (window >> 16) of its last unit; the rest are padding or a neighbouring group's.
+                         // Pruned scan (single-unit items): the first offset is below 32 -- a group's units start in the
+                         // lane group of its first candidate (group_units, issl_bin.hip) -- and the scan relies on it: only
+                         // lane 0 of a full unit, only the first lanes of a short one, look at it
     uint32_t shape;      // candidates per lane of the item's units: 32 = a full unit of 2048 candidates, one guide per
                          // pass; 16 / 8 = the SHORT last unit of a successor-byte group (<= 1024 / <= 512 candidates):
                          // every register then holds the lane's 16 / 8 candidates two / four times over and a pass
-                         // compares two / four guides at once, with masks the wave makes in LDS (short_unit_masks)
+                         // compares two / four guides at once, with masks the wave makes in LDS (short_unit_masks).
+                         // Nothing else than 8, 16, 32: the scan takes guides per pass, lane shifts and byte selector
+                         // from it with scalar selects (no division), and the plane quads of the item's slice from a
+                         // table (kFineOrders), so the item carries no derived geometry and stays 48 bytes
     uint32_t gmid;       // pruned scan: the group's class-0 guides (successor byte = the group's own) sit in the slots from
                          // here on, its class-1 guides (one mismatch there) in front of them (fine_word, issl_bin.hip)
 };

@@ -146,23 +146,28 @@ __device__ __forceinline__ uint32_t near_plane_masks(const uint32_t (&c)[kPlanes
 
 // Masks of up to 8 passes of a short unit (guide slots g0 .. g0 + 8 * per - 1) into the wave's own 1 KiB of LDS: lane
 // (pass i, quarter q) makes the four words 4q .. 4q + 3 of pass i: bit p of each of the pass's `per` guide words, spread
-// over that guide's field of `shape` bits.
-__device__ __forceinline__ void short_unit_masks(const uint32_t *__restrict__ gword_stream, uint32_t g0, uint32_t shape,
+// over that guide's field of `shape` bits.  wide: shape 16, two guides per pass (their words arrive as one 8-byte load);
+// else shape 8, four guides (one 16-byte load: g0 is a multiple of 8).
+__device__ __forceinline__ void short_unit_masks(const uint32_t *__restrict__ gword_stream, uint32_t g0, bool wide,
                                                  uint32_t lane, uint4 *lds_masks)
 {
-    const uint32_t per = 32u / shape, field = shape == 16u ? 0xFFFFu : 0xFFu;
     const uint32_t i = lane >> 3, q = lane & 7u;
-    uint32_t gw[4];
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) gw[j] = j < per ? gword_stream[g0 + i * per + j] : 0u;
     uint32_t m[4];
+    if (wide) {
+        const uint2 gw = *reinterpret_cast<const uint2 *>(gword_stream + g0 + 2u * i);
+        const uint32_t a = gw.x >> (4u * q), b = gw.y >> (4u * q);
 #pragma unroll
-    for (uint32_t r = 0; r < 4; ++r) {
-        const uint32_t p = 4u * q + r;
-        uint32_t x = 0;
+        for (uint32_t r = 0; r < 4; ++r)
+            m[r] = ((0u - ((a >> r) & 1u)) & 0xFFFFu) | ((0u - ((b >> r) & 1u)) << 16);
+    } else {
+        const uint4 gw = *reinterpret_cast<const uint4 *>(gword_stream + g0 + 4u * i);
+        const uint32_t t[4] = {gw.x >> (4u * q), gw.y >> (4u * q), gw.z >> (4u * q), gw.w >> (4u * q)};
 #pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) x |= (0u - ((gw[j] >> p) & 1u)) & (field << ((j * shape) & 31u)) & (j < per ? ~0u : 0u);
-        m[r] = x;
+        for (uint32_t r = 0; r < 4; ++r) {
+            // bit r of the four words into bits 0, 8, 16, 24; times 255 = each spread over its byte
+            const uint32_t bits = ((t[0] >> r) & 1u) | (((t[1] >> r) & 1u) << 8) | (((t[2] >> r) & 1u) << 16) | (((t[3] >> r) & 1u) << 24);
+            m[r] = bits * 255u;
+        }
     }
     lds_masks[i * 8u + q] = make_uint4(m[0], m[1], m[2], m[3]);
 }
@@ -332,11 +337,43 @@ struct alignas(4) GuideGroupAny {
     uint32_t w[kGuideGroup];
 };
 
+// fine_order as a table: the three plane quads of a slice's 12 positions in 2 bits each, the five 8-bit slices side by side
+// (narrow slices: the same three quads for every slice).
+constexpr uint32_t fine_order_code(uint32_t slice, uint32_t slice_width)
+{
+    return fine_order(slice, 0u, slice_width) | (fine_order(slice, 1u, slice_width) << 2) | (fine_order(slice, 2u, slice_width) << 4);
+}
+constexpr uint32_t kFineOrders = fine_order_code(0u, 8u) | (fine_order_code(1u, 8u) << 6) | (fine_order_code(2u, 8u) << 12) |
+                                 (fine_order_code(3u, 8u) << 18) | (fine_order_code(4u, 8u) << 24);
+constexpr uint32_t kFineOrderNarrow = fine_order_code(0u, 4u);
+static_assert(fine_order_code(0u, 2u) == kFineOrderNarrow && fine_order_code(7u, 4u) == kFineOrderNarrow && (kFineOrders & 63u) == kFineOrderNarrow,
+              "narrow slices: one order, that of slice 0 of the 8-bit ones");
+
 // Cold block of the scan: the wave knows that SOME lane has a candidate within thr of a guide.  `ok` = this lane's
 // plane of such candidates; bit q of it is candidate q % (1 << w_log) of the lane -- which sits at offset off0 + that of
 // `tile` (the lane's own: a window of the pruned scan straddles two tiles) -- against the guide in slot gslot + (q >>
 // w_log) (full units: w_log = 5, one guide per pass).
-__device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, uint32_t w_log, uint32_t tile, uint32_t off0,
+// What of a record is the lane's alone is made once per unit (RecLane): the two words of raw_record(0, tile, off0); a round
+// ORs the candidate's number into the low word and the (wave-uniform) guide slot into the high one.  (The store keeps its
+// 64-bit lane address: a scalar base + 8 * rank as a 32-bit offset, with the lane's remaining candidates cleared outside the
+// branch, is five vector operations fewer per noting pass and a LONGER launch -- uniform index +-0, skewed one +2 %, same-box
+// against this form, profiles/ab_scan_trim_bench.log.)
+struct RecLane {
+    uint32_t lo, hi;
+};
+__device__ __forceinline__ RecLane rec_lane(uint32_t tile, uint32_t off0)
+{
+    return {(tile << 11) | off0, tile >> 21};
+}
+// ... of the pruned scan's units, whose lanes may sit in two tiles: the lane's candidates start `cand` candidates behind
+// lane group `group_abs` of the stream (tile * 64 + group), i.e. at tile << 11 | offset = 32 * group_abs + cand.
+__device__ __forceinline__ RecLane rec_lane_at(uint32_t group_abs, uint32_t cand)
+{
+    const uint64_t at = (static_cast<uint64_t>(group_abs) << 5) + cand;
+    return {static_cast<uint32_t>(at), static_cast<uint32_t>(at >> 32)};
+}
+
+__device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, uint32_t w_log, const RecLane &rl,
                                                 uint32_t lane, RawWriter &w, uint64_t *raw, uint32_t *raw_used,
                                                 uint32_t max_chunks, Counters *counters)
 {
@@ -356,7 +393,9 @@ __device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, uin
             ok &= ok - 1u;
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(who >> 32),
                                                             __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(who), 0u));
-            w.chunk[w.fill + rank] = raw_record(gslot + (q >> w_log), tile, off0 + (q & ((1u << w_log) - 1u)));
+            // = raw_record(gslot + (q >> w_log), tile, off0 + (q & ((1u << w_log) - 1u))): off0 is a multiple of 1 << w_log
+            const uint32_t lo = rl.lo | (q & ((1u << w_log) - 1u)), hi = rl.hi | ((gslot + (q >> w_log)) << 5);
+            w.chunk[w.fill + rank] = (static_cast<uint64_t>(hi) << 32) | lo;
         }
         w.fill += n;
         who = __ballot(ok != 0u);
@@ -418,6 +457,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
     uint32_t it = first.item;
     ScanItem cur = items[it];
 
+    const uint32_t order_step = slice_bits == 8u ? 6u : 0u; // pruned scan: bits per slice in kFineOrders
     while (true) {
         uint32_t u = 0;
         if (lane == 0) u = atomicAdd(&next_unit, 1u);
@@ -435,26 +475,34 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
             // The planes the unit needs: 12 of the 16 positions (fine_word) -- the successor slice's four sit in plane quads
             // sq and 4 + sq of the tile and stay in memory.
             const uint32_t slice_of = cur.bucket >> (8u + slice_bits); // bucket << 8 | successor byte; slice = bucket >> slice width
-            const uint32_t q0 = fine_order(slice_of, 0u, slice_bits), q1 = fine_order(slice_of, 1u, slice_bits), q2 = fine_order(slice_of, 2u, slice_bits);
+            const uint32_t order = (kFineOrders >> (slice_of * order_step)) & 63u; // (narrow slices: step 0, all take slice 0's)
             const uint32_t dup_filter = slice_of != 0u ? ~0u : 0u; // (fine_dup: positions 0..3 are the previous slice's)
+            // Where the lanes read.  The window starts in lane group g0 of tile t0 and may reach into the next tile: all
+            // wave-uniform, so the planes come through three scalar bases (quad q and quad 4 + q lie 4096 bytes apart, an
+            // immediate offset either side of the middle) and ONE 32-bit offset per lane.  (A window at the very end of
+            // the stream would reach past it: those lanes read the last tile instead, and `keep` hides them.)
+            const uint32_t t0 = cur.group_abs >> 6, g0 = cur.group_abs & 63u;
+            const uint32_t next_tile = t0 + 1u < n_tiles ? 64u * 16u : 0u; // bit of a lane's 16 * (g0 + its lane group) that says "next tile"
+            const char *planes = reinterpret_cast<const char *>(scan_stream) + static_cast<uint64_t>(t0) * (4u * kTileCands) + 4096u;
+            const char *plane0 = planes + ((order & 3u) << 10), *plane1 = planes + (((order >> 2) & 3u) << 10), *plane2 = planes + ((order >> 4) << 10);
+            const uint32_t lo = cur.window & 0xFFFFu, hi = cur.window >> 16; // lo < 32: a window starts in its first lane group
+            compared += static_cast<unsigned long long>(cur.last_cands) * (g_end - g_begin);
             if (cur.shape != 32u) {
                 // ---- a SHORT unit: the last 64 * shape candidates of a successor-byte group, 32 / shape guides per pass ----
                 // Lane l takes candidates [l * shape, (l + 1) * shape) of the window, i.e. field l % per of lane group
                 // first + l / per: the same 16-byte loads, then one byte permute per plane spreads the field over the
-                // whole register.
-                const uint32_t shape = cur.shape, per = 32u / shape, w_log = shape == 16u ? 4u : 3u;
-                const uint32_t glane = cur.group_abs + lane / per;
-                uint32_t tile = glane >> 6;
-                const uint32_t grp = glane & 63u, sub = lane & (per - 1u);
-                if (tile >= n_tiles) tile = n_tiles - 1u;
-                compared += static_cast<unsigned long long>(cur.last_cands) * (g_end - g_begin);
-                const uint4 *__restrict__ src =
-                    reinterpret_cast<const uint4 *>(scan_stream + static_cast<uint64_t>(tile) * kTileCands) + grp;
-                const uint32_t sel = shape == 16u ? (sub ? 0x03020302u : 0x01000100u) : sub * 0x01010101u;
+                // whole register.  shape is 16 or 8: everything that depends on it is a shift or a select.
+                const bool wide = cur.shape == 16u;
+                const uint32_t shape = wide ? 16u : 8u, w_log = wide ? 4u : 3u, per_log = wide ? 1u : 2u, per = wide ? 2u : 4u;
+                const uint32_t at16 = (g0 + (lane >> per_log)) << 4, sub = lane & (per - 1u);
+                const uint32_t off = (at16 & 0x3F0u) + ((at16 & next_tile) << 3);
+                const uint32_t sel = (wide ? 0x01000100u : 0u) + sub * (wide ? 0x02020202u : 0x01010101u);
                 uint32_t c[24];
                 {
-                    const uint4 a0 = src[q0 * 64u], a1 = src[q1 * 64u], a2 = src[q2 * 64u];
-                    const uint4 b0 = src[(4u + q0) * 64u], b1 = src[(4u + q1) * 64u], b2 = src[(4u + q2) * 64u];
+                    const uint4 a0 = *reinterpret_cast<const uint4 *>(plane0 - 4096 + off), a1 = *reinterpret_cast<const uint4 *>(plane1 - 4096 + off);
+                    const uint4 a2 = *reinterpret_cast<const uint4 *>(plane2 - 4096 + off);
+                    const uint4 b0 = *reinterpret_cast<const uint4 *>(plane0 + off), b1 = *reinterpret_cast<const uint4 *>(plane1 + off);
+                    const uint4 b2 = *reinterpret_cast<const uint4 *>(plane2 + off);
                     const uint4 t6[6] = {a0, a1, a2, b0, b1, b2};
 #pragma unroll
                     for (int q = 0; q < 6; ++q) {
@@ -462,25 +510,24 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                         c[4 * q + 2] = __builtin_amdgcn_perm(0u, t6[q].z, sel); c[4 * q + 3] = __builtin_amdgcn_perm(0u, t6[q].w, sel);
                     }
                 }
-                // the lane's candidates that are the item's: window offsets [lo, hi), the same for every guide field
-                const int lo = static_cast<int>(cur.window & 0xFFFFu), hi = static_cast<int>(cur.window >> 16);
-                const int below = lo - static_cast<int>(lane * shape), upto = hi - static_cast<int>(lane * shape);
-                const uint32_t field = shape == 16u ? 0xFFFFu : 0xFFu;
-                const uint32_t mine = (below <= 0 ? field : below >= static_cast<int>(shape) ? 0u : (field << below) & field) &
-                                      (upto >= static_cast<int>(shape) ? field : upto <= 0 ? 0u : field >> (shape - upto));
-                const uint32_t keep = mine * (shape == 16u ? 0x00010001u : 0x01010101u);
-                const uint32_t off0 = grp * 32u + sub * shape;
+                // the lane's candidates that are the item's: window offsets [lo, hi), the same for every guide field: bits
+                // [from, to) of the field, both clamped to it
+                const int mine0 = static_cast<int>(lane << w_log), width = static_cast<int>(shape);
+                const int from = min(max(static_cast<int>(lo) - mine0, 0), width), to = min(max(static_cast<int>(hi) - mine0, 0), width);
+                const uint32_t keep = ((1u << to) - (1u << from)) * (wide ? 0x00010001u : 0x01010101u);
+                // (candidate q of the lane sits at window offset lane * shape + q: 32 * its lane group + shape * sub)
+                const RecLane rl = rec_lane_at(cur.group_abs, lane << w_log);
                 for (uint32_t gb = g_begin; gb < g_end; gb += 8u * per) { // 8 passes' masks at a time
                     __builtin_amdgcn_wave_barrier();
-                    short_unit_masks(gword_stream, gb, shape, lane, wave_masks);
+                    short_unit_masks(gword_stream, gb, wide, lane, wave_masks);
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
-                    const uint32_t passes = (g_end - gb + per - 1u) / per;
+                    const uint32_t passes = (g_end - gb + per - 1u) >> per_log;
                     for (uint32_t i = 0; i < (passes < 8u ? passes : 8u); ++i) {
                         PrevSlice prev;
                         const uint32_t ok = near_plane12_masks<THR>(c, wave_masks + i * 8u, thr, keep, prev);
                         if (__ballot(ok != 0u) != 0ull) {
-                            note_candidates(fine_dup(ok, prev, dup_filter), gb + i * per, w_log, tile, off0, lane, w, raw, raw_used, max_chunks, counters);
+                            note_candidates(fine_dup(ok, prev, dup_filter), gb + (i << per_log), w_log, rl, lane, w, raw, raw_used, max_chunks, counters);
                             own_chunk = true;
                         }
                     }
@@ -488,30 +535,25 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                 continue;
             }
             // ---- a full unit: 2048 consecutive candidates of the bucket from lane group cur.group_abs on; lane l takes the
-            // 32 of group (first + l).  A window may start on any lane group and then straddles two tiles -- the same
-            // 16-byte loads per lane, from two places.  (A window at the very end of the stream would reach past it:
-            // those lanes read the last tile instead, and `keep` hides them.)
-            const uint32_t glane = cur.group_abs + lane;
-            uint32_t tile = glane >> 6;
-            const uint32_t grp = glane & 63u;
-            if (tile >= n_tiles) tile = n_tiles - 1u;
-            compared += static_cast<unsigned long long>(cur.last_cands) * (g_end - g_begin);
-            const uint4 *__restrict__ src =
-                reinterpret_cast<const uint4 *>(scan_stream + static_cast<uint64_t>(tile) * kTileCands) + grp;
+            // 32 of group (first + l).
+            const uint32_t at16 = (g0 + lane) << 4;
+            const uint32_t off = (at16 & 0x3F0u) + ((at16 & next_tile) << 3);
             uint32_t c[24];
             {
-                const uint4 a0 = src[q0 * 64u], a1 = src[q1 * 64u], a2 = src[q2 * 64u];
-                const uint4 b0 = src[(4u + q0) * 64u], b1 = src[(4u + q1) * 64u], b2 = src[(4u + q2) * 64u];
+                const uint4 a0 = *reinterpret_cast<const uint4 *>(plane0 - 4096 + off), a1 = *reinterpret_cast<const uint4 *>(plane1 - 4096 + off);
+                const uint4 a2 = *reinterpret_cast<const uint4 *>(plane2 - 4096 + off);
+                const uint4 b0 = *reinterpret_cast<const uint4 *>(plane0 + off), b1 = *reinterpret_cast<const uint4 *>(plane1 + off);
+                const uint4 b2 = *reinterpret_cast<const uint4 *>(plane2 + off);
                 c[0] = a0.x; c[1] = a0.y; c[2] = a0.z; c[3] = a0.w; c[4] = a1.x; c[5] = a1.y; c[6] = a1.z; c[7] = a1.w;
                 c[8] = a2.x; c[9] = a2.y; c[10] = a2.z; c[11] = a2.w;
                 c[12] = b0.x; c[13] = b0.y; c[14] = b0.z; c[15] = b0.w; c[16] = b1.x; c[17] = b1.y; c[18] = b1.z; c[19] = b1.w;
                 c[20] = b2.x; c[21] = b2.y; c[22] = b2.z; c[23] = b2.w;
             }
-            // the lane's candidates that are the item's: offsets [lo, hi) of the unit
-            const int lo = static_cast<int>(cur.window & 0xFFFFu), hi = static_cast<int>(cur.window >> 16);
-            const int below = lo - static_cast<int>(lane * 32u), upto = hi - static_cast<int>(lane * 32u);
-            const uint32_t keep = (below <= 0 ? ~0u : below >= 32 ? 0u : ~0u << below) &
-                                  (upto >= 32 ? ~0u : upto <= 0 ? 0u : ~0u >> (32 - upto));
+            // the lane's candidates that are the item's: offsets [lo, hi) of the unit.  lo touches lane 0 alone; of hi the lane
+            // keeps its first clamp(hi - 32 * lane, 0, 32) candidates: the high word of 32 ones shifted up by that many.
+            const int to = min(max(static_cast<int>(hi) - static_cast<int>(lane << 5), 0), 32);
+            const uint32_t keep = static_cast<uint32_t>((0xFFFFFFFFull << to) >> 32) & (lane == 0u ? ~0u << lo : ~0u);
+            const RecLane rl = rec_lane_at(cur.group_abs, lane << 5);
             if (stamps) { // diagnostics: how long the planes take to arrive once they are requested
                 const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -530,7 +572,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                         PrevSlice prev;
                         const uint32_t ok = near_plane12<-1>(c, gg.w[uu], thr - cls, keep, prev);
                         if (__ballot(ok != 0u) != 0ull) {
-                            note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, tile, grp * 32u, lane, w, raw, raw_used, max_chunks, counters);
+                            note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                             own_chunk = true;
                         }
                     }
@@ -549,7 +591,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                             PrevSlice prev;
                             const uint32_t ok = near_plane12<(THR < 1 ? 0 : THR - 1)>(c, gg.w[uu], thr - 1u, keep, prev);
                             if (__ballot(ok != 0u) != 0ull) {
-                                note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, tile, grp * 32u, lane, w, raw, raw_used, max_chunks, counters);
+                                note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                                 own_chunk = true;
                             }
                         }
@@ -564,7 +606,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                     PrevSlice prev;
                     const uint32_t ok = near_plane12<THR>(c, gg.w[uu], thr, keep, prev);
                     if (__ballot(ok != 0u) != 0ull) {
-                        note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, tile, grp * 32u, lane, w, raw, raw_used, max_chunks, counters);
+                        note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                         own_chunk = true;
                     }
                 }
@@ -595,6 +637,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
         const int below = lo - static_cast<int>(lane * 32u), upto = hi - static_cast<int>(lane * 32u);
         const uint32_t keep = (below <= 0 ? ~0u : below >= 32 ? 0u : ~0u << below) &
                               (upto >= 32 ? ~0u : upto <= 0 ? 0u : ~0u >> (32 - upto));
+        const RecLane rl = rec_lane(tile, grp * 32u);
         if (stamps) { // diagnostics: how long the planes take to arrive once they are requested
             const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -609,7 +652,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                 if (g + uu >= g_end) break; // padding slots of the bucket's last group (scalar test, not taken: free)
                 const uint32_t ok = near_plane<THR>(c, gg.w[uu], thr, keep);
                 if (__ballot(ok != 0u) != 0ull) { // ~4 % of the (guide, tile) pairs on random data
-                    note_candidates(ok, g + uu, 5u, tile, grp * 32u, lane, w, raw, raw_used, max_chunks, counters);
+                    note_candidates(ok, g + uu, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                     own_chunk = true;
                 }
             }

@@ -148,13 +148,13 @@ __device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t *lds /*[256
 // A group's slots hold its class-1 guides first (from a multiple of 8 on), its class-0 guides behind them from
 // ScanItem::gmid on: full units run the two classes as two loops with their own compiled tests, short units take the
 // class bit as a thirteenth plane.
-__host__ __device__ __forceinline__ uint32_t fine_quad(uint32_t slice) { return slice < 4u ? slice : 0u; }
+__host__ __device__ __forceinline__ constexpr uint32_t fine_quad(uint32_t slice) { return slice < 4u ? slice : 0u; }
 // The order of the 12 positions (three quads of the scan word's four): the quad of the PREVIOUS slice (slice - 1) first --
 // its four mismatch planes tell, for nothing, whether the slice before the bucket's own matches the guide exactly too, and
 // a candidate for which it does is reported from that slice's bucket already (fine_dup) -- then the other two, ascending.
 // Slice 0 has no previous slice: its quads in ascending order.  (Quad q of slice s's scan word holds slice q < s ? q : q + 1.)
 // Narrow slices (scan_word_sorted_narrow): the successor unit is quad 0 for every slice, the previous slice opens quad 1: quads 1, 2, 3.
-__host__ __device__ __forceinline__ uint32_t fine_order(uint32_t slice, uint32_t j, uint32_t slice_width = 8u)
+__host__ __device__ __forceinline__ constexpr uint32_t fine_order(uint32_t slice, uint32_t j, uint32_t slice_width = 8u)
 {
     if (slice_width != 8u) return j + 1u;
     const uint32_t sq = fine_quad(slice);
