@@ -660,8 +660,8 @@ __device__ __forceinline__ void fine_scatter_guides(const ImageView &v, uint32_t
                                                     const uint32_t *__restrict__ gfill, const uint32_t *__restrict__ gword,
                                                     const uint32_t *__restrict__ gidx, const uint64_t *__restrict__ gsig,
                                                     const uint32_t *__restrict__ fcount, const uint32_t *__restrict__ fcount0,
-                                                    const FineSum *__restrict__ fbase, uint32_t *__restrict__ fword,
-                                                    FineMeta *__restrict__ fmeta, FineGuideLds<THREADS> &l)
+                                                    const FineSum *__restrict__ fbase, FineSlot *__restrict__ fword,
+                                                    FineGuideLds<THREADS> &l)
 {
     constexpr uint32_t ways = WAYS;
     const uint32_t w = threadIdx.x, slice = b >> v.slice_width;
@@ -687,19 +687,18 @@ __device__ __forceinline__ void fine_scatter_guides(const ImageView &v, uint32_t
         // fcount is zero where the group has no candidates -- and nowhere else among the groups a guide of this bucket
         // visits: k_fine_count counted these very guides there
         l.has_cands[w] = c ? 1u : 0u;
-        for (uint32_t k2 = c; k2 < slots; ++k2) { fmeta[slot_at + k2] = FineMeta{kNoGuide, 0u, 0ull}; fword[slot_at + k2] = kPadGuideWord; } // padding slots behind the group's guides
+        for (uint32_t k2 = c; k2 < slots; ++k2) fword[slot_at + k2] = FineSlot{kPadGuideWord, kPadSlotId}; // padding slots behind the group's guides
     }
     __syncthreads();
     while (i < n) {
         const uint32_t gj = succ_byte(sig, slice, v.slice_width);
-        const uint32_t word12 = fine_word(word, slice, v.slice_width);
+        const uint32_t word12 = fine_word(word, slice, v.slice_width), id = slot_id(slice, guide);
 #pragma unroll
         for (uint32_t way = 0; way < ways; ++way) {
             const uint32_t ww = fine_way(gj, way);
             if (!l.has_cands[ww]) continue; // no candidates there: the group has no slots
             const uint32_t slot = way ? l.slot_of[ww] + atomicAdd(&l.cursor[ww], 1u) : l.slot0_of[ww] + atomicAdd(&l.cursor0[ww], 1u);
-            fword[slot] = word12 | (fine_class(way) << 24);
-            fmeta[slot] = FineMeta{guide, (b << 8) | ww, sig};
+            fword[slot] = FineSlot{word12 | (fine_class(way) << 24), id}; // one 8-byte store per placement
         }
         i += THREADS;
         if (i < n) { guide = gidx[g0 + i]; word = gword[g0 + i]; sig = gsig[g0 + i]; }
@@ -712,7 +711,7 @@ __global__ __launch_bounds__(THREADS) void k_fine_scatter(ImageView v, const uin
                                                           const uint32_t *__restrict__ gidx, const uint64_t *__restrict__ gsig,
                                                           const uint32_t *__restrict__ fcount, const uint32_t *__restrict__ fcount0,
                                                           const FineSum *__restrict__ fbase, const PlanInfo *__restrict__ plan,
-                                                          uint32_t *__restrict__ fword, FineMeta *__restrict__ fmeta,
+                                                          FineSlot *__restrict__ fword,
                                                           ScanItem *__restrict__ fitems, uint32_t item_guides, uint32_t tail_shapes)
 {
     short_kernel_priority();
@@ -720,7 +719,7 @@ __global__ __launch_bounds__(THREADS) void k_fine_scatter(ImageView v, const uin
     __shared__ union { FineItemLds<THREADS> items; FineGuideLds<THREADS> guides; } lds;
     const uint32_t nb = v.n_buckets;
     if (blockIdx.x < nb) fine_scatter_items(v, blockIdx.x, fcount, fcount0, fbase, fitems, item_guides, tail_shapes, lds.items);
-    else fine_scatter_guides<WAYS, THREADS>(v, blockIdx.x - nb, gstart, gfill, gword, gidx, gsig, fcount, fcount0, fbase, fword, fmeta, lds.guides);
+    else fine_scatter_guides<WAYS, THREADS>(v, blockIdx.x - nb, gstart, gfill, gword, gidx, gsig, fcount, fcount0, fbase, fword, lds.guides);
 }
 
 // Cost ranges of the pruned scan (the bucket-level ones are resolved by k_guide_scatter's last workgroups).
@@ -832,12 +831,10 @@ __global__ __launch_bounds__(kSmallPairs) void k_bin_small(ImageView v, Workspac
         const uint32_t word12 = fine_word(image_word(sig, sl, v.slice_width, sorted_layout != 0u), sl, v.slice_width);
         const uint32_t ww = fine_way(gj, way);
         const uint32_t c1 = way ? 1u : 0u; // a group's class-1 guides come first, its class-0 guides from gmid on: here ONE guide
-        uint4 *fw = reinterpret_cast<uint4 *>(ws.fword + slot_at); // (slot_at is a multiple of 8: 32-byte aligned)
-        fw[0] = make_uint4(word12 | (fine_class(way) << 24), kPadGuideWord, kPadGuideWord, kPadGuideWord);
-        fw[1] = make_uint4(kPadGuideWord, kPadGuideWord, kPadGuideWord, kPadGuideWord);
-        ws.fmeta[slot_at] = FineMeta{g, (b << 8) | ww, sig};
+        uint4 *fw = reinterpret_cast<uint4 *>(ws.fword + slot_at); // (slot_at is a multiple of 8: 64-byte aligned)
+        fw[0] = make_uint4(word12 | (fine_class(way) << 24), slot_id(sl, g), kPadGuideWord, kPadSlotId);
 #pragma unroll
-        for (uint32_t k2 = 1; k2 < kGuideGroup; ++k2) ws.fmeta[slot_at + k2] = FineMeta{kNoGuide, 0u, 0ull};
+        for (uint32_t k2 = 1; k2 < kGuideGroup / 2u; ++k2) fw[k2] = make_uint4(kPadGuideWord, kPadSlotId, kPadGuideWord, kPadSlotId);
         const GroupUnits gu = group_units(s0, s1, tail_shapes);
         for (uint32_t u = 0; u < gu.units; ++u) { // as k_fine_scatter lays a group's units out, for one guide
             const bool full = u < gu.n_full;
@@ -953,10 +950,10 @@ void launch_bin_guides(const ImageView &v, const Workspace &ws, const Tuning &tn
             // (the workgroup size from the mean bucket: 391 guides at 100 k guides of five slices over 1280 buckets)
             if (static_cast<uint64_t>(n) * v.n_slices > 256ull * nb)
                 hipLaunchKernelGGL((k_fine_scatter<W, 512u>), dim3(2u * nb), dim3(512), 0, stream, v, ws.gstart, ws.gfill, ws.gword, ws.gidx, ws.gsig,
-                                   ws.fcount, ws.fcount0, ws.fsum, ws.plan, ws.fword, ws.fmeta, ws.fitems, tn.item_guides, tail_shapes);
+                                   ws.fcount, ws.fcount0, ws.fsum, ws.plan, ws.fword, ws.fitems, tn.item_guides, tail_shapes);
             else
                 hipLaunchKernelGGL((k_fine_scatter<W, 256u>), dim3(2u * nb), dim3(256), 0, stream, v, ws.gstart, ws.gfill, ws.gword, ws.gidx, ws.gsig,
-                                   ws.fcount, ws.fcount0, ws.fsum, ws.plan, ws.fword, ws.fmeta, ws.fitems, tn.item_guides, tail_shapes);
+                                   ws.fcount, ws.fcount0, ws.fsum, ws.plan, ws.fword, ws.fitems, tn.item_guides, tail_shapes);
         };
         if (ways == 1u) launch_fine(std::integral_constant<uint32_t, 1u>{});
         else if (ways == kFineWays) launch_fine(std::integral_constant<uint32_t, kFineWays>{});

@@ -360,7 +360,7 @@ constexpr uint32_t kFineWays = 13;      // successor bytes within one mismatch o
 constexpr uint32_t kFineWays2 = 67;     // ... within two (max_dist 5): + 6 pairs of positions x 9 base pairs
 constexpr uint32_t kFetchPairs = 8;     // time of fetching one 8 KiB tile, in (guide, tile) comparisons of the chip: measured 7
                                         // (50 M sites, neighbouring groups share tiles in L2) to 12 (300 M sites)
-constexpr uint32_t kPruneMaxGuides = 1u << 20; // guides per pruned launch: 65 slots per guide + padding must fit the 27-bit slot field
+constexpr uint32_t kPruneMaxGuides = 1u << 20; // guides per pruned launch: what the slot arrays are sized for (65 slots per guide + padding); a record's slot id has 22 bits for the guide
 constexpr uint32_t kPruneMaxGuides2 = 1u << 18; // ... 335 slots per guide (max_dist 5)
 // (ten 4-bit / twenty 2-bit slices: two / four times the buckets per guide, a half / a quarter of the guides)
 inline uint32_t prune_max_guides(uint32_t prune_mode, uint32_t n_slices)
@@ -369,11 +369,32 @@ inline uint32_t prune_max_guides(uint32_t prune_mode, uint32_t n_slices)
     return n_slices > 10 ? m >> 2 : n_slices > 5 ? m >> 1 : m;
 }
 
-// What k_verify needs to know about a guide slot of the pruned plan, in one 16-byte load.
-struct alignas(16) FineMeta {
-    uint32_t guide;  // index into the batch, kNoGuide in padding slots
-    uint32_t where;  // bucket << 8 | successor byte of the group the slot belongs to
-    uint64_t gsig;   // the guide's packed signature
+// Slot id of the pruned plan: slice << 22 | guide, the 27 bits a raw record carries above tile and offset.  The record
+// alone then tells k_verify whose it is: the guide's signature comes from the batch (beside the stream record, not behind a
+// table), and its bucket follows from slice and signature.  All ones = a padding slot.
+constexpr uint32_t kSlotIdBits = 27, kSlotGuideBits = 22;
+constexpr uint32_t kPadSlotId = (1u << kSlotIdBits) - 1u;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t slot_id(uint32_t slice, uint32_t guide) { return (slice << kSlotGuideBits) | guide; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void slot_id_unpack(uint32_t id, uint32_t &slice, uint32_t &guide)
+{
+    slice = id >> kSlotGuideBits;
+    guide = id & ((1u << kSlotGuideBits) - 1u);
+}
+static_assert(kPruneMaxGuides <= (1u << kSlotGuideBits), "a pruned launch's guides fit the id's guide field");
+static_assert(kMaxSlices <= (1u << (kSlotIdBits - kSlotGuideBits)), "an index's slices fit the id's slice field");
+static_assert(((kMaxSlices - 1u) << kSlotGuideBits | (kPruneMaxGuides - 1u)) < kPadSlotId, "no slot's id is the padding id");
+static_assert(kSlotIdBits + 26u + 11u == 64u, "raw record: slot id, tile, offset in tile");
+
+// One guide slot of the pruned plan: what the scan fetches (eight slots per scalar load) and k_fine_scatter stores whole.
+struct alignas(8) FineSlot {
+    uint32_t word;   // fine_word | class << 24; kPadGuideWord in padding slots
+    uint32_t id;     // slot_id(slice of the slot's bucket, index into the batch); kPadSlotId in padding slots
 };
 
 struct Workspace {
@@ -386,8 +407,7 @@ struct Workspace {
     uint64_t *gsig = nullptr;    // the guide's packed signature (valid where gidx is a guide): what the pruned plan's kernels read in bucket order
     ScanItem *items = nullptr;   // [max_items+1]
     // pruned scan: the guide arrays and the item list once more, grouped by (bucket, successor byte)
-    uint32_t *fword = nullptr;   // scan words of the guides, grouped
-    FineMeta *fmeta = nullptr;   // per slot: its guide (kNoGuide in padding), its group, the guide's signature
+    FineSlot *fword = nullptr;   // scan word and slot id of the guides, grouped
     ScanItem *fitems = nullptr;
     uint32_t *fcount = nullptr;  // [nb * 256] guides per (bucket, successor byte)
     uint32_t *fcount0 = nullptr; // [nb * 256] ... of them the ones whose own successor byte it is (class 0)

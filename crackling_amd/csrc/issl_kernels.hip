@@ -24,6 +24,8 @@
 // they share is in issl_kernels.hpp.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "issl_kernels.hpp"
 
 namespace issl {
@@ -146,28 +148,35 @@ __device__ __forceinline__ uint32_t near_plane_masks(const uint32_t (&c)[kPlanes
 
 // Masks of up to 8 passes of a short unit (guide slots g0 .. g0 + 8 * per - 1) into the wave's own 1 KiB of LDS: lane
 // (pass i, quarter q) makes the four words 4q .. 4q + 3 of pass i: bit p of each of the pass's `per` guide words, spread
-// over that guide's field of `shape` bits.  wide: shape 16, two guides per pass (their words arrive as one 8-byte load);
-// else shape 8, four guides (one 16-byte load: g0 is a multiple of 8).
-__device__ __forceinline__ void short_unit_masks(const uint32_t *__restrict__ gword_stream, uint32_t g0, bool wide,
+// over that guide's field of `shape` bits.  wide: shape 16, two guides per pass (their slots arrive as one 16-byte load);
+// else shape 8, four guides (two 16-byte loads: g0 is a multiple of 8).  A slot's word uses bits 0..25, so the quarter that
+// would make words 28 .. 31 stores the pass's slot ids there instead: the cold block reads the id of the guide a candidate
+// came near from the wave's own LDS (kPassIds).
+constexpr uint32_t kPassIds = 28; // word of a pass's 32 that holds the first of its ids
+typedef uint32_t SlotPair __attribute__((ext_vector_type(4))); // two slots, word and id each, as one load (a uint4's four members are loaded one by one where only one lane in eight wants the ids)
+__device__ __forceinline__ void short_unit_masks(const FineSlot *__restrict__ slots, uint32_t g0, bool wide,
                                                  uint32_t lane, uint4 *lds_masks)
 {
     const uint32_t i = lane >> 3, q = lane & 7u;
     uint32_t m[4];
     if (wide) {
-        const uint2 gw = *reinterpret_cast<const uint2 *>(gword_stream + g0 + 2u * i);
-        const uint32_t a = gw.x >> (4u * q), b = gw.y >> (4u * q);
+        const SlotPair gw = *reinterpret_cast<const SlotPair *>(slots + g0 + 2u * i);
+        const uint32_t a = gw.x >> (4u * q), b = gw.z >> (4u * q);
 #pragma unroll
         for (uint32_t r = 0; r < 4; ++r)
             m[r] = ((0u - ((a >> r) & 1u)) & 0xFFFFu) | ((0u - ((b >> r) & 1u)) << 16);
+        if (q == 7u) { m[0] = gw.y; m[1] = gw.w; }
     } else {
-        const uint4 gw = *reinterpret_cast<const uint4 *>(gword_stream + g0 + 4u * i);
-        const uint32_t t[4] = {gw.x >> (4u * q), gw.y >> (4u * q), gw.z >> (4u * q), gw.w >> (4u * q)};
+        const SlotPair *src = reinterpret_cast<const SlotPair *>(slots + g0 + 4u * i);
+        const SlotPair ga = src[0], gb = src[1];
+        const uint32_t t[4] = {ga.x >> (4u * q), ga.z >> (4u * q), gb.x >> (4u * q), gb.z >> (4u * q)};
 #pragma unroll
         for (uint32_t r = 0; r < 4; ++r) {
             // bit r of the four words into bits 0, 8, 16, 24; times 255 = each spread over its byte
             const uint32_t bits = ((t[0] >> r) & 1u) | (((t[1] >> r) & 1u) << 8) | (((t[2] >> r) & 1u) << 16) | (((t[3] >> r) & 1u) << 24);
             m[r] = bits * 255u;
         }
+        if (q == 7u) { m[0] = ga.y; m[1] = ga.w; m[2] = gb.y; m[3] = gb.w; }
     }
     lds_masks[i * 8u + q] = make_uint4(m[0], m[1], m[2], m[3]);
 }
@@ -336,6 +345,11 @@ __device__ __forceinline__ uint32_t fine_dup(uint32_t ok, const PrevSlice &prev,
 struct alignas(4) GuideGroupAny {
     uint32_t w[kGuideGroup];
 };
+// ... of the pruned plan: eight slots, word and id side by side, in ONE 16-dword scalar load -- the id of a guide a
+// candidate came near is in a scalar register when the cold block wants it.
+struct alignas(8) FineSlotGroup {
+    FineSlot s[kGuideGroup];
+};
 
 // fine_order as a table: the three plane quads of a slice's 12 positions in 2 bits each, the five 8-bit slices side by side
 // (narrow slices: the same three quads for every slice).
@@ -352,7 +366,9 @@ static_assert(fine_order_code(0u, 2u) == kFineOrderNarrow && fine_order_code(7u,
 // Cold block of the scan: the wave knows that SOME lane has a candidate within thr of a guide.  `ok` = this lane's
 // plane of such candidates; bit q of it is candidate q % (1 << w_log) of the lane -- which sits at offset off0 + that of
 // `tile` (the lane's own: a window of the pruned scan straddles two tiles) -- against the guide in slot gslot + (q >>
-// w_log) (full units: w_log = 5, one guide per pass).
+// w_log) (full units: w_log = 5, one guide per pass).  Pruned scan: a record carries the slot's id (slot_id), not its
+// number: `gslot` is the pass's id in a full unit, and in a short one the ids of the pass's guides are pass_ids[q >> w_log]
+// (the wave's LDS, short_unit_masks).
 // What of a record is the lane's alone is made once per unit (RecLane): the two words of raw_record(0, tile, off0); a round
 // ORs the candidate's number into the low word and the (wave-uniform) guide slot into the high one.  (The store keeps its
 // 64-bit lane address: a scalar base + 8 * rank as a 32-bit offset, with the lane's remaining candidates cleared outside the
@@ -373,7 +389,7 @@ __device__ __forceinline__ RecLane rec_lane_at(uint32_t group_abs, uint32_t cand
     return {static_cast<uint32_t>(at), static_cast<uint32_t>(at >> 32)};
 }
 
-__device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, uint32_t w_log, const RecLane &rl,
+__device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, const uint32_t *pass_ids, uint32_t w_log, const RecLane &rl,
                                                 uint32_t lane, RawWriter &w, uint64_t *raw, uint32_t *raw_used,
                                                 uint32_t max_chunks, Counters *counters)
 {
@@ -394,7 +410,8 @@ __device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, uin
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(who >> 32),
                                                             __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(who), 0u));
             // = raw_record(gslot + (q >> w_log), tile, off0 + (q & ((1u << w_log) - 1u))): off0 is a multiple of 1 << w_log
-            const uint32_t lo = rl.lo | (q & ((1u << w_log) - 1u)), hi = rl.hi | ((gslot + (q >> w_log)) << 5);
+            const uint32_t slot = pass_ids ? pass_ids[q >> w_log] : gslot + (q >> w_log);
+            const uint32_t lo = rl.lo | (q & ((1u << w_log) - 1u)), hi = rl.hi | (slot << 5);
             w.chunk[w.fill + rank] = (static_cast<uint64_t>(hi) << 32) | lo;
         }
         w.fill += n;
@@ -421,7 +438,7 @@ __device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, uin
 template <int THR, bool FINE>
 __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_stream, const ScanItem *__restrict__ items,
                                            const PlanInfo *__restrict__ plan, const RangeStart *__restrict__ range_start,
-                                           const uint32_t *__restrict__ gword_stream, uint4 *wave_masks,
+                                           const std::conditional_t<FINE, FineSlot, uint32_t> *__restrict__ gword_stream, uint4 *wave_masks,
                                            uint64_t *raw, uint32_t *raw_used, uint32_t max_chunks,
                                            Counters *counters, uint32_t thr, unsigned long long *stamps,
                                            uint64_t *__restrict__ scan_count, uint32_t *next_unit_p, uint32_t *waves_done_p,
@@ -527,7 +544,8 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                         PrevSlice prev;
                         const uint32_t ok = near_plane12_masks<THR>(c, wave_masks + i * 8u, thr, keep, prev);
                         if (__ballot(ok != 0u) != 0ull) {
-                            note_candidates(fine_dup(ok, prev, dup_filter), gb + (i << per_log), w_log, rl, lane, w, raw, raw_used, max_chunks, counters);
+                            note_candidates(fine_dup(ok, prev, dup_filter), 0u, reinterpret_cast<const uint32_t *>(wave_masks + i * 8u) + kPassIds, w_log, rl, lane, w, raw,
+                                            raw_used, max_chunks, counters);
                             own_chunk = true;
                         }
                     }
@@ -563,16 +581,16 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                 // The runtime-threshold build (max_dist 5, the scan_generic knob): one loop, every guide's budget from the class
                 // bits of its word -- thr minus the 0, 1 or 2 mismatches it has in the successor slice.
                 for (uint32_t g = g_begin; g < g_end; g += kGuideGroup) {
-                    const GuideGroup gg = *reinterpret_cast<const GuideGroup *>(gword_stream + g);
+                    const FineSlotGroup gg = *reinterpret_cast<const FineSlotGroup *>(gword_stream + g);
 #pragma unroll
                     for (uint32_t uu = 0; uu < kGuideGroup; ++uu) {
                         if (g + uu >= g_end) break;
-                        const uint32_t cls = (gg.w[uu] >> 24) & 3u;
+                        const uint32_t cls = (gg.s[uu].word >> 24) & 3u;
                         if (cls > thr) continue;
                         PrevSlice prev;
-                        const uint32_t ok = near_plane12<-1>(c, gg.w[uu], thr - cls, keep, prev);
+                        const uint32_t ok = near_plane12<-1>(c, gg.s[uu].word, thr - cls, keep, prev);
                         if (__ballot(ok != 0u) != 0ull) {
-                            note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
+                            note_candidates(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                             own_chunk = true;
                         }
                     }
@@ -584,14 +602,14 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
             if constexpr (THR >= 1) {
                 {
                     for (uint32_t g = g_begin; g < gmid; g += kGuideGroup) {
-                        const GuideGroupAny gg = *reinterpret_cast<const GuideGroupAny *>(gword_stream + g);
+                        const FineSlotGroup gg = *reinterpret_cast<const FineSlotGroup *>(gword_stream + g);
 #pragma unroll
                         for (uint32_t uu = 0; uu < kGuideGroup; ++uu) {
                             if (g + uu >= gmid) break;
                             PrevSlice prev;
-                            const uint32_t ok = near_plane12<(THR < 1 ? 0 : THR - 1)>(c, gg.w[uu], thr - 1u, keep, prev);
+                            const uint32_t ok = near_plane12<(THR < 1 ? 0 : THR - 1)>(c, gg.s[uu].word, thr - 1u, keep, prev);
                             if (__ballot(ok != 0u) != 0ull) {
-                                note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
+                                note_candidates(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                                 own_chunk = true;
                             }
                         }
@@ -599,14 +617,14 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                 }
             }
             for (uint32_t g = gmid; g < g_end; g += kGuideGroup) {
-                const GuideGroupAny gg = *reinterpret_cast<const GuideGroupAny *>(gword_stream + g);
+                const FineSlotGroup gg = *reinterpret_cast<const FineSlotGroup *>(gword_stream + g);
 #pragma unroll
                 for (uint32_t uu = 0; uu < kGuideGroup; ++uu) {
                     if (g + uu >= g_end) break;
                     PrevSlice prev;
-                    const uint32_t ok = near_plane12<THR>(c, gg.w[uu], thr, keep, prev);
+                    const uint32_t ok = near_plane12<THR>(c, gg.s[uu].word, thr, keep, prev);
                     if (__ballot(ok != 0u) != 0ull) {
-                        note_candidates(fine_dup(ok, prev, dup_filter), g + uu, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
+                        note_candidates(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                         own_chunk = true;
                     }
                 }
@@ -652,7 +670,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                 if (g + uu >= g_end) break; // padding slots of the bucket's last group (scalar test, not taken: free)
                 const uint32_t ok = near_plane<THR>(c, gg.w[uu], thr, keep);
                 if (__ballot(ok != 0u) != 0ull) { // ~4 % of the (guide, tile) pairs on random data
-                    note_candidates(ok, g + uu, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
+                    note_candidates(ok, g + uu, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                     own_chunk = true;
                 }
             }
@@ -686,7 +704,7 @@ __global__ __launch_bounds__(1024, 8) void k_scan(const uint32_t *__restrict__ s
                                                   const PlanInfo *__restrict__ plan,
                                                   const RangeStart *__restrict__ range_start,
                                                   const uint32_t *__restrict__ gword_full,
-                                                  const uint32_t *__restrict__ gword_fine, uint64_t *raw,
+                                                  const FineSlot *__restrict__ gword_fine, uint64_t *raw,
                                                   uint32_t *raw_used, uint32_t max_chunks, Counters *counters, uint32_t thr,
                                                   unsigned long long *stamps, uint64_t *__restrict__ scan_count,
                                                   unsigned long long *span, uint32_t n_tiles, uint32_t slice_bits)
@@ -720,7 +738,7 @@ static void launch_scan_thr(const ImageView &v, const Workspace &ws, const Tunin
 {
     // pruned scan: the items and guide words grouped by (bucket, successor byte); the plan says which list counts
     hipLaunchKernelGGL(k_scan<THR>, dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, v.scan, ws.items,
-                       prune_mode ? ws.fitems : ws.items, ws.plan, ws.range_start, ws.gword, prune_mode ? ws.fword : ws.gword,
+                       prune_mode ? ws.fitems : ws.items, ws.plan, ws.range_start, ws.gword, ws.fword,
                        ws.raw, ws.raw_used, static_cast<uint32_t>(ws.cap_chunks), ws.counters, thr, ws.stamps, ws.scan_count,
                        ws.scan_span + 2u * ws.span_slot, v.n_tiles, v.slice_width);
 }

@@ -41,7 +41,7 @@ int select_device(int device)
 static void free_workspace(Workspace &w)
 {
     void *ptrs[] = {w.ng, w.gfill, w.gstart, w.gword, w.gidx, w.gbucket, w.gsig, w.items, w.plan, w.range_start, w.counters, w.scan_count, w.scan_span, w.sticky, w.stamps, w.gcur_big, w.gcur_big2, w.terms, w.sorted, w.gcount,
-                    w.goff, w.blocksum, w.d_guides, w.d_mit, w.d_cfd, w.d_kept, w.d_hitrec, w.pay, w.rank, w.fword, w.fmeta,
+                    w.goff, w.blocksum, w.d_guides, w.d_mit, w.d_cfd, w.d_kept, w.d_hitrec, w.pay, w.rank, w.fword,
                     w.fitems, w.fcount, w.fcount0, w.fsum, w.slots};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -205,7 +205,6 @@ int ensure_workspace(issl_index *ix, size_t n, Lane &lane, uint32_t fine_ways)
         // (fine_items knob: start with a short list -- tests of the two ways out of a list that is too short)
         const size_t fitems = std::max<size_t>(tn.fine_items ? tn.fine_items : tiles_per_group * (groups + places / 64) + 2, w.cap_fitems);
         if ((rc = dev_alloc(w.fword, fslots + 64))) return rc; // (+ slack: short_unit_masks reads whole groups of 32 slots)
-        if ((rc = dev_alloc(w.fmeta, fslots))) return rc;
         if ((rc = dev_alloc(w.fitems, fitems + 1))) return rc;
         if ((rc = dev_alloc(w.fcount, nb * 256))) return rc;
         if ((rc = dev_alloc(w.fcount0, nb * 256))) return rc;

@@ -13,7 +13,7 @@ namespace issl {
 // ws.slot_hits hits of a guide are written to its slots; what lies beyond overwrites the record with its key for the
 // grouping pass; every other slot of the chunk becomes kDeadKey.
 __global__ __launch_bounds__(kChunkRecs, 8) void k_verify(ImageView v, Workspace ws, const uint64_t *__restrict__ guides,
-                                                       ScoreParams p)
+                                                       uint32_t n, ScoreParams p)
 {
     short_kernel_priority();
     const int max_dist = p.max_dist;
@@ -33,7 +33,8 @@ __global__ __launch_bounds__(kChunkRecs, 8) void k_verify(ImageView v, Workspace
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         // The passes behind the scan are chains of dependent loads at full occupancy: what they cost is the number of
         // links.  Header and record of the chunk are asked for together (a chunk always has its 128 slots), then the
-        // stream record and the guide slot's 16 bytes together, then -- nothing more before the exact test.
+        // stream record and the guide's signature (bucket-level plan: the guide slot's two words) together, then -- nothing
+        // more before the exact test.
         uint64_t *recs = ws.raw + static_cast<uint64_t>(chunk) * kChunkRecs;
         const uint32_t t = threadIdx.x + 1u;
         const uint64_t rec_any = recs[t < kChunkRecs ? t : 0u];
@@ -47,23 +48,32 @@ __global__ __launch_bounds__(kChunkRecs, 8) void k_verify(ImageView v, Workspace
         uint32_t hit_occ = 0;
         const uint32_t offset = static_cast<uint32_t>(rec) & (kTileCands - 1u);
         const uint32_t tile = static_cast<uint32_t>(rec >> 11) & 0x3FFFFFFu;
-        const uint32_t gslot = static_cast<uint32_t>(rec >> 37);
+        const uint32_t gslot = static_cast<uint32_t>(rec >> 37); // pruned scan: the slot's id, not its number
         // sorted layouts: what the stream holds at the record's place, asked for before anything else is known about it
         const bool by_id = v.srec || v.sid; // the scoring order is (slice, site id): ImageHeader
         StreamRec sr_early{};
         if (in_use && v.srec) sr_early = v.srec[static_cast<uint64_t>(tile) * kTileCands + offset];
         else if (in_use && v.sid) sr_early.id = v.sid[static_cast<uint64_t>(tile) * kTileCands + offset];
-        // the guide slot knows its guide and its bucket (pruned scan: and its successor-byte group, and the guide's
-        // signature): no search for the tile's
-        uint32_t guide = kNoGuide, where = 0;
+        // Whose record it is.  Pruned scan: the record says so itself (slot_id: guide and slice; the bucket follows from the
+        // slice and the guide's signature, which is asked for beside the stream record, not behind it).  Bucket-level plan:
+        // the guide slot knows its guide and its bucket -- no search for the tile's.
+        uint32_t guide = kNoGuide, bucket = 0, slice = 0;
         uint64_t gsig = 0;
         if (in_use) {
-            if (prune_mode) { const FineMeta m = ws.fmeta[gslot]; guide = m.guide; where = m.where; gsig = m.gsig; }
-            else { guide = ws.gidx[gslot]; where = ws.gbucket[gslot]; }
+            if (prune_mode) {
+                if (gslot != kPadSlotId) slot_id_unpack(gslot, slice, guide);
+                if (guide >= n || slice >= v.n_slices) guide = kNoGuide; // (a padding slot, or no slot of this batch at all)
+                else {
+                    gsig = guides[guide];
+                    bucket = (slice << v.slice_width) + (static_cast<uint32_t>(gsig >> (v.slice_width * slice)) & static_cast<uint32_t>(low));
+                }
+            } else {
+                guide = ws.gidx[gslot];
+                bucket = ws.gbucket[gslot];
+                slice = bucket >> v.slice_width;
+            }
         }
         if (guide != kNoGuide) {
-            const uint32_t bucket = prune_mode ? where >> 8 : where;
-            const uint32_t slice = bucket >> v.slice_width;
             // Is the candidate the item's?  The scan notes only candidates of the item's own window (`keep`: not the zero
             // padding behind a bucket, not the neighbouring group that shares the tile), so on the sorted layouts, which need
             // nothing else from the bucket tables, the question is not asked again.  The list-order layouts find their list
@@ -187,7 +197,7 @@ void launch_verify(const ImageView &v, const Workspace &ws, const uint64_t *d_gu
     if (p.max_dist < 0) return;
     // (the kernel strides over the chunks the scan used: a small batch's few thousand need no 16 384 workgroups to start and leave)
     const uint32_t grid = n < 256u ? std::max<uint32_t>(2048u, 64u * n) : kTailGrid;
-    hipLaunchKernelGGL(k_verify, dim3(std::min(grid, kTailGrid)), dim3(kChunkRecs), 0, static_cast<hipStream_t>(stream), v, ws, d_guides, p);
+    hipLaunchKernelGGL(k_verify, dim3(std::min(grid, kTailGrid)), dim3(kChunkRecs), 0, static_cast<hipStream_t>(stream), v, ws, d_guides, n, p);
 }
 
 } // namespace issl
