@@ -173,9 +173,38 @@ int issl_index_device_bytes(const issl_index *idx, size_t *out)
     return abi_call([&] { return planned_image_bytes(idx, out); });
 }
 
+// Read-only keys that describe lane 0's scoring workspace (0 before the first batch): what a caller -- a test of a
+// long-lived handle -- reads to see which state the handle has reached.  Resolved here, where the handle is known;
+// the option table (issl_options.cpp) knows nothing of workspaces.
+static bool workspace_option(const issl_index *idx, const char *key, long long *value)
+{
+    const Workspace &w = idx->lane.ws;
+    const bool used = w.cap_guides != 0;
+    const struct { const char *key; long long v; } keys[] = {
+        {"ws_cap_guides", static_cast<long long>(w.cap_guides)},
+        {"ws_slot_width", used ? static_cast<long long>(w.slot_width) : 0}, // (the member starts at kSlotHits)
+        {"ws_fine_ways", static_cast<long long>(w.fine_ways)},
+        {"ws_cap_chunks", static_cast<long long>(w.cap_chunks)},
+        {"ws_cap_fitems", static_cast<long long>(w.cap_fitems)},
+        {"ws_lean", idx->lane.lean ? 1 : 0},
+    };
+    for (const auto &k : keys)
+        if (std::strcmp(k.key, key) == 0) {
+            if (value) *value = k.v;
+            return true;
+        }
+    return false;
+}
+
 int issl_index_set_option(issl_index *idx, const char *key, const char *value)
 {
     if (!idx || !key || !value) { set_error("null argument"); return ISSL_E_ARG; }
+    if (workspace_option(idx, key, nullptr)) {
+        return abi_call([&]() -> int {
+            set_error(std::string("read-only option: ") + key);
+            return ISSL_E_ARG;
+        });
+    }
     if (idx->n_pending) { set_error("issl_index_set_option: batches are in flight, call issl_score_finish first"); return ISSL_E_STATE; }
     return abi_call([&]() -> int {
         Tuning t = idx->tuning;
@@ -200,7 +229,7 @@ int issl_index_set_option(issl_index *idx, const char *key, const char *value)
 int issl_index_get_option(const issl_index *idx, const char *key, long long *value)
 {
     if (!idx || !key || !value) { set_error("null argument"); return ISSL_E_ARG; }
-    if (idx->tuning.get(key, value) || image_option(idx->d_image ? &idx->hdr : nullptr, key, value)) return ISSL_OK;
+    if (idx->tuning.get(key, value) || image_option(idx->d_image ? &idx->hdr : nullptr, key, value) || workspace_option(idx, key, value)) return ISSL_OK;
     return abi_call([&]() -> int {
         set_error(std::string("unknown option: ") + key);
         return ISSL_E_ARG;

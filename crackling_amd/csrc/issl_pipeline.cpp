@@ -429,6 +429,11 @@ int finish_batches(issl_index *ix, hipStream_t stream)
         if (sticky[0]) HIP_TRY(hipMemset(lp->ws.sticky, 0, 16));
     }
     if (retry) {
+        // The caller enqueues the same batches again, and two workspaces need not get them the same way round (n_async runs on:
+        // an odd number of batches changes sides).  A workspace that saw only clean batches would be lean for the many-hit batch
+        // of the repeat while the other turns lean again over ITS clean ones -- "again" for ever.  No lane is lean for the repeat.
+        ix->lane.lean = false;
+        ix->lane2.lean = false;
         set_error("a batch has to be scored again: its raw record buffer was too small (it has been enlarged), or it was enqueued "
                   "without the many-hit part of the pipeline and met a guide that needs it");
         return ISSL_E_RETRY;

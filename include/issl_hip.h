@@ -289,7 +289,11 @@ int issl_index_attach_image_cold(int device, void *dev_buf, size_t bytes, void *
 int issl_index_set_option(issl_index *idx, const char *key, const char *value);
 /* Current value of an integer knob; also the read-only keys is_sorted, is_compact, cold_on_host, cold_sections (0, 1 =
  * slice lists, 3 = lists + site table in host memory), lists_absent, has_inline_sigs and dense_mit (layout of the uploaded image, -1
- * before an upload). */
+ * before an upload), and the read-only keys of the first lane's scoring workspace (0 before the first batch; set_option
+ * refuses them with ISSL_E_ARG): ws_cap_guides (guides its arrays hold), ws_slot_width (hit slots per guide: 512 or 2048),
+ * ws_fine_ways (placements per guide and bucket the pruned plan's arrays are sized for: 13 or 67), ws_cap_chunks (chunks of
+ * the raw-record buffer), ws_cap_fitems (items of the pruned plan's list), ws_lean (1: the next batch is enqueued without
+ * the grouping pass and the many-hit replays). */
 int issl_index_get_option(const issl_index *idx, const char *key, long long *value);
 
 /* ---- guides (A2, isslScoreOfftargets.cpp:63-71,82-89,275-305) ---------------------------- */

@@ -364,6 +364,34 @@ def test_every_documented_option_can_be_set_and_read_back(golden_uniform):
         ix.close()
 
 
+WORKSPACE_KEYS = ("ws_cap_guides", "ws_slot_width", "ws_fine_ways", "ws_cap_chunks", "ws_cap_fitems", "ws_lean")
+
+
+def test_workspace_keys_are_read_only_and_zero_before_the_first_batch(golden_uniform):
+    """The keys that describe the first lane's scoring workspace: a handle that has scored nothing -- here one without a device
+    -- answers 0 for each; issl_index_set_option refuses them with ISSL_E_ARG and leaves them as they were; the header and the
+    README list them; they are no rows of the option table (no environment variable sets them)."""
+    header = (ROOT / "include" / "issl_hip.h").read_text()
+    readme = (ROOT / "README.md").read_text()
+    assert not set(WORKSPACE_KEYS) & {k for k, _ in _option_table()}
+    ix = ca.IsslIndex.open(golden_uniform.issl)
+    try:
+        for key in WORKSPACE_KEYS:
+            assert key in header and "`%s`" % key in readme, key
+            assert ix.get_option(key) == 0, key
+            for value in (0, 1, 2048, "x", ""):
+                rc = _lib.lib.issl_index_set_option(ix._h, key.encode(), str(value).encode())
+                assert rc == -1, (key, value, rc)   # ISSL_E_ARG
+                assert b"read-only" in _lib.lib.issl_last_error()
+            assert ix.get_option(key) == 0, key
+        with pytest.raises(ca.IsslError):
+            ix.get_option("ws_nothing")
+    finally:
+        ix.close()
+    for key in ("small_bin", "fine_items", "expect_guides", "scan_events", "upload_threads"):   # settable keys the README had missed
+        assert "`%s`" % key in readme, key
+
+
 _ENV_CHILD = """
 import json, sys
 sys.path.insert(0, sys.argv[1])
