@@ -1,5 +1,6 @@
 # Build of the MI355X ISSL scorer: libissl_hip.so (C ABI, include/issl_hip.h; libissl_hip.map keeps every other symbol
-# out of its dynamic table), the three drop-in executables, isslReportOfftargets, isslLocateOfftargets, isslIndexFromFasta, cracklingGuides, cracklingBowtie and countHitTranscripts.  hipcc cross-compiles for gfx950 without a GPU present.
+# out of its dynamic table), the three drop-in executables, isslReportOfftargets, isslLocateOfftargets, isslIndexFromFasta,
+# cracklingGuides, cracklingBowtie and countHitTranscripts.  hipcc cross-compiles for gfx950 without a GPU present.
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC     = crackling_amd/csrc
@@ -31,36 +32,23 @@ $(LIB): $(OBJS) $(CSRC)/libissl_hip.map
 
 -include $(OBJS:.o=.d)
 
-# host-only executable: libissl_hip.so is loaded with dlopen when the process has to score by itself, not when a resident
-# server answers (cli_score.cpp)
-bin/isslScoreOfftargets: $(CSRC)/cli_score.cpp include/issl_hip.h $(LIB)
+# The host-only executables: libissl_hip.so is loaded with dlopen (cli_api.hpp: the search for the library, the symbols each
+# one needs, the ABI check) -- by isslScoreOfftargets only when the process has to score by itself, not when a resident
+# server answers (cli_score.cpp).  One recipe for the six, each behind its own source:
+#   isslScoreOfftargets   the drop-in scorer                 isslReportOfftargets  the off-target report (records or --profile)
+#   isslLocateOfftargets  where the off-targets lie          cracklingGuides       the candidate guides of FASTA inputs
+#   cracklingBowtie       the Bowtie step for a guide list   countHitTranscripts   transcript hit counts for Crackling's output
+DLOPEN_EXES = bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOfftargets bin/cracklingGuides bin/cracklingBowtie \
+              bin/countHitTranscripts
+bin/isslScoreOfftargets: $(CSRC)/cli_score.cpp $(CSRC)/issl_host.hpp
+bin/isslReportOfftargets: $(CSRC)/cli_report.cpp
+bin/isslLocateOfftargets: $(CSRC)/cli_locate.cpp
+bin/cracklingGuides: $(CSRC)/cli_guides.cpp
+bin/cracklingBowtie: $(CSRC)/cli_bowtie.cpp
+bin/countHitTranscripts: $(CSRC)/cli_transcripts.cpp
+$(DLOPEN_EXES): $(CSRC)/cli_api.hpp include/issl_hip.h $(LIB)
 	@mkdir -p bin
-	g++ $(CXXFLAGS) -o $@ $< -lpthread -ldl
-
-# the off-target report (records or --profile per guide): host-only as well, the library through dlopen
-bin/isslReportOfftargets: $(CSRC)/cli_report.cpp include/issl_hip.h $(LIB)
-	@mkdir -p bin
-	g++ $(CXXFLAGS) -o $@ $< -ldl
-
-# where the off-targets lie in the genome: host-only too, the library through dlopen
-bin/isslLocateOfftargets: $(CSRC)/cli_locate.cpp include/issl_hip.h $(LIB)
-	@mkdir -p bin
-	g++ $(CXXFLAGS) -o $@ $< -ldl
-
-# the candidate guides of FASTA inputs (Crackling's extraction step): host-only, the library through dlopen
-bin/cracklingGuides: $(CSRC)/cli_guides.cpp include/issl_hip.h $(LIB)
-	@mkdir -p bin
-	g++ $(CXXFLAGS) -o $@ $< -ldl
-
-# the Bowtie step for a list of guides (exact occurrences of their eight reads): host-only, the library through dlopen
-bin/cracklingBowtie: $(CSRC)/cli_bowtie.cpp include/issl_hip.h $(LIB)
-	@mkdir -p bin
-	g++ $(CXXFLAGS) -o $@ $< -ldl
-
-# transcript hit counts for Crackling's output file (countHitTranscripts.py): host-only, the library through dlopen
-bin/countHitTranscripts: $(CSRC)/cli_transcripts.cpp include/issl_hip.h $(LIB)
-	@mkdir -p bin
-	g++ $(CXXFLAGS) -o $@ $< -ldl
+	g++ $(CXXFLAGS) -o $@ $(filter %.cpp,$^) -lpthread -ldl
 
 bin/extractOfftargets: $(CSRC)/cli_extract.cpp $(CSRC)/cli_inputs.hpp $(LIB)
 	@mkdir -p bin

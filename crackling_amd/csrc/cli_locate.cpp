@@ -14,88 +14,30 @@
 //   ISSL_DEVICE=<n>       HIP device to use (default 0)
 //   ISSL_LIBRARY=<path>   libissl_hip.so to load (default: ../crackling_amd/ next to the executable, then the loader's path)
 // The executable does not link the library: it is loaded with dlopen, as isslReportOfftargets does.
-#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <unordered_set>
 #include <vector>
-#include <dlfcn.h>
 #include <unistd.h>
 
-#include "../../include/issl_hip.h"
-
-namespace {
-
+#define ISSL_CLI_NAME "isslLocateOfftargets"
 #define ISSL_CLI_API(X)                                                                                                   \
     X(issl_last_error) X(issl_abi_version) X(issl_read_query_file) X(issl_free) X(issl_encode_guides) X(issl_decode_guide)  \
     X(issl_genome_open_files) X(issl_genome_info) X(issl_genome_record) X(issl_genome_locate) X(issl_genome_close)
-struct Api {
-#define X(f) decltype(&::f) f = nullptr;
-    ISSL_CLI_API(X)
-#undef X
-};
-Api api;
+#include "cli_api.hpp"
 
-bool load_api()
-{
-    std::vector<std::string> tried;
-    void *h = nullptr;
-    auto attempt = [&](const std::string &path) {
-        if (h || path.empty()) return;
-        h = ::dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) tried.push_back(path + ": " + ::dlerror());
-    };
-    if (const char *e = std::getenv("ISSL_LIBRARY")) attempt(e);
-    char exe[PATH_MAX];
-    const ssize_t k = ::readlink("/proc/self/exe", exe, sizeof exe - 1);
-    if (k > 0) {
-        exe[k] = 0;
-        std::string dir(exe);
-        dir.erase(dir.find_last_of('/') == std::string::npos ? 0 : dir.find_last_of('/'));
-        attempt(dir + "/../crackling_amd/libissl_hip.so");
-        attempt(dir + "/libissl_hip.so");
-        attempt(dir + "/../lib/libissl_hip.so");
-    }
-    attempt("libissl_hip.so");
-    if (!h) {
-        std::fprintf(stderr, "isslLocateOfftargets: cannot load libissl_hip.so (set ISSL_LIBRARY):\n");
-        for (const auto &t : tried) std::fprintf(stderr, "  %s\n", t.c_str());
-        return false;
-    }
-#define X(f)                                                                                                              \
-    api.f = reinterpret_cast<decltype(api.f)>(::dlsym(h, #f));                                                            \
-    if (!api.f) { std::fprintf(stderr, "isslLocateOfftargets: libissl_hip.so lacks %s (another version of the library?)\n", #f); return false; }
-    ISSL_CLI_API(X)
-#undef X
-    if (api.issl_abi_version() != ISSL_ABI_VERSION) {
-        std::fprintf(stderr, "isslLocateOfftargets: libissl_hip.so has ABI %d, this executable was built for %d\n", api.issl_abi_version(), ISSL_ABI_VERSION);
-        return false;
-    }
-    return true;
-}
-
-int fail(const char *what)
-{
-    const char *e = api.issl_last_error ? api.issl_last_error() : nullptr;
-    std::fprintf(stderr, "%s\n", (e && e[0]) ? e : what);
-    return 1;
-}
+namespace {
 
 // The second field of every line of an isslReportOfftargets TSV, packed.  false: the file is no such TSV.
 bool read_report_sites(const char *path, std::vector<uint64_t> &sites)
 {
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) {
+    std::string text;
+    if (!read_text_file(path, text)) {
         std::fprintf(stderr, "cannot open '%s'\n", path);
         return false;
     }
-    std::string text;
-    char buf[1 << 16];
-    size_t got;
-    while ((got = std::fread(buf, 1, sizeof buf, fp)) > 0) text.append(buf, got);
-    std::fclose(fp);
     std::string packed; // the 20-mers one after the other
     size_t line = 0;
     for (size_t p = 0; p < text.size(); ++line) {
@@ -157,7 +99,8 @@ int main(int argc, char **argv)
         locs.resize(total);
         if (api.issl_genome_locate(g, distinct.data(), distinct.size(), offsets.data(), locs.data(), locs.size(), &total)) return fail("locate failed");
     }
-    std::string out;
+    StdoutText so;
+    std::string &out = so.text;
     char site[64], buf[64];
     bool ok = true;
     for (size_t k = 0; ok && k < distinct.size(); ++k) {
@@ -174,12 +117,9 @@ int main(int argc, char **argv)
             std::snprintf(buf, sizeof buf, "\t%llu\t%c\n", static_cast<unsigned long long>(locs[j].pos), locs[j].strand ? '-' : '+');
             out += buf;
         }
-        if (out.size() >= (size_t(1) << 20)) {
-            ok = std::fwrite(out.data(), 1, out.size(), stdout) == out.size();
-            out.clear();
-        }
+        ok = so.wrote();
     }
-    ok = ok && std::fwrite(out.data(), 1, out.size(), stdout) == out.size() && std::fflush(stdout) == 0;
+    ok = ok && so.finish();
     if (!ok) { std::fprintf(stderr, "short write on stdout\n"); return 1; }
     api.issl_genome_close(g);
     return 0;

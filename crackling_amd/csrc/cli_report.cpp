@@ -13,75 +13,18 @@
 //   ISSL_DEVICE=<n>       HIP device to use (default 0)
 //   ISSL_LIBRARY=<path>   libissl_hip.so to load (default: ../crackling_amd/ next to the executable, then the loader's path)
 // The executable does not link the library: it is loaded with dlopen, as isslScoreOfftargets does.
-#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
-#include <dlfcn.h>
 #include <unistd.h>
 
-#include "../../include/issl_hip.h"
-
-namespace {
-
+#define ISSL_CLI_NAME "isslReportOfftargets"
 #define ISSL_CLI_API(X)                                                                                                   \
     X(issl_last_error) X(issl_abi_version) X(issl_index_open) X(issl_index_header) X(issl_index_upload) X(issl_index_close) \
     X(issl_read_query_file) X(issl_free) X(issl_decode_guide) X(issl_offtarget_profile) X(issl_offtargets)
-struct Api {
-#define X(f) decltype(&::f) f = nullptr;
-    ISSL_CLI_API(X)
-#undef X
-};
-Api api;
-
-bool load_api()
-{
-    std::vector<std::string> tried;
-    void *h = nullptr;
-    auto attempt = [&](const std::string &path) {
-        if (h || path.empty()) return;
-        h = ::dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) tried.push_back(path + ": " + ::dlerror());
-    };
-    if (const char *e = std::getenv("ISSL_LIBRARY")) attempt(e);
-    char exe[PATH_MAX];
-    const ssize_t k = ::readlink("/proc/self/exe", exe, sizeof exe - 1);
-    if (k > 0) {
-        exe[k] = 0;
-        std::string dir(exe);
-        dir.erase(dir.find_last_of('/') == std::string::npos ? 0 : dir.find_last_of('/'));
-        attempt(dir + "/../crackling_amd/libissl_hip.so");
-        attempt(dir + "/libissl_hip.so");
-        attempt(dir + "/../lib/libissl_hip.so");
-    }
-    attempt("libissl_hip.so");
-    if (!h) {
-        std::fprintf(stderr, "isslReportOfftargets: cannot load libissl_hip.so (set ISSL_LIBRARY):\n");
-        for (const auto &t : tried) std::fprintf(stderr, "  %s\n", t.c_str());
-        return false;
-    }
-#define X(f)                                                                                                              \
-    api.f = reinterpret_cast<decltype(api.f)>(::dlsym(h, #f));                                                            \
-    if (!api.f) { std::fprintf(stderr, "isslReportOfftargets: libissl_hip.so lacks %s (another version of the library?)\n", #f); return false; }
-    ISSL_CLI_API(X)
-#undef X
-    if (api.issl_abi_version() != ISSL_ABI_VERSION) {
-        std::fprintf(stderr, "isslReportOfftargets: libissl_hip.so has ABI %d, this executable was built for %d\n", api.issl_abi_version(), ISSL_ABI_VERSION);
-        return false;
-    }
-    return true;
-}
-
-int fail(const char *what)
-{
-    const char *e = api.issl_last_error ? api.issl_last_error() : nullptr;
-    std::fprintf(stderr, "%s\n", (e && e[0]) ? e : what);
-    return 1;
-}
-
-} // namespace
+#include "cli_api.hpp"
 
 int main(int argc, char **argv)
 {
@@ -115,14 +58,9 @@ int main(int argc, char **argv)
     std::vector<char> seq(n * (hdr.seq_len + 1));
     for (size_t i = 0; i < n; ++i)
         if (api.issl_decode_guide(guides[i], hdr.seq_len, seq.data() + i * (hdr.seq_len + 1))) return fail("cannot decode guide");
-    std::string out;
+    StdoutText so;
+    std::string &out = so.text;
     char buf[128];
-    auto flush = [&](bool all) {
-        if (out.size() < (size_t(1) << 20) && !all) return true;
-        const bool ok = std::fwrite(out.data(), 1, out.size(), stdout) == out.size();
-        out.clear();
-        return ok;
-    };
     bool ok = true;
     if (profile) {
         std::vector<issl_profile> prof(n);
@@ -132,7 +70,7 @@ int main(int argc, char **argv)
             for (long d = 0; d <= max_dist; ++d) { std::snprintf(buf, sizeof buf, "\t%u", prof[i].sites[d]); out += buf; }
             for (long d = 0; d <= max_dist; ++d) { std::snprintf(buf, sizeof buf, "\t%llu", static_cast<unsigned long long>(prof[i].occurrences[d])); out += buf; }
             out += '\n';
-            ok = flush(false);
+            ok = so.wrote();
         }
     } else {
         // the query in runs of guides, so that the records of one run are in memory at a time
@@ -157,11 +95,11 @@ int main(int argc, char **argv)
                 out += seq.data() + (at + r.guide) * (hdr.seq_len + 1);
                 std::snprintf(buf, sizeof buf, "\t%s\t%u\t%u\t%.17g\t%.17g\n", site, unsigned(r.dist), r.occ, r.mit, r.cfd);
                 out += buf;
-                ok = flush(false);
+                ok = so.wrote();
             }
         }
     }
-    ok = ok && flush(true) && std::fflush(stdout) == 0;
+    ok = ok && so.finish();
     if (!ok) { std::fprintf(stderr, "short write on stdout\n"); return 1; }
     api.issl_free(guides);
     api.issl_index_close(idx);

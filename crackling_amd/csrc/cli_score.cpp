@@ -30,7 +30,6 @@
 // server answers -- a page of 10 000 guides is scored in less time than the runtime takes to load.
 #include <atomic>
 #include <cerrno>
-#include <chrono>
 #include <climits>
 #include <csignal>
 #include <cstdio>
@@ -41,83 +40,36 @@
 #include <string>
 #include <algorithm>
 #include <thread>
-#include <dlfcn.h>
 #include <sys/socket.h>
 #include <sys/stat.h>
 #include <sys/un.h>
 #include <unistd.h>
 #include <vector>
 
-#include "../../include/issl_hip.h"
-
-namespace {
-
-double now_ms()
-{
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
-// ---- the library, loaded on demand ----------------------------------------------------------------------------------
+#define ISSL_CLI_NAME "isslScoreOfftargets"
 #define ISSL_CLI_API(X)                                                                                                   \
     X(issl_last_error) X(issl_abi_version) X(issl_index_open) X(issl_index_set_option) X(issl_index_header)                \
     X(issl_index_upload) X(issl_index_device_bytes) X(issl_index_close) X(issl_device_memory) X(issl_read_query_file)     \
     X(issl_free) X(issl_method_from_string) X(issl_score) X(issl_last_stats) X(issl_decode_guide) X(issl_verdicts)        \
     X(issl_format_scores) X(issl_free_spans) X(issl_node_create) X(issl_node_get_info) X(issl_node_score) X(issl_node_close)
-struct Api {
-#define X(f) decltype(&::f) f = nullptr;
-    ISSL_CLI_API(X)
-#undef X
-    double load_ms = 0;
-};
-Api api;
+#include "cli_api.hpp"
+#include "issl_host.hpp"
+
+namespace {
+
+using issl::now_ms;
+
+// ---- the library, loaded on demand ----------------------------------------------------------------------------------
+double library_ms = 0; // what loading it took, for ISSL_TIMING
 
 // Loads libissl_hip.so once; false + message on stderr when it cannot be had (the caller exits 1).
-bool load_api()
+bool load_library()
 {
     if (api.issl_score) return true;
     const double t0 = now_ms();
-    std::vector<std::string> tried;
-    void *h = nullptr;
-    auto attempt = [&](const std::string &path) {
-        if (h || path.empty()) return;
-        h = ::dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) tried.push_back(path + ": " + ::dlerror());
-    };
-    if (const char *e = std::getenv("ISSL_LIBRARY")) attempt(e);
-    char exe[PATH_MAX];
-    const ssize_t k = ::readlink("/proc/self/exe", exe, sizeof exe - 1);
-    if (k > 0) {
-        exe[k] = 0;
-        std::string dir(exe);
-        dir.erase(dir.find_last_of('/') == std::string::npos ? 0 : dir.find_last_of('/'));
-        attempt(dir + "/../crackling_amd/libissl_hip.so");
-        attempt(dir + "/libissl_hip.so");
-        attempt(dir + "/../lib/libissl_hip.so");
-    }
-    attempt("libissl_hip.so");
-    if (!h) {
-        std::fprintf(stderr, "isslScoreOfftargets: cannot load libissl_hip.so (set ISSL_LIBRARY):\n");
-        for (const auto &t : tried) std::fprintf(stderr, "  %s\n", t.c_str());
-        return false;
-    }
-#define X(f)                                                                                                              \
-    api.f = reinterpret_cast<decltype(api.f)>(::dlsym(h, #f));                                                            \
-    if (!api.f) { std::fprintf(stderr, "isslScoreOfftargets: libissl_hip.so lacks %s (another version of the library?)\n", #f); return false; }
-    ISSL_CLI_API(X)
-#undef X
-    if (api.issl_abi_version() != ISSL_ABI_VERSION) {
-        std::fprintf(stderr, "isslScoreOfftargets: libissl_hip.so has ABI %d, this executable was built for %d\n", api.issl_abi_version(), ISSL_ABI_VERSION);
-        return false;
-    }
-    api.load_ms = now_ms() - t0;
+    if (!load_api()) return false;
+    library_ms = now_ms() - t0;
     return true;
-}
-
-std::string last_error(const char *fallback)
-{
-    const char *e = api.issl_last_error ? api.issl_last_error() : nullptr;
-    return (e && e[0]) ? e : fallback;
 }
 
 struct DeviceChoice {
@@ -443,7 +395,7 @@ int unix_socket(const char *path, sockaddr_un &addr)
 
 int serve(const char *sock_path)
 {
-    if (!load_api()) return 1;
+    if (!load_library()) return 1;
     sockaddr_un addr;
     const int lfd = unix_socket(sock_path, addr);
     if (lfd < 0) { std::fprintf(stderr, "cannot create socket %s\n", sock_path); return 1; }
@@ -765,7 +717,7 @@ int main(int argc, char **argv)
         const int rc = try_server(sock, argv, timing);
         if (rc >= 0) return rc;
     }
-    if (!load_api()) return 1;
+    if (!load_library()) return 1;
     Request q;
     q.issl = argv[1];
     q.query = argv[2];
@@ -822,7 +774,7 @@ int main(int argc, char **argv)
             return 1;
         }
     stg.write_ms = now_ms() - t0;
-    if (timing) std::fprintf(stderr, "%s\n", timing_json(r, stg, stats, false, api.load_ms, runtime_ms, now_ms() - t_main).c_str());
+    if (timing) std::fprintf(stderr, "%s\n", timing_json(r, stg, stats, false, library_ms, runtime_ms, now_ms() - t_main).c_str());
     // Everything is written; what is left is returning 45 GB of HBM and tearing the runtime down, which the driver does
     // for a process that ends anyway: leave at once (ISSL_TIDY_EXIT=1: release everything first, for leak checkers).
     if (std::getenv("ISSL_TIDY_EXIT")) {

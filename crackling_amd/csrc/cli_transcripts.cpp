@@ -22,90 +22,27 @@
 //   ISSL_DEVICE=<n>       HIP device to use (default 0)
 //   ISSL_LIBRARY=<path>   libissl_hip.so to load (default: ../crackling_amd/ next to the executable, then the loader's path)
 // The executable does not link the library: it is loaded with dlopen, as cracklingBowtie does.
-#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <unordered_map>
 #include <vector>
-#include <dlfcn.h>
 #include <unistd.h>
 
-#include "../../include/issl_hip.h"
-
-namespace {
-
+#define ISSL_CLI_NAME "countHitTranscripts"
 #define ISSL_CLI_API(X)                                                                                                   \
     X(issl_last_error) X(issl_abi_version) X(issl_annotation_open_file) X(issl_annotation_lookup) X(issl_annotation_hits) \
     X(issl_annotation_close)
-struct Api {
-#define X(f) decltype(&::f) f = nullptr;
-    ISSL_CLI_API(X)
-#undef X
-};
-Api api;
+#include "cli_api.hpp"
 
-bool load_api()
-{
-    std::vector<std::string> tried;
-    void *h = nullptr;
-    auto attempt = [&](const std::string &path) {
-        if (h || path.empty()) return;
-        h = ::dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) tried.push_back(path + ": " + ::dlerror());
-    };
-    if (const char *e = std::getenv("ISSL_LIBRARY")) attempt(e);
-    char exe[PATH_MAX];
-    const ssize_t k = ::readlink("/proc/self/exe", exe, sizeof exe - 1);
-    if (k > 0) {
-        exe[k] = 0;
-        std::string dir(exe);
-        dir.erase(dir.find_last_of('/') == std::string::npos ? 0 : dir.find_last_of('/'));
-        attempt(dir + "/../crackling_amd/libissl_hip.so");
-        attempt(dir + "/libissl_hip.so");
-        attempt(dir + "/../lib/libissl_hip.so");
-    }
-    attempt("libissl_hip.so");
-    if (!h) {
-        std::fprintf(stderr, "countHitTranscripts: cannot load libissl_hip.so (set ISSL_LIBRARY):\n");
-        for (const auto &t : tried) std::fprintf(stderr, "  %s\n", t.c_str());
-        return false;
-    }
-#define X(f)                                                                                                              \
-    api.f = reinterpret_cast<decltype(api.f)>(::dlsym(h, #f));                                                            \
-    if (!api.f) { std::fprintf(stderr, "countHitTranscripts: libissl_hip.so lacks %s (another version of the library?)\n", #f); return false; }
-    ISSL_CLI_API(X)
-#undef X
-    if (api.issl_abi_version() != ISSL_ABI_VERSION) {
-        std::fprintf(stderr, "countHitTranscripts: libissl_hip.so has ABI %d, this executable was built for %d\n", api.issl_abi_version(), ISSL_ABI_VERSION);
-        return false;
-    }
-    return true;
-}
+namespace {
 
-int fail(const std::string &what)
+// This executable's messages carry its name, the library's included.
+int fail_with(const std::string &message)
 {
-    std::fprintf(stderr, "countHitTranscripts: %s\n", what.c_str());
+    std::fprintf(stderr, "countHitTranscripts: %s\n", message.c_str());
     return 1;
-}
-
-int fail_api(const char *what)
-{
-    const char *e = api.issl_last_error ? api.issl_last_error() : nullptr;
-    return fail((e && e[0]) ? e : what);
-}
-
-bool read_file(const char *path, std::string &text)
-{
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return false;
-    char buf[1 << 16];
-    size_t k;
-    while ((k = std::fread(buf, 1, sizeof buf, fp)) > 0) text.append(buf, k);
-    const bool ok = !std::ferror(fp);
-    std::fclose(fp);
-    return ok;
 }
 
 // "\r\n" and a lone "\r" -> "\n": what Python's text mode hands the csv module.
@@ -264,9 +201,9 @@ int main(int argc, char **argv)
     // the annotation first, as the reference does: parsed on the host, then resolved on the device
     const char *dev = std::getenv("ISSL_DEVICE");
     issl_annotation *a = nullptr;
-    if (api.issl_annotation_open_file(annotation, dev ? std::atoi(dev) : 0, &a)) return fail_api("cannot open annotation");
+    if (api.issl_annotation_open_file(annotation, dev ? std::atoi(dev) : 0, &a)) return fail_with(last_error("cannot open annotation"));
     std::string raw;
-    if (!read_file(crackling, raw)) return fail(std::string("cannot read '") + crackling + "'");
+    if (!read_text_file(crackling, raw)) return fail_with(std::string("cannot read '") + crackling + "'");
     std::vector<Row> rows = read_csv(universal_newlines(raw));
     std::vector<uint32_t> seq;
     std::vector<int64_t> start;
@@ -277,23 +214,23 @@ int main(int argc, char **argv)
         for (int c = 0; c < 4; ++c) {
             col[c] = 0;
             while (col[c] < rows[0].size() && rows[0][col[c]] != names[c]) ++col[c];
-            if (col[c] == rows[0].size()) return fail(std::string("the header of '") + crackling + "' has no column " + names[c]);
+            if (col[c] == rows[0].size()) return fail_with(std::string("the header of '") + crackling + "' has no column " + names[c]);
         }
         rows[0].push_back("hits");
         std::unordered_map<std::string, uint32_t> known;
         for (size_t r = 1; r < rows.size(); ++r) {
             const Row &row = rows[r];
             const std::string where = "row " + std::to_string(r + 1) + " of '" + crackling + "'";
-            if (row.size() <= col[1]) return fail(where + " has no bowtieChr");
+            if (row.size() <= col[1]) return fail_with(where + " has no bowtieChr");
             if (row[col[1]] == "?") continue;
             long long s = 0, e = 0;
-            if (row.size() <= col[0] || row.size() <= col[2] || row.size() <= col[3]) return fail(where + " is too short");
-            if (!to_int64(row[col[2]], s)) return fail(where + ": bowtieStart '" + row[col[2]] + "' is not an integer");
-            if (!to_int64(row[col[3]], e)) return fail(where + ": bowtieEnd '" + row[col[3]] + "' is not an integer");
+            if (row.size() <= col[0] || row.size() <= col[2] || row.size() <= col[3]) return fail_with(where + " is too short");
+            if (!to_int64(row[col[2]], s)) return fail_with(where + ": bowtieStart '" + row[col[2]] + "' is not an integer");
+            if (!to_int64(row[col[3]], e)) return fail_with(where + ": bowtieEnd '" + row[col[3]] + "' is not an integer");
             auto it = known.find(row[col[1]]);
             if (it == known.end()) {
                 uint32_t k = 0;
-                if (api.issl_annotation_lookup(a, row[col[1]].data(), row[col[1]].size(), &k)) return fail_api("lookup failed");
+                if (api.issl_annotation_lookup(a, row[col[1]].data(), row[col[1]].size(), &k)) return fail_with(last_error("lookup failed"));
                 it = known.emplace(row[col[1]], k).first;
             }
             seq.push_back(it->second);
@@ -302,7 +239,7 @@ int main(int argc, char **argv)
         }
     }
     std::vector<issl_transcript_hits> hits(asked.size());
-    if (api.issl_annotation_hits(a, seq.data(), start.data(), asked.size(), hits.data())) return fail_api("hits failed");
+    if (api.issl_annotation_hits(a, seq.data(), start.data(), asked.size(), hits.data())) return fail_with(last_error("hits failed"));
     for (size_t r = 1; r < rows.size(); ++r) rows[r].push_back("?/?");
     for (size_t k = 0; k < asked.size(); ++k)
         if (hits[k].status == 0) rows[asked[k]].back() = std::to_string(hits[k].hit) + "/" + std::to_string(hits[k].total);
@@ -310,8 +247,8 @@ int main(int argc, char **argv)
     std::string out;
     for (const Row &row : rows) write_row(row, out);
     FILE *fp = std::fopen(output, "wb");
-    if (!fp) return fail(std::string("cannot write '") + output + "'");
+    if (!fp) return fail_with(std::string("cannot write '") + output + "'");
     const bool ok = std::fwrite(out.data(), 1, out.size(), fp) == out.size();
-    if (std::fclose(fp) != 0 || !ok) return fail(std::string("short write on '") + output + "'");
+    if (std::fclose(fp) != 0 || !ok) return fail_with(std::string("short write on '") + output + "'");
     return 0;
 }

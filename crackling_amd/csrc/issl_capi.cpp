@@ -16,7 +16,7 @@ namespace issl {
 int build_from_device_sites(const uint64_t *d_sigs, const uint32_t *d_occ, size_t n_sites, size_t n_lines, size_t seq_len,
                             size_t slice_width, int device, const char *options, issl_index **out)
 {
-    int rc = select_device(device);
+    int rc = select_device(device, "the ISSL scorer");
     if (rc) return rc;
     const uint32_t n_slices = static_cast<uint32_t>((seq_len * 2) / slice_width);
     std::vector<uint64_t> sizes(size_t(n_slices) << slice_width);
@@ -37,33 +37,33 @@ int issl_abi_version(void) { return ISSL_ABI_VERSION; }
 
 int issl_index_open(const char *path, issl_index **out)
 {
-    if (!path || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!path || !out) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] { return new_index([&](HostIndex &h) { return h.open_file(path); }, out); });
 }
 
 int issl_index_from_memory(const void *image, size_t len, issl_index **out)
 {
-    if (!image || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!image || !out) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] { return new_index([&](HostIndex &h) { return h.from_memory(image, len); }, out); });
 }
 
 int issl_index_build_from_text(const char *text, size_t n_lines, size_t seq_len, size_t slice_width,
                                issl_index **out)
 {
-    if (!text || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!text || !out) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] { return new_index([&](HostIndex &h) { return h.build_from_text(text, n_lines, seq_len, slice_width); }, out); });
 }
 
 int issl_index_build_from_sites(const uint64_t *sigs, const uint32_t *occ, size_t n_sites, size_t n_lines,
                                 size_t seq_len, size_t slice_width, issl_index **out)
 {
-    if (!sigs || !occ || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!sigs || !occ || !out) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] { return new_index([&](HostIndex &h) { return h.build_from_sites(sigs, occ, n_sites, n_lines, seq_len, slice_width); }, out); });
 }
 
 int issl_index_write(const issl_index *idx, const char *path)
 {
-    if (!idx || !path) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !path) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&]() -> int {
         if (!idx->host) { set_error("index was attached from a device image and has no host arrays"); return ISSL_E_STATE; }
         if (idx->host->has_arrays()) return idx->host->write_file(path);
@@ -139,7 +139,7 @@ int issl_index_write(const issl_index *idx, const char *path)
 
 int issl_index_header(const issl_index *idx, issl_header *out)
 {
-    if (!idx || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !out) return issl::fail(ISSL_E_ARG, "null argument");
     out->n_sites = idx->geo.n_sites;
     out->seq_len = idx->geo.seq_len;
     out->n_lines = idx->geo.n_lines;
@@ -151,7 +151,7 @@ int issl_index_header(const issl_index *idx, issl_header *out)
 
 int issl_index_bucket_sizes(const issl_index *idx, uint64_t *out, size_t n)
 {
-    if (!idx || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !out) return issl::fail(ISSL_E_ARG, "null argument");
     if (n < idx->bucket_sizes.size()) { set_error("bucket size buffer too small"); return ISSL_E_ARG; }
     std::copy(idx->bucket_sizes.begin(), idx->bucket_sizes.end(), out);
     return ISSL_OK;
@@ -167,7 +167,7 @@ int issl_index_close(issl_index *idx)
 
 int issl_index_device_bytes(const issl_index *idx, size_t *out)
 {
-    if (!idx || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !out) return issl::fail(ISSL_E_ARG, "null argument");
     if (idx->d_image) { *out = idx->hdr.total_bytes; return ISSL_OK; }
     if (!idx->host) { set_error("index has neither host arrays nor a device image"); return ISSL_E_STATE; }
     return abi_call([&] { return planned_image_bytes(idx, out); });
@@ -198,7 +198,7 @@ static bool workspace_option(const issl_index *idx, const char *key, long long *
 
 int issl_index_set_option(issl_index *idx, const char *key, const char *value)
 {
-    if (!idx || !key || !value) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !key || !value) return issl::fail(ISSL_E_ARG, "null argument");
     if (workspace_option(idx, key, nullptr)) {
         return abi_call([&]() -> int {
             set_error(std::string("read-only option: ") + key);
@@ -228,7 +228,7 @@ int issl_index_set_option(issl_index *idx, const char *key, const char *value)
 
 int issl_index_get_option(const issl_index *idx, const char *key, long long *value)
 {
-    if (!idx || !key || !value) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !key || !value) return issl::fail(ISSL_E_ARG, "null argument");
     if (idx->tuning.get(key, value) || image_option(idx->d_image ? &idx->hdr : nullptr, key, value) || workspace_option(idx, key, value)) return ISSL_OK;
     return abi_call([&]() -> int {
         set_error(std::string("unknown option: ") + key);
@@ -239,7 +239,7 @@ int issl_index_get_option(const issl_index *idx, const char *key, long long *val
 int issl_index_build_on_device_opt(const uint64_t *sigs, const uint32_t *occ, size_t n_sites, size_t n_lines,
                                    size_t seq_len, size_t slice_width, int device, const char *options, issl_index **out)
 {
-    if (!sigs || !occ || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!sigs || !occ || !out) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&]() -> int {
         std::unique_ptr<HostIndex> h(new HostIndex());
         int rc = h->init_without_arrays(sigs, n_sites, n_lines, seq_len, slice_width);
@@ -252,7 +252,7 @@ int issl_index_build_on_device_opt(const uint64_t *sigs, const uint32_t *occ, si
 int issl_index_build_from_device_sites(const uint64_t *d_sigs, const uint32_t *d_occ, size_t n_sites, size_t n_lines,
                                        size_t seq_len, size_t slice_width, int device, const char *options, issl_index **out)
 {
-    if (!d_sigs || !d_occ || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!d_sigs || !d_occ || !out) return issl::fail(ISSL_E_ARG, "null argument");
     if (seq_len == 0 || seq_len > 32 || slice_width < 2 || slice_width > 8 || (seq_len * 2) / slice_width == 0 ||
         (seq_len * 2) / slice_width > kMaxSlices) {
         set_error("bad sequence length or slice width");
@@ -269,8 +269,8 @@ int issl_index_build_on_device(const uint64_t *sigs, const uint32_t *occ, size_t
 
 int issl_device_memory(int device, size_t *free_bytes, size_t *total_bytes)
 {
-    if (!free_bytes || !total_bytes) { set_error("null argument"); return ISSL_E_ARG; }
-    int rc = select_device(device);
+    if (!free_bytes || !total_bytes) return issl::fail(ISSL_E_ARG, "null argument");
+    int rc = select_device(device, "the ISSL scorer");
     if (rc) return rc;
     HIP_TRY(hipMemGetInfo(free_bytes, total_bytes));
     return ISSL_OK;
@@ -278,14 +278,14 @@ int issl_device_memory(int device, size_t *free_bytes, size_t *total_bytes)
 
 int issl_index_upload(issl_index *idx, int device)
 {
-    if (!idx) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] { return upload_common(idx, device, nullptr, 0); });
 }
 
 int issl_index_upload_into(issl_index *idx, int device, void *dev_buf, size_t bytes)
 {
     if (!dev_buf) { set_error("null device buffer"); return ISSL_E_ARG; }
-    if (!idx) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] { return upload_common(idx, device, dev_buf, bytes); });
 }
 
@@ -303,7 +303,7 @@ int issl_index_attach_image_cold(int device, void *dev_buf, size_t bytes, void *
 
 int issl_index_cold(const issl_index *idx, void **host_ptr, size_t *bytes)
 {
-    if (!idx || !host_ptr || !bytes) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !host_ptr || !bytes) return issl::fail(ISSL_E_ARG, "null argument");
     if (!idx->d_image) { set_error("index has no device image"); return ISSL_E_STATE; }
     *host_ptr = idx->hdr.cold_on_host ? idx->h_cold : nullptr;
     *bytes = idx->hdr.cold_on_host ? idx->hdr.cold_bytes : 0;
@@ -312,7 +312,7 @@ int issl_index_cold(const issl_index *idx, void **host_ptr, size_t *bytes)
 
 int issl_index_image(const issl_index *idx, void **dev_ptr, size_t *bytes)
 {
-    if (!idx || !dev_ptr || !bytes) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !dev_ptr || !bytes) return issl::fail(ISSL_E_ARG, "null argument");
     if (!idx->d_image) { set_error("index has no device image"); return ISSL_E_STATE; }
     *dev_ptr = idx->d_image;
     *bytes = idx->hdr.total_bytes;
@@ -321,7 +321,7 @@ int issl_index_image(const issl_index *idx, void **dev_ptr, size_t *bytes)
 
 int issl_index_copy_image_to(const issl_index *idx, void *dev_dst, size_t bytes)
 {
-    if (!idx || !dev_dst) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !dev_dst) return issl::fail(ISSL_E_ARG, "null argument");
     if (!idx->d_image) { set_error("index has no device image"); return ISSL_E_STATE; }
     if (bytes < idx->hdr.total_bytes || (reinterpret_cast<uintptr_t>(dev_dst) & 255u)) {
         set_error("destination too small or not 256-byte aligned");
@@ -340,7 +340,7 @@ void issl_free(void *p) { std::free(p); }
 int issl_score_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, double threshold,
                       int method, double *d_mit, double *d_cfd, void *stream)
 {
-    if (!idx || (n && (!d_guides || !d_mit || !d_cfd))) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || (n && (!d_guides || !d_mit || !d_cfd))) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&]() -> int {
         return score_core(idx, d_guides, n, max_dist, threshold, method, d_mit, d_cfd, static_cast<hipStream_t>(stream), false);
     });
@@ -349,7 +349,7 @@ int issl_score_device(issl_index *idx, const uint64_t *d_guides, size_t n, int m
 int issl_score_device_async(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, double threshold,
                             int method, double *d_mit, double *d_cfd, void *stream)
 {
-    if (!idx || (n && (!d_guides || !d_mit || !d_cfd))) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || (n && (!d_guides || !d_mit || !d_cfd))) return issl::fail(ISSL_E_ARG, "null argument");
     if (!idx->d_image) { set_error("index has no device image: call issl_index_upload first"); return ISSL_E_STATE; }
     if (n == 0) return ISSL_OK;
     if (n > kMaxBatch) { // before any workspace is sized for it
@@ -363,20 +363,20 @@ int issl_score_device_async(issl_index *idx, const uint64_t *d_guides, size_t n,
 
 int issl_score_wait(issl_index *idx, void *stream)
 {
-    if (!idx) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] { return wait_batches(idx, static_cast<hipStream_t>(stream)); });
 }
 
 int issl_score_finish(issl_index *idx, void *stream)
 {
-    if (!idx) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] { return finish_batches(idx, static_cast<hipStream_t>(stream)); });
 }
 
 int issl_score(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, double threshold, int method,
                double *mit, double *cfd)
 {
-    if (!idx || (n && (!guides || !mit || !cfd))) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || (n && (!guides || !mit || !cfd))) return issl::fail(ISSL_E_ARG, "null argument");
     if (!idx->d_image) { set_error("index has no device image: call issl_index_upload first"); return ISSL_E_STATE; }
     if (n == 0) return ISSL_OK;
     return abi_call([&] { return score_host(idx, guides, n, max_dist, threshold, method, mit, cfd); });
@@ -385,7 +385,7 @@ int issl_score(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, 
 int issl_dump_hits(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, double threshold, int method,
                    issl_hit *hits, size_t cap, size_t *n_hits)
 {
-    if (!idx || !n_hits || (n && !guides) || (cap && !hits)) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !n_hits || (n && !guides) || (cap && !hits)) return issl::fail(ISSL_E_ARG, "null argument");
     if (!idx->d_image) { set_error("index has no device image: call issl_index_upload first"); return ISSL_E_STATE; }
     *n_hits = 0;
     if (n == 0) return ISSL_OK;
@@ -396,7 +396,7 @@ int issl_dump_hits(issl_index *idx, const uint64_t *guides, size_t n, int max_di
 // Off-target report: arguments first (without a device), then the state of the handle.
 static int report_args(const issl_index *idx, bool pointers, int max_dist)
 {
-    if (!idx || !pointers) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !pointers) return issl::fail(ISSL_E_ARG, "null argument");
     if (max_dist < 0 || max_dist >= ISSL_PROFILE_BINS) { set_error("max_dist must lie in 0..6 for the off-target report"); return ISSL_E_ARG; }
     if (!idx->d_image) { set_error("index has no device image: call issl_index_upload first"); return ISSL_E_STATE; }
     return ISSL_OK;
@@ -434,14 +434,14 @@ int issl_offtargets_device(issl_index *idx, const uint64_t *d_guides, size_t n, 
 
 int issl_last_stats(const issl_index *idx, issl_stats *out)
 {
-    if (!idx || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !out) return issl::fail(ISSL_E_ARG, "null argument");
     *out = idx->stats;
     return ISSL_OK;
 }
 
 int issl_count_candidates(const issl_index *idx, const uint64_t *guides, size_t n, uint64_t *out)
 {
-    if (!idx || !out || (n && !guides)) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !out || (n && !guides)) return issl::fail(ISSL_E_ARG, "null argument");
     const uint64_t per = idx->geo.buckets_per_slice();
     uint64_t total = 0;
     for (size_t i = 0; i < n; ++i)

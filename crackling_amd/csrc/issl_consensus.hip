@@ -295,14 +295,6 @@ __global__ __launch_bounds__(kThreads) void k_pages_fill(const uint32_t *__restr
     starts[p] = edges[b] + (p - first[b]) * page_length;
 }
 
-struct OwnedStream {
-    hipStream_t s = nullptr;
-    OwnedStream() = default;
-    OwnedStream(const OwnedStream &) = delete;
-    OwnedStream &operator=(const OwnedStream &) = delete;
-    ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
-};
-
 } // namespace
 } // namespace issl
 
@@ -321,30 +313,28 @@ struct issl_consensus {
 namespace issl {
 namespace {
 
-uint32_t blocks_of(uint32_t n) { return (n + kThreads - 1) / kThreads; }
-
 // counts[0 .. blocks) of the kernel before -> the list: its length to the host, its rows ascending into `list`.
 int make_list(issl_consensus *c, List which, DevBuf &list, uint64_t &n_list)
 {
     hipStream_t stream = c->stream.s;
-    const uint32_t blocks = blocks_of(c->n);
+    const uint32_t blocks = blocks_for(c->n, kThreads);
     uint32_t *counts = static_cast<uint32_t *>(c->counts.p);
     launch_scan(counts, blocks + 1ull, stream);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     uint32_t total = 0;
-    EX_HIP_TRY(hipMemcpyAsync(&total, counts + blocks, 4, hipMemcpyDeviceToHost, stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpyAsync(&total, counts + blocks, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     if (total > c->n) {
         set_error("consensus list on the device: " + std::to_string(total) + " of " + std::to_string(c->n) + " guides");
         return ISSL_E_DEVICE;
     }
     n_list = total;
     if (total) {
-        EX_HIP_TRY(hipMalloc(&list.p, 4ull * total));
+        HIP_TRY(hipMalloc(&list.p, 4ull * total));
         hipLaunchKernelGGL(k_consensus_list, dim3(blocks), dim3(kThreads), 0, stream, c->guides, c->n, c->cfg, which,
                            static_cast<const ulonglong2 *>(c->rows.p), counts, static_cast<uint32_t *>(list.p), total);
-        EX_HIP_TRY(hipGetLastError());
-        EX_HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
     }
     return ISSL_OK;
 }
@@ -376,21 +366,21 @@ int consensus_begin(const issl_guide_set *gs, const issl_consensus_config *cfg, 
     c->cfg = Config{cfg->optimisation, cfg->n, cfg->mm10db, cfg->chopchop, cfg->sgrnascorer2, cfg->sgrnascorer2 ? cfg->n_sv : 0u,
                     cfg->intercept, cfg->sgrna_threshold, cfg->low_energy, cfg->high_energy};
     if (c->n) {
-        if (int rc = use_device(c->device)) return rc;
-        EX_HIP_TRY(hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
+        if (int rc = select_device(c->device, "the extraction")) return rc;
+        HIP_TRY(hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
         hipStream_t stream = c->stream.s;
-        const uint32_t blocks = blocks_of(c->n);
-        EX_HIP_TRY(hipMalloc(&c->rows.p, 32ull * c->n));
-        EX_HIP_TRY(hipMalloc(&c->counts.p, 4 * scan_words(blocks + 1ull)));
+        const uint32_t blocks = blocks_for(c->n, kThreads);
+        HIP_TRY(hipMalloc(&c->rows.p, 32ull * c->n));
+        HIP_TRY(hipMalloc(&c->counts.p, 4 * scan_words(blocks + 1ull)));
         if (!table.empty()) {
-            EX_HIP_TRY(hipMalloc(&c->sv.p, sizeof(SupportVector) * table.size()));
-            EX_HIP_TRY(hipMemcpyAsync(c->sv.p, table.data(), sizeof(SupportVector) * table.size(), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMalloc(&c->sv.p, sizeof(SupportVector) * table.size()));
+            HIP_TRY(hipMemcpyAsync(c->sv.p, table.data(), sizeof(SupportVector) * table.size(), hipMemcpyHostToDevice, stream));
         }
         uint32_t *counts = static_cast<uint32_t *>(c->counts.p);
-        EX_HIP_TRY(hipMemsetAsync(counts + blocks, 0, 4, stream));
+        HIP_TRY(hipMemsetAsync(counts + blocks, 0, 4, stream));
         hipLaunchKernelGGL(k_consensus_begin, dim3(blocks), dim3(kThreads), 0, stream, c->guides, c->n, c->cfg,
                            static_cast<ulonglong2 *>(c->rows.p), counts);
-        EX_HIP_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (int rc = make_list(c.get(), kFoldList, c->fold_list, c->n_fold)) return rc; // (waits: the table may go)
     }
     *out = c.release();
@@ -401,26 +391,26 @@ int consensus_begin(const issl_guide_set *gs, const issl_consensus_config *cfg, 
 int consensus_finish(issl_consensus *c, const issl_fold *folds, bool on_device = false)
 {
     if (c->n) {
-        EX_HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipSetDevice(c->device));
         hipStream_t stream = c->stream.s;
-        const uint32_t blocks = blocks_of(c->n);
+        const uint32_t blocks = blocks_for(c->n, kThreads);
         DevBuf d_folds;
         if (c->n_fold) {
             const uint32_t n_fold = static_cast<uint32_t>(c->n_fold);
             if (!on_device) {
-                EX_HIP_TRY(hipMalloc(&d_folds.p, 16ull * n_fold));
-                EX_HIP_TRY(hipMemcpyAsync(d_folds.p, folds, 16ull * n_fold, hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMalloc(&d_folds.p, 16ull * n_fold));
+                HIP_TRY(hipMemcpyAsync(d_folds.p, folds, 16ull * n_fold, hipMemcpyHostToDevice, stream));
             }
-            hipLaunchKernelGGL(k_consensus_fold, dim3(blocks_of(n_fold)), dim3(kThreads), 0, stream, c->guides, c->n, c->cfg,
+            hipLaunchKernelGGL(k_consensus_fold, dim3(blocks_for(n_fold, kThreads)), dim3(kThreads), 0, stream, c->guides, c->n, c->cfg,
                                static_cast<const uint32_t *>(c->fold_list.p), on_device ? folds : static_cast<const issl_fold *>(d_folds.p), n_fold,
                                static_cast<issl_consensus_row *>(c->rows.p));
-            EX_HIP_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         uint32_t *counts = static_cast<uint32_t *>(c->counts.p);
-        EX_HIP_TRY(hipMemsetAsync(counts + blocks, 0, 4, stream));
+        HIP_TRY(hipMemsetAsync(counts + blocks, 0, 4, stream));
         hipLaunchKernelGGL(k_consensus_finish, dim3(blocks), dim3(kThreads), 0, stream, c->guides, c->n, c->cfg,
                            static_cast<const SupportVector *>(c->sv.p), static_cast<ulonglong2 *>(c->rows.p), counts);
-        EX_HIP_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (int rc = make_list(c, kSelection, c->selection, c->n_selected)) return rc; // (waits: the folds may go)
     }
     c->finished = true;
@@ -430,13 +420,13 @@ int consensus_finish(issl_consensus *c, const issl_fold *folds, bool on_device =
 int consensus_selection_pages(issl_consensus *c, uint64_t batch_size, uint64_t page_length, const uint64_t **d_page_starts,
                               uint64_t *n_pages)
 {
-    if (int rc = use_device(c->device)) return rc;
+    if (int rc = select_device(c->device, "the extraction")) return rc;
     c->pages.release();
     const uint64_t n = c->n;
     const uint32_t n_selected = static_cast<uint32_t>(c->n_selected);
     if (n == 0) { // no batch: no page, and the one boundary that ends them
-        EX_HIP_TRY(hipMalloc(&c->pages.p, 8));
-        EX_HIP_TRY(hipMemset(c->pages.p, 0, 8));
+        HIP_TRY(hipMalloc(&c->pages.p, 8));
+        HIP_TRY(hipMemset(c->pages.p, 0, 8));
         *d_page_starts = static_cast<const uint64_t *>(c->pages.p);
         *n_pages = 0;
         return ISSL_OK;
@@ -448,34 +438,27 @@ int consensus_selection_pages(issl_consensus *c, uint64_t batch_size, uint64_t p
     const uint64_t cap = by_length < n_selected ? by_length : n_selected;
     Arena work;
     const size_t o_edges = work.reserve(4 * (n_batches + 1ull)), o_counts = work.reserve(4 * scan_words(n_batches + 1ull));
-    EX_HIP_TRY(hipMalloc(&work.buf.p, work.size));
-    EX_HIP_TRY(hipMalloc(&c->pages.p, 8 * (cap + 1)));
+    HIP_TRY(hipMalloc(&work.buf.p, work.size));
+    HIP_TRY(hipMalloc(&c->pages.p, 8 * (cap + 1)));
     uint32_t *edges = work.at<uint32_t>(o_edges), *counts = work.at<uint32_t>(o_counts);
     uint64_t *starts = static_cast<uint64_t *>(c->pages.p);
-    EX_HIP_TRY(hipMemsetAsync(counts + n_batches, 0, 4, stream));
+    HIP_TRY(hipMemsetAsync(counts + n_batches, 0, 4, stream));
     hipLaunchKernelGGL(k_pages_edges, dim3(static_cast<uint32_t>((n_batches + 1ull + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
                        static_cast<const uint32_t *>(c->selection.p), n_selected, n, batch_size, n_batches, edges);
-    hipLaunchKernelGGL(k_pages_count, dim3(blocks_of(n_batches)), dim3(kThreads), 0, stream, edges, n_batches, page_length, counts);
+    hipLaunchKernelGGL(k_pages_count, dim3(blocks_for(n_batches, kThreads)), dim3(kThreads), 0, stream, edges, n_batches, page_length, counts);
     launch_scan(counts, n_batches + 1ull, stream);
     hipLaunchKernelGGL(k_pages_fill, dim3(static_cast<uint32_t>((cap + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, edges,
                        counts, n_batches, page_length, n_selected, cap, starts);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     uint32_t total = 0;
-    EX_HIP_TRY(hipMemcpyAsync(&total, counts + n_batches, 4, hipMemcpyDeviceToHost, stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream)); // the one wait: the boundaries are written and the work buffers may go
+    HIP_TRY(hipMemcpyAsync(&total, counts + n_batches, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // the one wait: the boundaries are written and the work buffers may go
     if (total > cap) {
         set_error("pages on the device: " + std::to_string(total) + ", at most " + std::to_string(cap) + " expected");
         return ISSL_E_DEVICE;
     }
     *d_page_starts = starts;
     *n_pages = total;
-    return ISSL_OK;
-}
-
-int copy_from_device(const issl_consensus *c, void *out, const void *src, size_t bytes)
-{
-    EX_HIP_TRY(hipSetDevice(c->device));
-    EX_HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
     return ISSL_OK;
 }
 
@@ -523,7 +506,7 @@ int issl_consensus_fold_copy(const issl_consensus *c, uint32_t *rows, size_t cap
         return ISSL_E_ARG;
     }
     if (c->n_fold == 0) return ISSL_OK;
-    return issl::abi_call([&] { return issl::copy_from_device(c, rows, c->fold_list.p, 4 * c->n_fold); });
+    return issl::abi_call([&] { return issl::copy_to_host(c->device, rows, c->fold_list.p, 4 * c->n_fold); });
 }
 
 int issl_consensus_finish(issl_consensus *c, const issl_fold *folds, size_t n_folds)
@@ -555,7 +538,7 @@ int issl_consensus_copy(const issl_consensus *c, issl_consensus_row *out, size_t
         return ISSL_E_ARG;
     }
     if (c->n == 0) return ISSL_OK;
-    return issl::abi_call([&] { return issl::copy_from_device(c, out, c->rows.p, 32ull * c->n); });
+    return issl::abi_call([&] { return issl::copy_to_host(c->device, out, c->rows.p, 32ull * c->n); });
 }
 
 int issl_consensus_device(const issl_consensus *c, const issl_consensus_row **d_rows, const uint32_t **d_selected, uint64_t *n_selected)

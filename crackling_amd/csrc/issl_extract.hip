@@ -20,7 +20,6 @@
 
 #include <algorithm>
 #include <cctype>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -316,74 +315,35 @@ void append_records(const char *fasta, size_t len, bool per_file, std::string &s
 
 namespace {
 
-// ISSL_UPLOAD_TIMING=1: one stderr line per stage of the genome -> index path, the device synchronised at each boundary.
-struct StageClock {
-    bool on = false;
-    double t0 = 0;
-    static double now_ms()
-    {
-        using namespace std::chrono;
-        return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-    }
-    void start() { if (on) t0 = now_ms(); }
-    void note(const char *stage)
-    {
-        if (!on) return;
-        (void)hipDeviceSynchronize();
-        const double t = now_ms();
-        std::fprintf(stderr, "[issl genome] %s %.1f ms\n", stage, t - t0);
-        t0 = t;
-    }
-};
-
-} // namespace
-
-int use_device(int device)
-{
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        set_error("no HIP device available: the extraction has no CPU fallback");
-        return ISSL_E_DEVICE;
-    }
-    if (device < 0 || device >= count) {
-        set_error("device out of range");
-        return ISSL_E_ARG;
-    }
-    EX_HIP_TRY(hipSetDevice(device));
-    return ISSL_OK;
-}
-
-namespace {
-
 // seq (host) -> sorted site keys in the memory of the current device: keys.p holds *n_sites of them (null when there
 // are none).  Peak: the sequence, then 16 B per site (keys + sort scratch).
-int extract_sorted_keys(const std::string &seq, DevBuf &keys, uint64_t *n_sites, StageClock *clock)
+int extract_sorted_keys(const std::string &seq, DevBuf &keys, uint64_t *n_sites, StageTimer *clock)
 {
     *n_sites = 0;
     const uint64_t len = seq.size();
     if (len < 23) return ISSL_OK;
     DevBuf seq_buf, ctr_buf, tmp_buf;
-    EX_HIP_TRY(hipMalloc(&seq_buf.p, len));
-    EX_HIP_TRY(hipMalloc(&ctr_buf.p, 16));
+    HIP_TRY(hipMalloc(&seq_buf.p, len));
+    HIP_TRY(hipMalloc(&ctr_buf.p, 16));
     uint8_t *d_seq = static_cast<uint8_t *>(seq_buf.p);
     unsigned long long *d_ctr = static_cast<unsigned long long *>(ctr_buf.p);
-    EX_HIP_TRY(hipMemcpy(d_seq, seq.data(), len, hipMemcpyHostToDevice));
-    EX_HIP_TRY(hipMemset(d_ctr, 0, 16));
+    HIP_TRY(hipMemcpy(d_seq, seq.data(), len, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_ctr, 0, 16));
     if (clock) clock->note("upload");
     const uint32_t blocks = static_cast<uint32_t>((len + kPosPerBlock - 1) / kPosPerBlock);
     hipLaunchKernelGGL(k_match_count, dim3(blocks), dim3(256), 0, nullptr, d_seq, len, d_ctr);
     unsigned long long total = 0;
-    EX_HIP_TRY(hipMemcpy(&total, d_ctr, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&total, d_ctr, 8, hipMemcpyDeviceToHost));
     if (total > 0xFFFFFFFFull) { // the radix passes count and place with 32-bit offsets (issl_radix.hpp)
         set_error("more than 2^32 - 1 sites in one extraction (" + std::to_string(total) + "): split the input");
         return ISSL_E_UNSUPPORTED;
     }
     if (total == 0) return ISSL_OK;
-    EX_HIP_TRY(hipMalloc(&keys.p, 8 * total));
-    EX_HIP_TRY(hipMalloc(&tmp_buf.p, 8 * total));
+    HIP_TRY(hipMalloc(&keys.p, 8 * total));
+    HIP_TRY(hipMalloc(&tmp_buf.p, 8 * total));
     uint64_t *d_keys = static_cast<uint64_t *>(keys.p), *d_tmp = static_cast<uint64_t *>(tmp_buf.p);
     hipLaunchKernelGGL(k_match_emit, dim3(blocks), dim3(256), 0, nullptr, d_seq, len, d_ctr + 1, d_keys, total);
-    EX_HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     seq_buf.release();
     if (clock) clock->note("match");
     int rc = radix_sort(d_keys, d_tmp, total, 40);
@@ -397,7 +357,7 @@ int extract_sorted_keys(const std::string &seq, DevBuf &keys, uint64_t *n_sites,
 // seq (host) -> sorted site text (host, malloc'd).
 int extract_sorted_text(const std::string &seq, int device, char **out_text, size_t *out_len, uint64_t *n_sites)
 {
-    if (int rc = use_device(device)) return rc;
+    if (int rc = select_device(device, "the extraction")) return rc;
     *out_text = nullptr;
     *out_len = 0;
     *n_sites = 0;
@@ -409,7 +369,7 @@ int extract_sorted_text(const std::string &seq, int device, char **out_text, siz
         return ISSL_OK;
     }
     const uint64_t *d_keys = static_cast<const uint64_t *>(keys_buf.p);
-    EX_HIP_TRY(hipMalloc(&text_buf.p, 21 * total));
+    HIP_TRY(hipMalloc(&text_buf.p, 21 * total));
     char *d_text = static_cast<char *>(text_buf.p);
     hipLaunchKernelGGL(k_keys_to_text, dim3(static_cast<uint32_t>((total + 255) / 256)), dim3(256), 0, nullptr, d_keys,
                        total, d_text);
@@ -434,10 +394,10 @@ int extract_sorted_text(const std::string &seq, int device, char **out_text, siz
 // extract_sorted_text followed by HostIndex::build_from_text(text, n_sites, 20, slice_width) (the text is sorted, so
 // its runs of equal lines are the runs of equal keys), for the widths the device builder takes (checked by the caller).
 // Peak of the collapse: 8 B per raw site (keys) + 12 B per distinct site; keys are gone before the image build starts.
-int build_index_from_seq(const std::string &seq, size_t slice_width, int device, const char *options, StageClock &clock,
+int build_index_from_seq(const std::string &seq, size_t slice_width, int device, const char *options, StageTimer &clock,
                          issl_index **out)
 {
-    if (int rc = use_device(device)) return rc;
+    if (int rc = select_device(device, "the extraction")) return rc;
     {
         Tuning probe = Tuning::from_env(); // a typo in the options fails here, not after the extraction
         if (int rc = probe.set_list(options)) return rc;
@@ -451,24 +411,24 @@ int build_index_from_seq(const std::string &seq, size_t slice_width, int device,
     }
     const uint64_t *d_keys = static_cast<const uint64_t *>(keys_buf.p);
     const uint32_t n_blocks = static_cast<uint32_t>((n + kRunBlockKeys - 1) / kRunBlockKeys);
-    EX_HIP_TRY(hipMalloc(&first_buf.p, 4 * scan_words(n_blocks + 1ull)));
+    HIP_TRY(hipMalloc(&first_buf.p, 4 * scan_words(n_blocks + 1ull)));
     uint32_t *d_first = static_cast<uint32_t *>(first_buf.p);
-    EX_HIP_TRY(hipMemset(d_first + n_blocks, 0, 4));
+    HIP_TRY(hipMemset(d_first + n_blocks, 0, 4));
     hipLaunchKernelGGL(k_run_heads, dim3(n_blocks), dim3(256), 0, nullptr, d_keys, n, d_first);
     launch_scan(d_first, n_blocks + 1ull, nullptr);
     uint32_t n_distinct = 0;
-    EX_HIP_TRY(hipMemcpy(&n_distinct, d_first + n_blocks, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n_distinct, d_first + n_blocks, 4, hipMemcpyDeviceToHost));
     if (n_distinct == 0 || n_distinct > n) {
         set_error("site collapse on the device: " + std::to_string(n_distinct) + " distinct of " + std::to_string(n) + " sites");
         return ISSL_E_DEVICE;
     }
-    EX_HIP_TRY(hipMalloc(&sigs_buf.p, 8ull * n_distinct));
-    EX_HIP_TRY(hipMalloc(&occ_buf.p, 4ull * n_distinct));
+    HIP_TRY(hipMalloc(&sigs_buf.p, 8ull * n_distinct));
+    HIP_TRY(hipMalloc(&occ_buf.p, 4ull * n_distinct));
     uint64_t *d_sigs = static_cast<uint64_t *>(sigs_buf.p);
     uint32_t *d_occ = static_cast<uint32_t *>(occ_buf.p);
-    EX_HIP_TRY(hipMemset(d_occ, 0, 4ull * n_distinct));
+    HIP_TRY(hipMemset(d_occ, 0, 4ull * n_distinct));
     hipLaunchKernelGGL(k_run_sites, dim3(n_blocks), dim3(256), 0, nullptr, d_keys, n, d_first, d_sigs, d_occ);
-    EX_HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     keys_buf.release();
     first_buf.release();
     clock.note("collapse");
@@ -485,21 +445,8 @@ int build_index_from_seq(const std::string &seq, size_t slice_width, int device,
 int read_fasta_files(const char *const *paths, int n, std::string &seq, std::vector<FastaRecord> *records)
 {
     for (int f = 0; f < n; ++f) {
-        FILE *fp = std::fopen(paths[f], "rb");
-        if (!fp) {
-            set_error(std::string("cannot open '") + paths[f] + "'");
-            return ISSL_E_IO;
-        }
-        std::fseek(fp, 0, SEEK_END);
-        const long sz = std::ftell(fp);
-        std::fseek(fp, 0, SEEK_SET);
-        std::vector<char> buf(sz > 0 ? static_cast<size_t>(sz) : 0);
-        if (sz > 0 && std::fread(buf.data(), buf.size(), 1, fp) < 1) {
-            std::fclose(fp);
-            set_error(std::string("cannot read '") + paths[f] + "'");
-            return ISSL_E_IO;
-        }
-        std::fclose(fp);
+        std::vector<char> buf; // one file's bytes at a time: released before the next is read
+        if (int rc = read_whole_file(paths[f], buf)) return rc;
         append_records(buf.data(), buf.size(), n > 1, seq, records);
     }
     return ISSL_OK;
@@ -523,10 +470,7 @@ extern "C" {
 int issl_extract_from_memory(const char *const *files, const size_t *lens, int n_files, int device, char **out_text,
                              size_t *out_len, uint64_t *n_sites)
 {
-    if (!files || !lens || n_files <= 0 || !out_text || !out_len || !n_sites) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!files || !lens || n_files <= 0 || !out_text || !out_len || !n_sites) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] {
         std::string seq;
         for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], n_files > 1, seq);
@@ -537,10 +481,7 @@ int issl_extract_from_memory(const char *const *files, const size_t *lens, int n
 int issl_extract_offtargets(const char *const *inputs, int n_inputs, const char *output_path, int device,
                             uint64_t *n_sites)
 {
-    if (!inputs || n_inputs <= 0 || !output_path || !n_sites) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!inputs || n_inputs <= 0 || !output_path || !n_sites) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
         std::string seq;
         if (int rc = issl::read_fasta_files(inputs, n_inputs, seq)) return rc;
@@ -569,13 +510,9 @@ int issl_index_build_from_fasta(const char *const *files, const size_t *lens, in
                                 const char *options, issl_index **out)
 {
     if (!issl::fasta_index_width(slice_width)) return ISSL_E_ARG;
-    if (!files || !lens || n_files <= 0 || !out) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!files || !lens || n_files <= 0 || !out) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] {
-        issl::StageClock clock{issl::Tuning::from_env().upload_timing};
-        clock.start();
+        issl::StageTimer clock(issl::Tuning::from_env().upload_timing, "[issl genome]"); // ISSL_UPLOAD_TIMING=1: one stderr line per stage
         std::string seq;
         for (int f = 0; f < n_files; ++f) issl::append_records(files[f], lens[f], n_files > 1, seq);
         clock.note("parse");
@@ -587,13 +524,9 @@ int issl_index_build_from_fasta_files(const char *const *paths, int n_paths, siz
                                       const char *options, issl_index **out)
 {
     if (!issl::fasta_index_width(slice_width)) return ISSL_E_ARG;
-    if (!paths || n_paths <= 0 || !out) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!paths || n_paths <= 0 || !out) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
-        issl::StageClock clock{issl::Tuning::from_env().upload_timing};
-        clock.start();
+        issl::StageTimer clock(issl::Tuning::from_env().upload_timing, "[issl genome]"); // ISSL_UPLOAD_TIMING=1: one stderr line per stage
         std::string seq;
         if (int rc = issl::read_fasta_files(paths, n_paths, seq)) return rc;
         clock.note("parse");

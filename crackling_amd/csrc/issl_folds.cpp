@@ -14,19 +14,9 @@
 #include "issl_folds.hpp"
 #include "issl_folds_text.hpp"
 #include "issl_host.hpp"
-#include "issl_match.hpp"
 
 namespace issl {
 namespace {
-
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
 
 uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
@@ -46,15 +36,15 @@ int folds_open(const issl_consensus *c, issl_folds **out)
     f->consensus = c;
     f->src = consensus_fold_source(c);
     if (f->src.n_fold) {
-        if (int rc = use_device(f->src.device)) return rc;
-        EX_HIP_TRY(hipStreamCreateWithFlags(&f->stream.s, hipStreamNonBlocking));
-        EX_HIP_TRY(hipMalloc(&f->folds.p, 16ull * f->src.n_fold));
-        EX_HIP_TRY(hipMalloc(&f->spans.p, 48ull * f->src.n_fold));
-        EX_HIP_TRY(hipMalloc(&f->error.p, 8));
+        if (int rc = select_device(f->src.device, "the extraction")) return rc;
+        HIP_TRY(hipStreamCreateWithFlags(&f->stream.s, hipStreamNonBlocking));
+        HIP_TRY(hipMalloc(&f->folds.p, 16ull * f->src.n_fold));
+        HIP_TRY(hipMalloc(&f->spans.p, 48ull * f->src.n_fold));
+        HIP_TRY(hipMalloc(&f->error.p, 8));
         launch_folds_clear(static_cast<issl_fold *>(f->folds.p), static_cast<issl_text_span *>(f->spans.p), 0, f->src.n_fold,
                            f->stream.s);
-        EX_HIP_TRY(hipGetLastError());
-        EX_HIP_TRY(hipStreamSynchronize(f->stream.s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(f->stream.s));
     }
     *out = f.release();
     return ISSL_OK;
@@ -66,24 +56,23 @@ int folds_input(issl_folds *f, uint64_t first, uint64_t n)
     f->input.release();
     f->ms_input = 0;
     if (n == 0) return ISSL_OK;
-    if (int rc = use_device(f->src.device)) return rc;
-    EX_HIP_TRY(hipMalloc(&f->input.p, up16(n * kFoldLineBytes)));
-    EventPair ev;
-    EX_HIP_TRY(hipEventCreate(&ev.a));
-    EX_HIP_TRY(hipEventCreate(&ev.b));
-    EX_HIP_TRY(hipEventRecord(ev.a, f->stream.s));
+    if (int rc = select_device(f->src.device, "the extraction")) return rc;
+    HIP_TRY(hipMalloc(&f->input.p, up16(n * kFoldLineBytes)));
+    Events<2> ev;
+    if (int rc = ev.create()) return rc;
+    HIP_TRY(hipEventRecord(ev.e[0], f->stream.s));
     launch_folds_input(f->src, first, n, static_cast<char *>(f->input.p), f->stream.s);
-    EX_HIP_TRY(hipGetLastError());
-    EX_HIP_TRY(hipEventRecord(ev.b, f->stream.s));
-    EX_HIP_TRY(hipStreamSynchronize(f->stream.s));
-    EX_HIP_TRY(hipEventElapsedTime(&f->ms_input, ev.a, ev.b));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[1], f->stream.s));
+    HIP_TRY(hipStreamSynchronize(f->stream.s));
+    HIP_TRY(hipEventElapsedTime(&f->ms_input, ev.e[0], ev.e[1]));
     return ISSL_OK;
 }
 
 int folds_input_copy(issl_folds *f, uint64_t first, uint64_t n, char *out)
 {
     if (int rc = folds_input(f, first, n)) return rc;
-    if (n) EX_HIP_TRY(hipMemcpy(out, f->input.p, n * kFoldLineBytes, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(out, f->input.p, n * kFoldLineBytes, hipMemcpyDeviceToHost));
     return ISSL_OK;
 }
 
@@ -115,10 +104,10 @@ int reserve_text(issl_folds *f, uint64_t need, uint64_t guess)
     if (hipMalloc(&grown.p, cap) != hipSuccess) { // the guess was generous: what this page needs, then
         (void)hipGetLastError();
         cap = need;
-        EX_HIP_TRY(hipMalloc(&grown.p, cap));
+        HIP_TRY(hipMalloc(&grown.p, cap));
     }
-    if (f->text_used) EX_HIP_TRY(hipMemcpyAsync(grown.p, f->text.p, f->text_used, hipMemcpyDeviceToDevice, f->stream.s));
-    EX_HIP_TRY(hipStreamSynchronize(f->stream.s));
+    if (f->text_used) HIP_TRY(hipMemcpyAsync(grown.p, f->text.p, f->text_used, hipMemcpyDeviceToDevice, f->stream.s));
+    HIP_TRY(hipStreamSynchronize(f->stream.s));
     std::swap(f->text.p, grown.p);
     f->text_cap = cap;
     return ISSL_OK;
@@ -128,7 +117,7 @@ int folds_read(issl_folds *f, uint64_t first, uint64_t n, const char *text, uint
 {
     f->ms_read = 0;
     if (n == 0) return ISSL_OK;
-    if (int rc = use_device(f->src.device)) return rc;
+    if (int rc = select_device(f->src.device, "the extraction")) return rc;
     hipStream_t stream = f->stream.s;
     const uint64_t base = up16(f->text_used);
     const uint64_t padded = (len + kFoldGroupBytes - 1) / kFoldGroupBytes * kFoldGroupBytes + kFoldGroupBytes;
@@ -140,12 +129,12 @@ int folds_read(issl_folds *f, uint64_t first, uint64_t n, const char *text, uint
     const uint64_t guess = base + padded + (rest ? per_row * rest + 4096 : 0);
     if (int rc = reserve_text(f, base + padded, guess)) return rc;
     uint8_t *d_text = static_cast<uint8_t *>(f->text.p) + base;
-    if (len) EX_HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, stream));
-    EX_HIP_TRY(hipMemsetAsync(d_text + len, 0, padded - len, stream));
+    if (len) HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(d_text + len, 0, padded - len, stream));
     DevBuf work;
-    EX_HIP_TRY(hipMalloc(&work.p, folds_read_work(n, len) + 256));
+    HIP_TRY(hipMalloc(&work.p, folds_read_work(n, len) + 256));
     const uint64_t fine = kFoldNoError;
-    EX_HIP_TRY(hipMemcpyAsync(f->error.p, &fine, 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(f->error.p, &fine, 8, hipMemcpyHostToDevice, stream));
     FoldRead r{};
     r.text = d_text;
     r.len = len;
@@ -157,20 +146,19 @@ int folds_read(issl_folds *f, uint64_t first, uint64_t n, const char *text, uint
     r.spans = static_cast<issl_text_span *>(f->spans.p);
     r.error = static_cast<uint64_t *>(f->error.p);
     r.work = work.p;
-    EventPair ev;
-    EX_HIP_TRY(hipEventCreate(&ev.a));
-    EX_HIP_TRY(hipEventCreate(&ev.b));
-    EX_HIP_TRY(hipEventRecord(ev.a, stream));
-    EX_HIP_TRY(launch_folds_read(f->src, r, stream));
-    EX_HIP_TRY(hipEventRecord(ev.b, stream));
+    Events<2> ev;
+    if (int rc = ev.create()) return rc;
+    HIP_TRY(hipEventRecord(ev.e[0], stream));
+    HIP_TRY(launch_folds_read(f->src, r, stream));
+    HIP_TRY(hipEventRecord(ev.e[1], stream));
     uint64_t error = kFoldNoError;
-    EX_HIP_TRY(hipMemcpyAsync(&error, f->error.p, 8, hipMemcpyDeviceToHost, stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream)); // the one wait: the rows are written and the work buffer may go
-    EX_HIP_TRY(hipEventElapsedTime(&f->ms_read, ev.a, ev.b));
+    HIP_TRY(hipMemcpyAsync(&error, f->error.p, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // the one wait: the rows are written and the work buffer may go
+    HIP_TRY(hipEventElapsedTime(&f->ms_read, ev.e[0], ev.e[1]));
     if (error != kFoldNoError) { // nothing of this page is kept: its rows can be read again
         launch_folds_clear(r.folds, r.spans, first, n, stream);
-        EX_HIP_TRY(hipGetLastError());
-        EX_HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
         const uint64_t row = error >> 8;
         const uint32_t kind = static_cast<uint32_t>(error & 0xFF);
         if (kind == folds_text::kFormat) {
@@ -193,29 +181,9 @@ int folds_read(issl_folds *f, uint64_t first, uint64_t n, const char *text, uint
 
 int folds_read_file(issl_folds *f, uint64_t first, uint64_t n, const char *path)
 {
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) {
-        set_error(std::string("cannot open ") + path + ": " + std::strerror(errno));
-        return ISSL_E_IO;
-    }
     std::vector<char> text;
-    char buf[1 << 16];
-    size_t got;
-    while ((got = std::fread(buf, 1, sizeof buf, fp)) > 0) text.insert(text.end(), buf, buf + got);
-    const bool bad = std::ferror(fp) != 0;
-    std::fclose(fp);
-    if (bad) {
-        set_error(std::string("cannot read ") + path + ": " + std::strerror(errno));
-        return ISSL_E_IO;
-    }
+    if (int rc = read_whole_file(path, text)) return rc;
     return folds_read(f, first, n, text.data(), text.size());
-}
-
-int from_device(const issl_folds *f, void *out, const void *src, size_t bytes)
-{
-    EX_HIP_TRY(hipSetDevice(f->src.device));
-    EX_HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
-    return ISSL_OK;
 }
 
 } // namespace
@@ -331,9 +299,9 @@ int issl_folds_copy(const issl_folds *f, issl_fold *folds, issl_text_span *spans
     if (f->src.n_fold == 0) return ISSL_OK;
     return issl::abi_call([&]() -> int {
         if (folds)
-            if (int rc = issl::from_device(f, folds, f->folds.p, 16 * f->src.n_fold)) return rc;
+            if (int rc = issl::copy_to_host(f->src.device, folds, f->folds.p, 16 * f->src.n_fold)) return rc;
         if (spans)
-            if (int rc = issl::from_device(f, spans, f->spans.p, 48 * f->src.n_fold)) return rc;
+            if (int rc = issl::copy_to_host(f->src.device, spans, f->spans.p, 48 * f->src.n_fold)) return rc;
         return ISSL_OK;
     });
 }
@@ -345,7 +313,7 @@ int issl_folds_text_copy(const issl_folds *f, uint64_t fold_row, int which, char
     if (int rc = issl::in_list(f, fold_row, 1)) return rc;
     return issl::abi_call([&]() -> int {
         issl_text_span s;
-        if (int rc = issl::from_device(f, &s, static_cast<const issl_text_span *>(f->spans.p) + 3 * fold_row + which, 16)) return rc;
+        if (int rc = issl::copy_to_host(f->src.device, &s, static_cast<const issl_text_span *>(f->spans.p) + 3 * fold_row + which, 16)) return rc;
         if (s.length == issl::folds_text::kNoText) {
             *len = ~size_t(0);
             return ISSL_OK;
@@ -356,7 +324,7 @@ int issl_folds_text_copy(const issl_folds *f, uint64_t fold_row, int which, char
             return ISSL_E_ARG;
         }
         if (s.offset > f->text_used || s.length > f->text_used - s.offset) return issl::fail(ISSL_E_DEVICE, "a span outside the pages' text");
-        if (s.length) return issl::from_device(f, out, static_cast<const char *>(f->text.p) + s.offset, s.length);
+        if (s.length) return issl::copy_to_host(f->src.device, out, static_cast<const char *>(f->text.p) + s.offset, s.length);
         return ISSL_OK;
     });
 }

@@ -18,6 +18,7 @@
 
 #include "issl_folds.hpp"
 #include "issl_folds_text.hpp"
+#include "issl_match.hpp"
 #include "issl_radix.hpp"
 
 namespace issl {
@@ -199,7 +200,6 @@ __global__ __launch_bounds__(kThreads) void k_folds_rows(const ulonglong2 *__res
                                                                      static_cast<uint64_t>(folds_text::quote_bits(text, p.offset[k], p.length[k])) << 32);
 }
 
-uint32_t blocks_of(uint64_t n) { return static_cast<uint32_t>((n + kThreads - 1) / kThreads); }
 uint64_t groups_of(uint64_t len) { return (len + kFoldGroupBytes - 1) / kFoldGroupBytes; }
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -223,14 +223,14 @@ struct Work {
 void launch_folds_input(const FoldSource &src, uint64_t first, uint64_t n, char *text, hipStream_t stream)
 {
     if (!n) return;
-    hipLaunchKernelGGL(k_folds_input, dim3(blocks_of(n)), dim3(kThreads), 0, stream, src.guides, src.n_guides, src.fold_list,
+    hipLaunchKernelGGL(k_folds_input, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, src.guides, src.n_guides, src.fold_list,
                        first, n, text);
 }
 
 void launch_folds_clear(issl_fold *folds, issl_text_span *spans, uint64_t first, uint64_t n, hipStream_t stream)
 {
     if (!n) return;
-    hipLaunchKernelGGL(k_folds_clear, dim3(blocks_of(n)), dim3(kThreads), 0, stream, reinterpret_cast<ulonglong2 *>(folds),
+    hipLaunchKernelGGL(k_folds_clear, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, reinterpret_cast<ulonglong2 *>(folds),
                        reinterpret_cast<ulonglong2 *>(spans), first, n);
 }
 
@@ -248,14 +248,14 @@ hipError_t launch_folds_read(const FoldSource &src, const FoldRead &r, hipStream
     hipError_t e = hipMemsetAsync(ranks + n_groups, 0, 4, stream); // (unset, the ranks and the slots would give wrong pairs)
     if (e == hipSuccess) e = hipMemsetAsync(best, 0, 8 * r.n, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_folds_mark, dim3(blocks_of(n_groups)), dim3(kThreads), 0, stream, r.text, r.len, n_groups, ranks);
+    hipLaunchKernelGGL(k_folds_mark, dim3(blocks_for(n_groups, kThreads)), dim3(kThreads), 0, stream, r.text, r.len, n_groups, ranks);
     launch_scan(ranks, n_groups + 1, stream);
-    hipLaunchKernelGGL(k_folds_keys, dim3(blocks_of(r.n)), dim3(kThreads), 0, stream, src.guides, src.n_guides, src.fold_list,
+    hipLaunchKernelGGL(k_folds_keys, dim3(blocks_for(r.n, kThreads)), dim3(kThreads), 0, stream, src.guides, src.n_guides, src.fold_list,
                        r.first, r.n, keys);
     const uint64_t *sorted = radix_sort_async(keys, tmp, r.n, 0, 38, reinterpret_cast<uint32_t *>(work + w.hist), stream);
-    hipLaunchKernelGGL(k_folds_pairs, dim3(blocks_of(n_groups)), dim3(kThreads), 0, stream, r.text, r.len, n_groups, ranks,
+    hipLaunchKernelGGL(k_folds_pairs, dim3(blocks_for(n_groups, kThreads)), dim3(kThreads), 0, stream, r.text, r.len, n_groups, ranks,
                        r.last_line, sorted, r.n, best);
-    hipLaunchKernelGGL(k_folds_rows, dim3(blocks_of(r.n)), dim3(kThreads), 0, stream, src.guides, src.n_guides, src.fold_list,
+    hipLaunchKernelGGL(k_folds_rows, dim3(blocks_for(r.n, kThreads)), dim3(kThreads), 0, stream, src.guides, src.n_guides, src.fold_list,
                        r.first, r.n, r.text, r.len, r.base, sorted, best, reinterpret_cast<ulonglong2 *>(r.folds),
                        reinterpret_cast<ulonglong2 *>(r.spans), reinterpret_cast<unsigned long long *>(r.error));
     return hipGetLastError();

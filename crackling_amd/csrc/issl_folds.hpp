@@ -8,21 +8,13 @@
 #include <vector>
 
 #include "../../include/issl_hip.h"
-#include "issl_match.hpp"
+#include "issl_hiputil.hpp"
 
 namespace issl {
 
 constexpr uint32_t kFoldGroupBytes = 64;  // bytes of text whose line ends one thread marks: four 16-byte loads
 constexpr uint32_t kFoldLineBytes = 101;  // 'G', guide[1:20], the 80 characters of the scaffold, LF
 constexpr uint64_t kFoldNoError = ~0ull;  // the error word: fold row << 8 | kind, the lowest one wins
-
-struct OwnedFoldStream {
-    hipStream_t s = nullptr;
-    OwnedFoldStream() = default;
-    OwnedFoldStream(const OwnedFoldStream &) = delete;
-    OwnedFoldStream &operator=(const OwnedFoldStream &) = delete;
-    ~OwnedFoldStream() { if (s) (void)hipStreamDestroy(s); }
-};
 
 // What the consensus lends (issl_consensus.hip): the set's rows, the fold list.
 struct FoldSource {
@@ -61,7 +53,7 @@ hipError_t launch_folds_read(const FoldSource &src, const FoldRead &r, hipStream
 struct issl_folds {
     const issl_consensus *consensus = nullptr;
     issl::FoldSource src{};
-    issl::OwnedFoldStream stream;       // ahead of the buffers: they are released first
+    issl::OwnedStream stream;           // ahead of the buffers: they are released first
     issl::DevBuf folds, spans, error;   // n_fold rows, 3 n_fold spans, the error word
     issl::DevBuf text;                  // the pages' text, one behind the other, each at a multiple of 16
     uint64_t text_cap = 0, text_used = 0, text_bytes = 0; // bytes allocated / taken (padded) / of the pages' own text

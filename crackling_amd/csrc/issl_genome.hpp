@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -95,6 +96,59 @@ __device__ __forceinline__ int probe_key(const Probe &q, uint32_t nr, uint64_t k
     }
     return lo < nr && q.ukeys[lo] == key ? static_cast<int>(lo) : -1;
 }
+
+// ---- host: the preparation of one piece ---------------------------------------------------------------------------
+
+// reserve() takes the sections of n <= kPieceSites queries in the caller's arena, ahead of its one hipMalloc; enqueue()
+// puts the memsets and the launches on the caller's stream and waits nowhere.  Afterwards: `sorted` the n query words in
+// key order, `probe` what the scan of the text asks, qrank[i] the rank of query i's key, ctr 64 bytes of zeros for the
+// caller's counters.
+struct QueryPrep {
+    uint32_t n = 0, q_blocks = 0, map_bits = 0;
+    size_t o_wb = 0, o_hist = 0, o_first = 0, o_ukeys = 0, o_qrank = 0, o_map = 0, o_ctr = 0;
+    const uint64_t *sorted = nullptr;
+    Probe probe{};
+    uint32_t *qrank = nullptr;
+    unsigned long long *ctr = nullptr;
+
+    void reserve(Arena &a, uint32_t n_)
+    {
+        n = n_;
+        q_blocks = (n + 255) / 256;
+        map_bits = std::max(16u, bits_for(32ull * n)); // 32 .. 64 bits per query site
+        o_wb = a.reserve(8ull * n);
+        o_hist = a.reserve(4 * radix_hist_words(radix_sort_blocks(n)));
+        o_first = a.reserve(4 * scan_words(q_blocks + 1ull));
+        o_ukeys = a.reserve(8ull * n);
+        o_qrank = a.reserve(4ull * n);
+        o_map = a.reserve(size_t(1) << (map_bits - 3));
+        o_ctr = a.reserve(64);
+    }
+
+    // wa: room for the n words, the caller's.  The sort ends in wa or in the arena's buffer; with into_wa the words are
+    // copied to wa when it ended in the other one.
+    int enqueue(const Arena &a, const uint64_t *d_sites, uint64_t *wa, bool into_wa, hipStream_t stream)
+    {
+        uint64_t *wb = a.at<uint64_t>(o_wb), *ukeys = a.at<uint64_t>(o_ukeys);
+        uint32_t *first = a.at<uint32_t>(o_first), *bitmap = a.at<uint32_t>(o_map);
+        qrank = a.at<uint32_t>(o_qrank);
+        ctr = a.at<unsigned long long>(o_ctr);
+        HIP_TRY(hipMemsetAsync(bitmap, 0, size_t(1) << (map_bits - 3), stream));
+        HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
+        HIP_TRY(hipMemsetAsync(first + q_blocks, 0, 4, stream));
+        hipLaunchKernelGGL(k_query_words, dim3(q_blocks), dim3(256), 0, stream, d_sites, n, wa);
+        sorted = radix_sort_async(wa, wb, n, kPieceBits, kPieceBits + 41, a.at<uint32_t>(o_hist), stream);
+        if (into_wa && sorted != wa) {
+            HIP_TRY(hipMemcpyAsync(wa, sorted, 8ull * n, hipMemcpyDeviceToDevice, stream));
+            sorted = wa;
+        }
+        hipLaunchKernelGGL(k_query_heads, dim3(q_blocks), dim3(256), 0, stream, sorted, n, first);
+        launch_scan(first, q_blocks + 1ull, stream);
+        probe = Probe{ukeys, first + q_blocks, bitmap, 64 - map_bits};
+        hipLaunchKernelGGL(k_query_ranks, dim3(q_blocks), dim3(256), 0, stream, sorted, n, first, ukeys, qrank, bitmap, probe.hash_shift);
+        return ISSL_OK;
+    }
+};
 
 } // namespace
 } // namespace issl

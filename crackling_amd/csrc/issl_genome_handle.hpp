@@ -5,7 +5,7 @@
 #include <vector>
 
 #include "../../include/issl_hip.h"
-#include "issl_match.hpp"
+#include "issl_hiputil.hpp"
 
 struct issl_genome {
     int device = -1;

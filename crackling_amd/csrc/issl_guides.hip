@@ -333,15 +333,6 @@ __global__ __launch_bounds__(256) void k_guide_finish(const uint64_t *__restrict
     }
 }
 
-struct FileEvents {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~FileEvents()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-
 // counts[4 f ..]: matches, duplicates, second occurrences, first occurrences of input f (see "files" above).
 constexpr uint32_t kLdsFiles = 256;
 __global__ __launch_bounds__(256) void k_guide_files(const uint64_t *__restrict__ perm, const uint64_t *__restrict__ sorted_keys,
@@ -424,24 +415,6 @@ int append_guide_records(const char *data, size_t len, const std::string &what, 
     return ISSL_OK;
 }
 
-int read_file(const std::string &path, std::vector<char> &buf)
-{
-    struct stat st;
-    FILE *fp = ::stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode) ? std::fopen(path.c_str(), "rb") : nullptr;
-    if (!fp) {
-        set_error("cannot open '" + path + "'");
-        return ISSL_E_IO;
-    }
-    buf.resize(static_cast<size_t>(st.st_size));
-    const bool ok = buf.empty() || std::fread(buf.data(), buf.size(), 1, fp) == 1;
-    std::fclose(fp);
-    if (!ok) {
-        set_error("cannot read '" + path + "'");
-        return ISSL_E_IO;
-    }
-    return ISSL_OK;
-}
-
 // A lone directory stands for its files, top level only, in reverse sorted name order (ConfigManager.py:181-184).
 int expand_guide_inputs(const char *const *paths, int n, std::vector<std::string> &inputs)
 {
@@ -470,20 +443,11 @@ int expand_guide_inputs(const char *const *paths, int n, std::vector<std::string
 
 // ---- host: the device pass -----------------------------------------------------------------------------------------
 
-// The stream of one call: its work neither waits for nor holds up what the caller's process has on the default stream.
-struct OwnStream {
-    hipStream_t s = nullptr;
-    OwnStream() = default;
-    OwnStream(const OwnStream &) = delete;
-    OwnStream &operator=(const OwnStream &) = delete;
-    ~OwnStream() { if (s) (void)hipStreamDestroy(s); }
-};
-
 // text and its records -> the set on `device`.  parse_ms: the host pass, for the timing line.
 int extract_guides(const std::string &text, std::vector<FastaRecord> &records, std::vector<uint64_t> &file_starts, int device,
                    bool timing, double parse_ms, issl_guide_set **out)
 {
-    if (int rc = use_device(device)) return rc;
+    if (int rc = select_device(device, "the extraction")) return rc;
     const uint64_t len = text.size();
     if (len >> 41) {
         set_error("text of " + std::to_string(len) + " bytes: a guide's place holds positions below 2^41");
@@ -499,8 +463,8 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
     file_starts.push_back(len);
     g->file_counts.assign(4ull * n_files, 0u);
     const uint32_t n_records = static_cast<uint32_t>(records.size());
-    OwnStream own; // ahead of the arenas: they are released first
-    EX_HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    OwnedStream own; // ahead of the arenas: they are released first
+    HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
     hipStream_t stream = own.s;
     StageTimer clock(timing, stream);
     uint64_t n = 0;
@@ -513,7 +477,7 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
         const size_t o_seq = ta.reserve(len), o_starts = ta.reserve(8ull * n_records), o_ctr = ta.reserve(16),
                      o_cf = ta.reserve(4 * scan_words(blocks + 1ull)), o_cr = ta.reserve(4 * scan_words(blocks + 1ull)),
                      o_rf = ta.reserve(4 * (n_records + 1ull)), o_rr = ta.reserve(4 * (n_records + 1ull));
-        EX_HIP_TRY(hipMalloc(&ta.buf.p, ta.size));
+        HIP_TRY(hipMalloc(&ta.buf.p, ta.size));
         uint8_t *d_seq = ta.at<uint8_t>(o_seq);
         uint64_t *d_starts = ta.at<uint64_t>(o_starts);
         unsigned long long *d_ctr = ta.at<unsigned long long>(o_ctr);
@@ -521,17 +485,17 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
                  *rec_r = ta.at<uint32_t>(o_rr);
         std::vector<uint64_t> starts(n_records);
         for (uint32_t r = 0; r < n_records; ++r) starts[r] = records[r].start;
-        EX_HIP_TRY(hipMemcpyAsync(d_seq, text.data(), len, hipMemcpyHostToDevice, stream));
-        EX_HIP_TRY(hipMemcpyAsync(d_starts, starts.data(), 8ull * n_records, hipMemcpyHostToDevice, stream));
-        EX_HIP_TRY(hipMemsetAsync(d_ctr, 0, 16, stream));
-        EX_HIP_TRY(hipMemsetAsync(cnt_f + blocks, 0, 4, stream));
-        EX_HIP_TRY(hipMemsetAsync(cnt_r + blocks, 0, 4, stream));
+        HIP_TRY(hipMemcpyAsync(d_seq, text.data(), len, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_starts, starts.data(), 8ull * n_records, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(d_ctr, 0, 16, stream));
+        HIP_TRY(hipMemsetAsync(cnt_f + blocks, 0, 4, stream));
+        HIP_TRY(hipMemsetAsync(cnt_r + blocks, 0, 4, stream));
         clock.note("upload");
         // -- count
         hipLaunchKernelGGL(k_guide_count, dim3(blocks), dim3(256), 0, stream, d_seq, len, cnt_f, cnt_r, d_ctr);
-        EX_HIP_TRY(hipGetLastError()); // a launch that fails is reported as such, at its stage
-        EX_HIP_TRY(hipMemcpyAsync(ctr, d_ctr, 8, hipMemcpyDeviceToHost, stream));
-        EX_HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError()); // a launch that fails is reported as such, at its stage
+        HIP_TRY(hipMemcpyAsync(ctr, d_ctr, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         clock.note("count");
         n = ctr[0];
         if (n > 0xFFFFFFFFull) { // ordinals and the offsets of the radix passes are 32 bits (issl_radix.hpp)
@@ -545,19 +509,19 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
             launch_scan(cnt_r, blocks + 1ull, stream);
             hipLaunchKernelGGL(k_guide_bases, dim3(std::min<uint32_t>(n_records + 1u, 1u << 20)), dim3(256), 0, stream, d_seq, len,
                                d_starts, n_records, cnt_f, cnt_r, rec_f, rec_r);
-            EX_HIP_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             // -- emit
             Arena ma;
             const size_t o_keys = ma.reserve(8 * n), o_places = ma.reserve(8 * n), o_wa = ma.reserve(8 * n), o_wb = ma.reserve(8 * n),
                          o_hist = ma.reserve(4 * radix_hist_words(radix_sort_blocks(n))),
                          o_first = ma.reserve(4 * scan_words(n_blocks + 1ull));
-            EX_HIP_TRY(hipMalloc(&ma.buf.p, ma.size));
+            HIP_TRY(hipMalloc(&ma.buf.p, ma.size));
             uint64_t *keys = ma.at<uint64_t>(o_keys), *places = ma.at<uint64_t>(o_places), *wa = ma.at<uint64_t>(o_wa),
                      *wb = ma.at<uint64_t>(o_wb);
             uint32_t *hist = ma.at<uint32_t>(o_hist), *first = ma.at<uint32_t>(o_first);
             hipLaunchKernelGGL(k_guide_emit, dim3(blocks), dim3(256), 0, stream, d_seq, len, cnt_f, cnt_r, d_starts, n_records, rec_f,
                                rec_r, keys, places, wa, n32);
-            EX_HIP_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             clock.note("emit");
             // -- the permutation by guide, ordinals ascending inside a run
             uint64_t *low = radix_sort_async(wa, wb, n, 32, 64, hist, stream);
@@ -565,15 +529,15 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
             uint64_t *perm = radix_sort_async(low, low == wa ? wb : wa, n, 32, 48, hist, stream);
             uint64_t *sorted_keys = perm == wa ? wb : wa;
             hipLaunchKernelGGL(k_guide_gather, dim3(n_blocks), dim3(256), 0, stream, perm, n32, keys, sorted_keys);
-            EX_HIP_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             clock.note("sort");
             // -- runs
-            EX_HIP_TRY(hipMemsetAsync(first + n_blocks, 0, 4, stream));
+            HIP_TRY(hipMemsetAsync(first + n_blocks, 0, 4, stream));
             hipLaunchKernelGGL(k_guide_heads, dim3(n_blocks), dim3(256), 0, stream, sorted_keys, n32, first);
             launch_scan(first, n_blocks + 1ull, stream);
-            EX_HIP_TRY(hipGetLastError());
-            EX_HIP_TRY(hipMemcpyAsync(&n_runs, first + n_blocks, 4, hipMemcpyDeviceToHost, stream));
-            EX_HIP_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&n_runs, first + n_blocks, 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
             if (n_runs == 0 || n_runs > n32) {
                 set_error("guide collapse on the device: " + std::to_string(n_runs) + " distinct of " + std::to_string(n) + " matches");
                 return ISSL_E_DEVICE;
@@ -581,30 +545,29 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
             Arena ra;
             const size_t o_rs = ra.reserve(4 * (n_runs + 1ull)), o_ro = ra.reserve(4ull * n_runs), o_fs = ra.reserve(8ull * n_files),
                          o_fc = ra.reserve(16ull * n_files);
-            EX_HIP_TRY(hipMalloc(&ra.buf.p, ra.size));
-            EX_HIP_TRY(hipMalloc(&g->guides.p, 32ull * n_runs));
-            EX_HIP_TRY(hipMalloc(&g->sigs.p, 8ull * n_runs));
+            HIP_TRY(hipMalloc(&ra.buf.p, ra.size));
+            HIP_TRY(hipMalloc(&g->guides.p, 32ull * n_runs));
+            HIP_TRY(hipMalloc(&g->sigs.p, 8ull * n_runs));
             uint32_t *run_start = ra.at<uint32_t>(o_rs), *run_ord = ra.at<uint32_t>(o_ro);
             hipLaunchKernelGGL(k_guide_ranks, dim3(n_blocks), dim3(256), 0, stream, sorted_keys, perm, n32, first, n_runs, run_start,
                                run_ord);
             // -- per input, while the runs are there (in the arena of the runs: no allocation of its own)
-            EX_HIP_TRY(hipMemcpyAsync(ra.at<uint64_t>(o_fs), file_starts.data(), 8ull * n_files, hipMemcpyHostToDevice, stream));
-            EX_HIP_TRY(hipMemsetAsync(ra.at<uint32_t>(o_fc), 0, 16ull * n_files, stream));
-            FileEvents fe;
+            HIP_TRY(hipMemcpyAsync(ra.at<uint64_t>(o_fs), file_starts.data(), 8ull * n_files, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemsetAsync(ra.at<uint32_t>(o_fc), 0, 16ull * n_files, stream));
+            Events<2> fe;
             if (timing) { // the kernel alone by HIP events, for the timing line
-                EX_HIP_TRY(hipEventCreate(&fe.a));
-                EX_HIP_TRY(hipEventCreate(&fe.b));
-                EX_HIP_TRY(hipEventRecord(fe.a, stream));
+                if (int rc = fe.create()) return rc;
+                HIP_TRY(hipEventRecord(fe.e[0], stream));
             }
             hipLaunchKernelGGL(k_guide_files, dim3(n_blocks), dim3(256), 0, stream, perm, sorted_keys, places, n32, ra.at<uint64_t>(o_fs),
                                n_files, ra.at<uint32_t>(o_fc));
-            if (timing) EX_HIP_TRY(hipEventRecord(fe.b, stream));
-            EX_HIP_TRY(hipMemcpyAsync(g->file_counts.data(), ra.at<uint32_t>(o_fc), 16ull * n_files, hipMemcpyDeviceToHost, stream));
-            EX_HIP_TRY(hipGetLastError());
+            if (timing) HIP_TRY(hipEventRecord(fe.e[1], stream));
+            HIP_TRY(hipMemcpyAsync(g->file_counts.data(), ra.at<uint32_t>(o_fc), 16ull * n_files, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipGetLastError());
             clock.note("files");
             if (timing) {
                 float ms = 0;
-                EX_HIP_TRY(hipEventElapsedTime(&ms, fe.a, fe.b)); // (note() synchronised the stream)
+                HIP_TRY(hipEventElapsedTime(&ms, fe.e[0], fe.e[1])); // (note() synchronised the stream)
                 char buf[64];
                 std::snprintf(buf, sizeof buf, " (k_guide_files %.4f ms by events)", ms);
                 clock.line += buf;
@@ -612,11 +575,11 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
             // perm and sorted_keys are read no more: the run words and the scratch of their sort take the two buffers
             const dim3 run_grid((n_runs + 255) / 256);
             hipLaunchKernelGGL(k_guide_runs, run_grid, dim3(256), 0, stream, run_start, run_ord, n_runs, wa);
-            EX_HIP_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             clock.note("runs");
             // -- first-seen order
             const uint64_t *runs = radix_sort_async(wa, wb, n_runs, 32, 64, hist, stream);
-            EX_HIP_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             clock.note("order");
             // -- finish
             ulonglong2 *d_guides = static_cast<ulonglong2 *>(g->guides.p);
@@ -627,9 +590,9 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
             else
                 hipLaunchKernelGGL(k_guide_finish<false>, run_grid, dim3(256), 0, stream, runs, n_runs, keys, places, n32, d_starts, n_records,
                                    d_guides, d_sigs, d_ctr + 1);
-            EX_HIP_TRY(hipGetLastError());
-            EX_HIP_TRY(hipMemcpyAsync(ctr + 1, d_ctr + 1, 8, hipMemcpyDeviceToHost, stream));
-            EX_HIP_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(ctr + 1, d_ctr + 1, 8, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
             clock.note("finish");
         }
     }
@@ -647,8 +610,8 @@ int extract_guides(const std::string &text, std::vector<FastaRecord> &records, s
 
 int copy_guides(const issl_guide_set *g, issl_guide *out)
 {
-    EX_HIP_TRY(hipSetDevice(g->device));
-    EX_HIP_TRY(hipMemcpy(out, g->guides.p, 32 * g->n_guides, hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipMemcpy(out, g->guides.p, 32 * g->n_guides, hipMemcpyDeviceToHost));
     return ISSL_OK;
 }
 
@@ -666,18 +629,12 @@ extern "C" {
 int issl_guides_extract(const char *const *files, const size_t *lens, int n_files, int device, issl_guide_set **out)
 {
     if (out) *out = nullptr;
-    if (!files || !lens || n_files <= 0 || !out) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!files || !lens || n_files <= 0 || !out) return issl::fail(ISSL_E_ARG, "null argument");
     for (int f = 0; f < n_files; ++f)
-        if (!files[f] && lens[f]) {
-            issl::set_error("null argument");
-            return ISSL_E_ARG;
-        }
+        if (!files[f] && lens[f]) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
         const bool timing = issl::timing_wanted();
-        const double t0 = issl::StageTimer::now_ms();
+        const double t0 = issl::now_ms();
         std::string text;
         std::vector<issl::FastaRecord> records;
         std::unordered_set<std::string> recorded;
@@ -686,25 +643,19 @@ int issl_guides_extract(const char *const *files, const size_t *lens, int n_file
             file_starts.push_back(text.size());
             if (int rc = issl::append_guide_records(files[f], lens[f], "input " + std::to_string(f), recorded, text, records)) return rc;
         }
-        return issl::extract_guides(text, records, file_starts, device, timing, issl::StageTimer::now_ms() - t0, out);
+        return issl::extract_guides(text, records, file_starts, device, timing, issl::now_ms() - t0, out);
     });
 }
 
 int issl_guides_extract_files(const char *const *paths, int n_paths, int device, issl_guide_set **out)
 {
     if (out) *out = nullptr;
-    if (!paths || n_paths <= 0 || !out) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!paths || n_paths <= 0 || !out) return issl::fail(ISSL_E_ARG, "null argument");
     for (int f = 0; f < n_paths; ++f)
-        if (!paths[f]) {
-            issl::set_error("null argument");
-            return ISSL_E_ARG;
-        }
+        if (!paths[f]) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
         const bool timing = issl::timing_wanted();
-        const double t0 = issl::StageTimer::now_ms();
+        const double t0 = issl::now_ms();
         std::vector<std::string> inputs;
         if (int rc = issl::expand_guide_inputs(paths, n_paths, inputs)) return rc;
         std::string text;
@@ -714,20 +665,17 @@ int issl_guides_extract_files(const char *const *paths, int n_paths, int device,
         std::vector<uint64_t> file_starts;
         for (const auto &path : inputs) {
             file_starts.push_back(text.size());
-            if (int rc = issl::read_file(path, buf)) return rc;
+            if (int rc = issl::read_whole_file(path.c_str(), buf)) return rc;
             if (int rc = issl::append_guide_records(buf.data(), buf.size(), "'" + path + "'", recorded, text, records)) return rc;
         }
         buf = std::vector<char>();
-        return issl::extract_guides(text, records, file_starts, device, timing, issl::StageTimer::now_ms() - t0, out);
+        return issl::extract_guides(text, records, file_starts, device, timing, issl::now_ms() - t0, out);
     });
 }
 
 int issl_guides_info(const issl_guide_set *g, uint64_t *n_guides, uint64_t *n_unique, uint64_t *n_matches, uint64_t *n_records)
 {
-    if (!g || !n_guides || !n_unique || !n_matches || !n_records) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || !n_guides || !n_unique || !n_matches || !n_records) return issl::fail(ISSL_E_ARG, "null argument");
     *n_guides = g->n_guides;
     *n_unique = g->n_unique;
     *n_matches = g->n_matches;
@@ -737,10 +685,7 @@ int issl_guides_info(const issl_guide_set *g, uint64_t *n_guides, uint64_t *n_un
 
 int issl_guides_record(const issl_guide_set *g, uint64_t r, const char **name, size_t *name_len, uint64_t *length)
 {
-    if (!g || !name || !name_len || !length) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || !name || !name_len || !length) return issl::fail(ISSL_E_ARG, "null argument");
     if (r >= g->records.size()) {
         issl::set_error("record out of range");
         return ISSL_E_ARG;
@@ -753,20 +698,14 @@ int issl_guides_record(const issl_guide_set *g, uint64_t r, const char **name, s
 
 int issl_guides_files(const issl_guide_set *g, uint64_t *n_files)
 {
-    if (!g || !n_files) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || !n_files) return issl::fail(ISSL_E_ARG, "null argument");
     *n_files = g->file_counts.size() / 4;
     return ISSL_OK;
 }
 
 int issl_guides_file_counts(const issl_guide_set *g, uint64_t file, issl_guides_file *out)
 {
-    if (!g || !out) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || !out) return issl::fail(ISSL_E_ARG, "null argument");
     if (file >= g->file_counts.size() / 4) {
         issl::set_error("input " + std::to_string(file) + " of " + std::to_string(g->file_counts.size() / 4));
         return ISSL_E_ARG;
@@ -778,10 +717,7 @@ int issl_guides_file_counts(const issl_guide_set *g, uint64_t file, issl_guides_
 
 int issl_guides_copy(const issl_guide_set *g, issl_guide *out, size_t cap)
 {
-    if (!g || (!out && g->n_guides)) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || (!out && g->n_guides)) return issl::fail(ISSL_E_ARG, "null argument");
     if (cap < g->n_guides) {
         issl::set_error("room for " + std::to_string(cap) + " guides, the set has " + std::to_string(g->n_guides));
         return ISSL_E_ARG;
@@ -792,10 +728,7 @@ int issl_guides_copy(const issl_guide_set *g, issl_guide *out, size_t cap)
 
 int issl_guides_device(const issl_guide_set *g, const issl_guide **d_guides, const uint64_t **d_sigs)
 {
-    if (!g || !d_guides || !d_sigs) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || !d_guides || !d_sigs) return issl::fail(ISSL_E_ARG, "null argument");
     *d_guides = static_cast<const issl_guide *>(g->guides.p);
     *d_sigs = static_cast<const uint64_t *>(g->sigs.p);
     return ISSL_OK;

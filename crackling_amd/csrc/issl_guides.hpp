@@ -4,7 +4,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "issl_match.hpp"
+#include "issl_hiputil.hpp"
 
 struct issl_guide_set {
     int device = -1;

@@ -1,6 +1,7 @@
 // Host-side ISSL index: .issl parsing/validation, index construction, geometry helpers.
 // Product code (no oracle involved).  Reference paths are relative to /root/reference.
 #pragma once
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -22,6 +23,13 @@ void set_error(const char *msg) noexcept; // (a message there is no memory for i
 const char *get_error();
 // set_error(msg), then rc.
 int fail(int rc, const char *msg) noexcept;
+
+// The steady clock in milliseconds: the library's one wall clock, and that of the executables that time themselves.
+inline double now_ms()
+{
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
 
 // The guard of every extern "C" entry point that allocates or calls into the library: the C ABI never throws
 // (include/issl_hip.h), so what the C++ underneath throws comes back as an error code -- no memory, or no thread to be
@@ -46,6 +54,14 @@ struct ThreadGroup {
     template <class... A> void add(A &&...a) { threads.emplace_back(std::forward<A>(a)...); }
     void join() { for (auto &t : threads) if (t.joinable()) t.join(); }
     ~ThreadGroup() { join(); }
+};
+
+// One surviving record of the text append_records builds (issl_match.hpp): where its sequence starts in seq, how many characters it
+// has (0 for a header without sequence) and its header line without '>' and line end, as the bytes stand in the file
+// (empty for text ahead of the first header).  Records are listed in the order they are joined, starts ascending.
+struct FastaRecord {
+    uint64_t start, length;
+    std::string name;
 };
 
 // Geometry of an index (header fields + derived values).

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "issl_device.hpp"
+#include "issl_hiputil.hpp"
 
 namespace issl {
 
@@ -72,15 +73,6 @@ struct issl_index {
     int proven_dist = -1;
 };
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            issl::set_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr);    \
-            return ISSL_E_DEVICE;                                                                  \
-        }                                                                                          \
-    } while (0)
-
 namespace issl {
 
 // ---- issl_upload.cpp: the HBM image -----------------------------------------------------------
@@ -105,7 +97,6 @@ void release_device(issl_index *ix);
 
 // ---- issl_pipeline.cpp: scoring batches ------------------------------------------------------
 int supported_geometry(const Geometry &g);
-int select_device(int device);
 void release_lanes(issl_index *ix);
 inline uint32_t scan_waves(const Tuning &tn) { return tn.scan_blocks * 16u; }
 int ensure_workspace(issl_index *ix, size_t n, Lane &lane, uint32_t fine_ways = kFineWays);

@@ -24,7 +24,6 @@
 // locations (the capacity rule is the host's: nothing is launched when they do not fit) and for the end.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -224,38 +223,27 @@ int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t n_sites
     pc.n = n;
     StageTimer clock(g->timing, stream);
     // -- buffers whose size the query fixes
-    const uint32_t q_blocks = (n + 255) / 256, sort_blocks = radix_sort_blocks(n);
-    const uint32_t map_bits = std::max(16u, bits_for(32ull * n)); // 32 .. 64 bits per query site
     Arena &qa = pc.query;
-    const size_t o_wa = qa.reserve(8ull * n), o_wb = qa.reserve(8ull * n), o_hist = qa.reserve(4 * radix_hist_words(sort_blocks)),
-                 o_first = qa.reserve(4 * scan_words(q_blocks + 1ull)), o_ukeys = qa.reserve(8ull * n), o_qrank = qa.reserve(4ull * n),
-                 o_map = qa.reserve(size_t(1) << (map_bits - 3)), o_ctr = qa.reserve(64), o_rstart = qa.reserve(4ull * n),
-                 o_rend = qa.reserve(4ull * n), o_cnt = qa.reserve(4 * scan_words(n + 1ull));
-    EX_HIP_TRY(hipMalloc(&qa.buf.p, qa.size));
-    uint64_t *wa = qa.at<uint64_t>(o_wa), *wb = qa.at<uint64_t>(o_wb), *ukeys = qa.at<uint64_t>(o_ukeys);
-    uint32_t *hist = qa.at<uint32_t>(o_hist), *first = qa.at<uint32_t>(o_first), *qrank = qa.at<uint32_t>(o_qrank),
-             *bitmap = qa.at<uint32_t>(o_map), *rstart = qa.at<uint32_t>(o_rstart), *rend = qa.at<uint32_t>(o_rend),
-             *cnt = qa.at<uint32_t>(o_cnt);
-    unsigned long long *ctr = qa.at<unsigned long long>(o_ctr); // 0 hit words, 1 emit cursor, 2 matches, 3 passed, 4 locations
-    EX_HIP_TRY(hipMemsetAsync(bitmap, 0, size_t(1) << (map_bits - 3), stream));
-    EX_HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
-    EX_HIP_TRY(hipMemsetAsync(rstart, 0, static_cast<size_t>(o_cnt - o_rstart), stream)); // rstart and rend
-    EX_HIP_TRY(hipMemsetAsync(first + q_blocks, 0, 4, stream));
-    // -- query prep
-    hipLaunchKernelGGL(k_query_words, dim3(q_blocks), dim3(256), 0, stream, d_sites, n, wa);
-    const uint64_t *sorted = radix_sort_async(wa, wb, n, kPieceBits, kPieceBits + 41, hist, stream);
-    hipLaunchKernelGGL(k_query_heads, dim3(q_blocks), dim3(256), 0, stream, sorted, n, first);
-    launch_scan(first, q_blocks + 1ull, stream);
-    const Probe probe{ukeys, first + q_blocks, bitmap, 64 - map_bits};
-    hipLaunchKernelGGL(k_query_ranks, dim3(q_blocks), dim3(256), 0, stream, sorted, n, first, ukeys, qrank, bitmap, probe.hash_shift);
+    QueryPrep prep;
+    const size_t o_wa = qa.reserve(8ull * n);
+    prep.reserve(qa, n);
+    const size_t o_rstart = qa.reserve(4ull * n), o_rend = qa.reserve(4ull * n), o_cnt = qa.reserve(4 * scan_words(n + 1ull));
+    HIP_TRY(hipMalloc(&qa.buf.p, qa.size));
+    uint32_t *rstart = qa.at<uint32_t>(o_rstart), *rend = qa.at<uint32_t>(o_rend), *cnt = qa.at<uint32_t>(o_cnt);
+    HIP_TRY(hipMemsetAsync(rstart, 0, static_cast<size_t>(o_cnt - o_rstart), stream)); // rstart and rend
+    // -- query prep: the sorted words are read where the sort left them
+    if (int rc = prep.enqueue(qa, d_sites, qa.at<uint64_t>(o_wa), false, stream)) return rc;
+    const Probe &probe = prep.probe;
+    uint32_t *qrank = prep.qrank;
+    unsigned long long *ctr = prep.ctr; // 0 hit words, 1 emit cursor, 2 matches, 3 passed, 4 locations
     clock.note("prep");
     // -- count
     const uint8_t *d_seq = static_cast<const uint8_t *>(g->seq.p);
     const uint32_t blocks = static_cast<uint32_t>((g->len + kPosPerBlock - 1) / kPosPerBlock);
     hipLaunchKernelGGL(k_locate_count, dim3(blocks), dim3(256), 0, stream, d_seq, g->len, probe, ctr);
     unsigned long long seen[4] = {};
-    EX_HIP_TRY(hipMemcpyAsync(seen, ctr, sizeof seen, hipMemcpyDeviceToHost, stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpyAsync(seen, ctr, sizeof seen, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     clock.note("count");
     const uint64_t n_words = seen[0];
     if (n_words > 0xFFFFFFFFull) { // the radix passes count and place with 32-bit offsets (issl_radix.hpp)
@@ -269,7 +257,7 @@ int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t n_sites
         Arena &ha = pc.hit;
         const size_t o_ha = ha.reserve(8 * n_words), o_hb = ha.reserve(8 * n_words),
                      o_hh = ha.reserve(4 * radix_hist_words(radix_sort_blocks(n_words)));
-        EX_HIP_TRY(hipMalloc(&ha.buf.p, ha.size));
+        HIP_TRY(hipMalloc(&ha.buf.p, ha.size));
         uint64_t *ha_w = ha.at<uint64_t>(o_ha), *hb_w = ha.at<uint64_t>(o_hb);
         hipLaunchKernelGGL(k_locate_emit, dim3(blocks), dim3(256), 0, stream, d_seq, g->len, probe, g->pos_bits, ctr + 1, ha_w,
                            n_words);
@@ -284,8 +272,8 @@ int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t n_sites
     launch_scan(cnt, n + 1ull, stream);
     hipLaunchKernelGGL(k_write_offsets, dim3(n / 256 + 1), dim3(256), 0, stream, cnt, n + 1, base, d_offsets);
     unsigned long long total = 0;
-    EX_HIP_TRY(hipMemcpyAsync(&total, ctr + 4, 8, hipMemcpyDeviceToHost, stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpyAsync(&total, ctr + 4, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     clock.note("offsets");
     if (g->timing)
         std::fprintf(stderr, "[issl locate] %u sites:%s | matches %llu filter passed %llu hits %llu locations %llu\n", n,
@@ -316,8 +304,8 @@ int locate_finish(const issl_genome *g, const Piece &pc, issl_location *d_locs, 
     else
         hipLaunchKernelGGL(k_locate_finish<false>, grid, dim3(256), 0, stream, pc.words, pc.offs, pc.n, total, pc.qrank, pc.rstart,
                            starts, n_records, g->pos_bits, out);
-    EX_HIP_TRY(hipGetLastError());
-    EX_HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     clock.note("finish");
     if (g->timing) std::fprintf(stderr, "[issl locate]%s\n", clock.line.c_str());
     return ISSL_OK;
@@ -329,11 +317,11 @@ bool nothing_to_find(const issl_genome *g, size_t n) { return n == 0 || g->len <
 int locate_device(issl_genome *g, const uint64_t *d_sites, size_t n, uint64_t *d_offsets, issl_location *d_locs, size_t cap,
                   size_t *n_total, hipStream_t stream)
 {
-    EX_HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipSetDevice(g->device));
     *n_total = 0;
     if (nothing_to_find(g, n)) {
-        EX_HIP_TRY(hipMemsetAsync(d_offsets, 0, 8 * (n + 1), stream));
-        EX_HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8 * (n + 1), stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         return ISSL_OK;
     }
     // Counting pass over the pieces; a single piece is finished from what that pass left, several are run once more.
@@ -365,7 +353,7 @@ int locate_device(issl_genome *g, const uint64_t *d_sites, size_t n, uint64_t *d
 
 int locate_host(issl_genome *g, const uint64_t *sites, size_t n, uint64_t *offsets, issl_location *locs, size_t cap, size_t *n_total)
 {
-    EX_HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipSetDevice(g->device));
     *n_total = 0;
     if (nothing_to_find(g, n)) {
         std::memset(offsets, 0, 8 * (n + 1));
@@ -374,25 +362,25 @@ int locate_host(issl_genome *g, const uint64_t *sites, size_t n, uint64_t *offse
     // At most one piece of sites, offsets and locations is on the device at a time.
     const size_t piece = std::min(kPieceSites, n);
     DevBuf d_sites, d_offs, d_locs;
-    EX_HIP_TRY(hipMalloc(&d_sites.p, 8 * piece));
-    EX_HIP_TRY(hipMalloc(&d_offs.p, 8 * (piece + 1)));
+    HIP_TRY(hipMalloc(&d_sites.p, 8 * piece));
+    HIP_TRY(hipMalloc(&d_offs.p, 8 * (piece + 1)));
     uint64_t total = 0;
     for (int pass = 0; pass < 2; ++pass) {
         uint64_t base = 0;
         for (size_t at = 0; at < n; at += kPieceSites) {
             const size_t cnt = std::min(kPieceSites, n - at);
             Piece pc;
-            EX_HIP_TRY(hipMemcpy(d_sites.p, sites + at, 8 * cnt, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_sites.p, sites + at, 8 * cnt, hipMemcpyHostToDevice));
             if (int rc = locate_prepare(g, static_cast<const uint64_t *>(d_sites.p), cnt, base, static_cast<uint64_t *>(d_offs.p),
                                         nullptr, pc))
                 return rc;
-            if (pass == 0) EX_HIP_TRY(hipMemcpy(offsets + at, d_offs.p, 8 * (cnt + 1), hipMemcpyDeviceToHost));
+            if (pass == 0) HIP_TRY(hipMemcpy(offsets + at, d_offs.p, 8 * (cnt + 1), hipMemcpyDeviceToHost));
             // pass 1 (several pieces, everything fits), or the one piece of a call at once
             if ((pass == 1 || (n <= kPieceSites && locs && base + pc.total <= cap)) && pc.total) {
                 d_locs.release();
-                EX_HIP_TRY(hipMalloc(&d_locs.p, 16 * pc.total));
+                HIP_TRY(hipMalloc(&d_locs.p, 16 * pc.total));
                 if (int rc = locate_finish(g, pc, static_cast<issl_location *>(d_locs.p), nullptr)) return rc;
-                EX_HIP_TRY(hipMemcpy(locs + base, d_locs.p, 16 * pc.total, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(locs + base, d_locs.p, 16 * pc.total, hipMemcpyDeviceToHost));
             }
             base += pc.total;
             if (base > 0xFFFFFFFFull) {
@@ -410,7 +398,7 @@ int locate_host(issl_genome *g, const uint64_t *sites, size_t n, uint64_t *offse
 // seq and its records -> the handle on `device`.
 int open_genome(std::string &seq, std::vector<FastaRecord> &records, int device, issl_genome **out)
 {
-    if (int rc = use_device(device)) return rc;
+    if (int rc = select_device(device, "the extraction")) return rc;
     if (seq.size() >> 41) {
         set_error("genome text of " + std::to_string(seq.size()) + " bytes: a locate word holds positions below 2^41");
         return ISSL_E_UNSUPPORTED;
@@ -431,12 +419,12 @@ int open_genome(std::string &seq, std::vector<FastaRecord> &records, int device,
         g->n_bases += records[r].length;
     }
     if (g->len) {
-        EX_HIP_TRY(hipMalloc(&g->seq.p, g->len));
-        EX_HIP_TRY(hipMemcpy(g->seq.p, seq.data(), g->len, hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&g->seq.p, g->len));
+        HIP_TRY(hipMemcpy(g->seq.p, seq.data(), g->len, hipMemcpyHostToDevice));
     }
     if (!starts.empty()) {
-        EX_HIP_TRY(hipMalloc(&g->starts.p, 8 * starts.size()));
-        EX_HIP_TRY(hipMemcpy(g->starts.p, starts.data(), 8 * starts.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&g->starts.p, 8 * starts.size()));
+        HIP_TRY(hipMemcpy(g->starts.p, starts.data(), 8 * starts.size(), hipMemcpyHostToDevice));
     }
     g->records = std::move(records);
     *out = g.release();
@@ -451,15 +439,9 @@ extern "C" {
 int issl_genome_open(const char *const *files, const size_t *lens, int n_files, int device, issl_genome **out)
 {
     if (out) *out = nullptr;
-    if (!files || !lens || n_files <= 0 || !out) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!files || !lens || n_files <= 0 || !out) return issl::fail(ISSL_E_ARG, "null argument");
     for (int f = 0; f < n_files; ++f)
-        if (!files[f] && lens[f]) {
-            issl::set_error("null argument");
-            return ISSL_E_ARG;
-        }
+        if (!files[f] && lens[f]) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] {
         std::string seq;
         std::vector<issl::FastaRecord> records;
@@ -471,15 +453,9 @@ int issl_genome_open(const char *const *files, const size_t *lens, int n_files, 
 int issl_genome_open_files(const char *const *paths, int n_paths, int device, issl_genome **out)
 {
     if (out) *out = nullptr;
-    if (!paths || n_paths <= 0 || !out) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!paths || n_paths <= 0 || !out) return issl::fail(ISSL_E_ARG, "null argument");
     for (int f = 0; f < n_paths; ++f)
-        if (!paths[f]) {
-            issl::set_error("null argument");
-            return ISSL_E_ARG;
-        }
+        if (!paths[f]) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
         const std::vector<std::string> inputs = expand_fasta_inputs(std::vector<std::string>(paths, paths + n_paths));
         if (inputs.empty()) {
@@ -497,10 +473,7 @@ int issl_genome_open_files(const char *const *paths, int n_paths, int device, is
 
 int issl_genome_info(const issl_genome *g, uint64_t *n_records, uint64_t *n_bases)
 {
-    if (!g || !n_records || !n_bases) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || !n_records || !n_bases) return issl::fail(ISSL_E_ARG, "null argument");
     *n_records = g->records.size();
     *n_bases = g->n_bases;
     return ISSL_OK;
@@ -508,10 +481,7 @@ int issl_genome_info(const issl_genome *g, uint64_t *n_records, uint64_t *n_base
 
 int issl_genome_record(const issl_genome *g, uint64_t r, const char **name, size_t *name_len, uint64_t *length)
 {
-    if (!g || !name || !name_len || !length) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || !name || !name_len || !length) return issl::fail(ISSL_E_ARG, "null argument");
     if (r >= g->records.size()) {
         issl::set_error("record out of range");
         return ISSL_E_ARG;
@@ -525,20 +495,14 @@ int issl_genome_record(const issl_genome *g, uint64_t r, const char **name, size
 int issl_genome_locate(issl_genome *g, const uint64_t *sites, size_t n, uint64_t *offsets, issl_location *locs, size_t cap,
                        size_t *n_total)
 {
-    if (!g || (!sites && n) || !offsets || !n_total || (!locs && cap)) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || (!sites && n) || !offsets || !n_total || (!locs && cap)) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] { return issl::locate_host(g, sites, n, offsets, locs, cap, n_total); });
 }
 
 int issl_genome_locate_device(issl_genome *g, const uint64_t *d_sites, size_t n, uint64_t *d_offsets, issl_location *d_locs,
                               size_t cap, size_t *n_total, void *stream)
 {
-    if (!g || (!d_sites && n) || !d_offsets || !n_total || (!d_locs && cap)) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || (!d_sites && n) || !d_offsets || !n_total || (!d_locs && cap)) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call(
         [&] { return issl::locate_device(g, d_sites, n, d_offsets, d_locs, cap, n_total, static_cast<hipStream_t>(stream)); });
 }

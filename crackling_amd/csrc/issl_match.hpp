@@ -1,29 +1,20 @@
 // What the units that read genome text share (issl_extract.hip: site extraction and genome -> index; issl_locate.hip:
-// resident genome and locate; issl_guides.hip: candidate guides): the pattern test of extractOfftargets.py:23-24 on the device, the LSD radix sort of 64-bit
-// words, the FASTA -> record text pass of the host and the small helpers around device memory.  Kernels and device
-// functions live in an anonymous namespace, one copy per translation unit, like issl_radix.hpp.
+// resident genome and locate; issl_guides.hip: candidate guides): the pattern test of extractOfftargets.py:23-24 on the
+// device, the LSD radix sort of 64-bit words and the FASTA -> record text pass of the host.  Kernels and device functions
+// live in an anonymous namespace, one copy per translation unit, like issl_radix.hpp.  The host plumbing around a launch
+// (HIP_TRY, DevBuf, Arena, StageTimer, select_device) is issl_hiputil.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdint>
-#include <cstdio>
 #include <string>
 #include <utility>
 #include <vector>
 
-#include "issl_host.hpp"
+#include "issl_hiputil.hpp"
 #include "issl_radix.hpp"
 
 namespace issl {
-
-// One surviving record of the text append_records builds: where its sequence starts in seq, how many characters it
-// has (0 for a header without sequence) and its header line without '>' and line end, as the bytes stand in the file
-// (empty for text ahead of the first header).  Records are listed in the order they are joined, starts ascending.
-struct FastaRecord {
-    uint64_t start, length;
-    std::string name;
-};
 
 // FASTA bytes -> upper-cased sequence text appended to seq, '\n' after every record (issl_extract.hip).  per_file: the
 // reference's rules for several inputs.  records (optional): the record table of what was appended; seq is the same
@@ -31,29 +22,8 @@ struct FastaRecord {
 void append_records(const char *fasta, size_t len, bool per_file, std::string &seq, std::vector<FastaRecord> *records = nullptr);
 // The FASTA files at paths[0..n) -> seq: the explode rules for one input, the per-file rules for several.
 int read_fasta_files(const char *const *paths, int n, std::string &seq, std::vector<FastaRecord> *records = nullptr);
-// Select `device`: ISSL_E_DEVICE when there is none (no CPU fallback), ISSL_E_ARG when it is out of range.
-int use_device(int device);
-
-// Device buffers are released on every path out of the functions that hold them.
-struct DevBuf {
-    void *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
 
 namespace {
-
-#define EX_HIP_TRY(expr)                                                                           \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr);          \
-            return ISSL_E_DEVICE;                                                                  \
-        }                                                                                          \
-    } while (0)
 
 constexpr uint32_t kPosPerBlock = 4096; // text positions per 256-thread workgroup
 
@@ -107,39 +77,6 @@ template <class T> __device__ __forceinline__ uint32_t last_not_above(const T *t
     return lo ? lo - 1 : 0;
 }
 
-// Stage times of one call on one stream, for the stderr line of ISSL_LOCATE_TIMING / ISSL_GUIDES_TIMING: the stream is
-// synchronised at every note(); when it is off, note() does nothing and the call waits nowhere for the clock.
-struct StageTimer {
-    bool on;
-    hipStream_t stream;
-    double t0 = 0;
-    std::string line;
-    static double now_ms()
-    {
-        using namespace std::chrono;
-        return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-    }
-    StageTimer(bool on_, hipStream_t s) : on(on_), stream(s) { if (on) { (void)hipStreamSynchronize(stream); t0 = now_ms(); } }
-    void note(const char *stage)
-    {
-        if (!on) return;
-        (void)hipStreamSynchronize(stream);
-        const double t = now_ms();
-        char buf[64];
-        std::snprintf(buf, sizeof buf, " %s %.3f ms", stage, t - t0);
-        line += buf;
-        t0 = t;
-    }
-};
-
-// Sections of one allocation, 256-byte aligned.
-struct Arena {
-    DevBuf buf;
-    size_t size = 0;
-    size_t reserve(size_t bytes) { const size_t at = size; size = (size + bytes + 255) & ~size_t(255); return at; }
-    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(static_cast<char *>(buf.p) + off); }
-};
-
 inline uint32_t bits_for(uint64_t values) // bits that hold 0 .. values - 1
 {
     uint32_t b = 1;
@@ -172,14 +109,14 @@ inline int radix_sort(uint64_t *d_keys, uint64_t *d_tmp, uint64_t n, uint32_t bi
 {
     if (n < 2) return ISSL_OK;
     DevBuf hist;
-    EX_HIP_TRY(hipMalloc(&hist.p, 4ull * radix_hist_words(radix_sort_blocks(n))));
+    HIP_TRY(hipMalloc(&hist.p, 4ull * radix_hist_words(radix_sort_blocks(n))));
     uint64_t *src = radix_sort_async(d_keys, d_tmp, n, 0, bits, static_cast<uint32_t *>(hist.p), nullptr);
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         set_error(std::string("HIP error in radix sort: ") + hipGetErrorString(e));
         return ISSL_E_DEVICE;
     }
-    if (src != d_keys) EX_HIP_TRY(hipMemcpy(d_keys, src, 8 * n, hipMemcpyDeviceToDevice));
+    if (src != d_keys) HIP_TRY(hipMemcpy(d_keys, src, 8 * n, hipMemcpyDeviceToDevice));
     return ISSL_OK;
 }
 

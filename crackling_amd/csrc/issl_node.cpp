@@ -5,7 +5,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <dlfcn.h>
 #include <set>
@@ -14,16 +13,11 @@
 #include <vector>
 
 #include "issl_device.hpp"
+#include "issl_hiputil.hpp"
 
 using namespace issl;
 
 namespace {
-
-double now_ms()
-{
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 // RCCL is loaded on demand so that libissl_hip.so has no link-time dependency on it (a process that already
 // holds an RCCL -- e.g. PyTorch's -- is reused through the common SONAME).
@@ -72,15 +66,6 @@ struct issl_node {
     issl_node_info info{};
 };
 
-#define NODE_HIP_TRY(expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr);          \
-            return ISSL_E_DEVICE;                                                                  \
-        }                                                                                          \
-    } while (0)
-
 // Move the image of devices[0] to every other device.  Returns ISSL_OK and sets *used_rccl.
 static int broadcast_image(issl_node *nd, size_t bytes, int *used_rccl)
 {
@@ -128,10 +113,10 @@ static int broadcast_image(issl_node *nd, size_t bytes, int *used_rccl)
         // fall through to peer copies; the message is informational only
     }
     for (int i = 1; i < n; ++i) {
-        NODE_HIP_TRY(hipMemcpyPeer(nd->images[i], nd->devices[i], nd->images[0], nd->devices[0], bytes));
+        HIP_TRY(hipMemcpyPeer(nd->images[i], nd->devices[i], nd->images[0], nd->devices[0], bytes));
     }
-    NODE_HIP_TRY(hipSetDevice(nd->devices[0]));
-    NODE_HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipSetDevice(nd->devices[0]));
+    HIP_TRY(hipDeviceSynchronize());
     return ISSL_OK;
 }
 
@@ -154,13 +139,10 @@ int issl_node_close(issl_node *nd)
 
 int issl_node_create(issl_index *idx, const int *devices, int n_devices, issl_node **out)
 {
-    if (!idx || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!idx || !out) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&]() -> int {
         int visible = 0;
-        if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0) {
-            set_error("no HIP device available: the ISSL scorer has no CPU fallback");
-            return ISSL_E_DEVICE;
-        }
+        if (int rc = count_devices("the ISSL scorer", &visible)) return rc;
         issl_node *nd = new (std::nothrow) issl_node();
         if (!nd) { set_error("out of memory"); return ISSL_E_NOMEM; }
         if (!devices || n_devices <= 0) {
@@ -227,7 +209,7 @@ int issl_node_create(issl_index *idx, const int *devices, int n_devices, issl_no
 int issl_node_score(issl_node *nd, const uint64_t *guides, size_t n, int max_dist, double threshold, int method,
                     double *mit, double *cfd)
 {
-    if (!nd || (n && (!guides || !mit || !cfd))) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!nd || (n && (!guides || !mit || !cfd))) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&]() -> int {
         const size_t world = nd->replicas.size();
         const double t0 = now_ms();
@@ -276,7 +258,7 @@ int issl_node_score(issl_node *nd, const uint64_t *guides, size_t n, int max_dis
 
 int issl_node_shard_times(const issl_node *nd, double *busy_ms, uint64_t *guides, int n)
 {
-    if (!nd || !busy_ms || !guides) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!nd || !busy_ms || !guides) return issl::fail(ISSL_E_ARG, "null argument");
     if (n < static_cast<int>(nd->replicas.size())) { set_error("buffer too small"); return ISSL_E_ARG; }
     for (size_t r = 0; r < nd->replicas.size(); ++r) { busy_ms[r] = nd->busy_ms[r]; guides[r] = nd->guides_done[r]; }
     return ISSL_OK;
@@ -284,7 +266,7 @@ int issl_node_shard_times(const issl_node *nd, double *busy_ms, uint64_t *guides
 
 int issl_node_get_info(const issl_node *nd, issl_node_info *out)
 {
-    if (!nd || !out) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!nd || !out) return issl::fail(ISSL_E_ARG, "null argument");
     *out = nd->info;
     return ISSL_OK;
 }

@@ -358,49 +358,37 @@ int occur_piece(const issl_genome *g, const uint64_t *d_all, size_t at, size_t n
 {
     const uint32_t n = static_cast<uint32_t>(n_piece);
     StageTimer clock(g->timing, stream);
-    const uint32_t q_blocks = (n + 255) / 256, sort_blocks = radix_sort_blocks(n);
-    const uint32_t map_bits = std::max(16u, bits_for(32ull * n)); // 32 .. 64 bits per query site
+    const uint32_t q_blocks = (n + 255) / 256;
     Arena qa;
-    const size_t o_wb = qa.reserve(8ull * n), o_hist = qa.reserve(4 * radix_hist_words(sort_blocks)),
-                 o_first = qa.reserve(4 * scan_words(q_blocks + 1ull)), o_ukeys = qa.reserve(8ull * n), o_qrank = qa.reserve(4ull * n),
-                 o_map = qa.reserve(size_t(1) << (map_bits - 3)), o_ctr = qa.reserve(64), o_flags = qa.reserve(4ull * n),
-                 o_total = qa.reserve(8ull * n), o_min = qa.reserve(8ull * n);
-    EX_HIP_TRY(hipMalloc(&qa.buf.p, qa.size));
-    uint64_t *wa = sorted_all + at, *wb = qa.at<uint64_t>(o_wb), *ukeys = qa.at<uint64_t>(o_ukeys);
-    uint32_t *hist = qa.at<uint32_t>(o_hist), *first = qa.at<uint32_t>(o_first), *qrank = qa.at<uint32_t>(o_qrank),
-             *bitmap = qa.at<uint32_t>(o_map);
-    unsigned long long *ctr = qa.at<unsigned long long>(o_ctr); // 0 occurrences, 1 matches, 2 passed
+    QueryPrep prep;
+    prep.reserve(qa, n);
+    const size_t o_flags = qa.reserve(4ull * n), o_total = qa.reserve(8ull * n), o_min = qa.reserve(8ull * n);
+    HIP_TRY(hipMalloc(&qa.buf.p, qa.size));
     const Ranks st{qa.at<uint32_t>(o_flags), qa.at<unsigned long long>(o_total), qa.at<unsigned long long>(o_min)};
-    EX_HIP_TRY(hipMemsetAsync(bitmap, 0, size_t(1) << (map_bits - 3), stream));
-    EX_HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
-    EX_HIP_TRY(hipMemsetAsync(st.flags, 0, o_min - o_flags, stream)); // flags and total
-    EX_HIP_TRY(hipMemsetAsync(st.first, 0xFF, 8ull * n, stream));
-    EX_HIP_TRY(hipMemsetAsync(first + q_blocks, 0, 4, stream));
-    // -- query prep
-    hipLaunchKernelGGL(k_query_words, dim3(q_blocks), dim3(256), 0, stream, d_all + at, n, wa);
-    const uint64_t *sorted = radix_sort_async(wa, wb, n, kPieceBits, kPieceBits + 41, hist, stream);
-    if (sorted != wa) EX_HIP_TRY(hipMemcpyAsync(wa, sorted, 8ull * n, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(k_query_heads, dim3(q_blocks), dim3(256), 0, stream, wa, n, first);
-    launch_scan(first, q_blocks + 1ull, stream);
-    const Probe probe{ukeys, first + q_blocks, bitmap, 64 - map_bits};
-    hipLaunchKernelGGL(k_query_ranks, dim3(q_blocks), dim3(256), 0, stream, wa, n, first, ukeys, qrank, bitmap, probe.hash_shift);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(st.flags, 0, o_min - o_flags, stream)); // flags and total
+    HIP_TRY(hipMemsetAsync(st.first, 0xFF, 8ull * n, stream));
+    // -- query prep: the sorted words stay in sorted_all[at ..] for the verdicts
+    if (int rc = prep.enqueue(qa, d_all + at, sorted_all + at, true, stream)) return rc;
+    const Probe &probe = prep.probe;
+    uint32_t *qrank = prep.qrank;
+    unsigned long long *ctr = prep.ctr; // 0 occurrences, 1 matches, 2 passed
+    HIP_TRY(hipGetLastError());
     clock.note("prep");
     // -- scan
     const uint32_t blocks = g->len < 23 ? 0u : static_cast<uint32_t>((g->len + kPosPerBlock - 1) / kPosPerBlock);
     if (blocks) {
         hipLaunchKernelGGL(k_occur_scan, dim3(blocks), dim3(256), 0, stream, static_cast<const uint8_t *>(g->seq.p), g->len, probe,
                            st, ctr);
-        EX_HIP_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     clock.note("scan");
     // -- rows
     hipLaunchKernelGGL(k_occur_rows, dim3(q_blocks), dim3(256), 0, stream, qrank, n, st, reinterpret_cast<ulonglong2 *>(d_rows + at),
                        own_all + at);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     unsigned long long seen[3] = {};
-    if (g->timing) EX_HIP_TRY(hipMemcpyAsync(seen, ctr, sizeof seen, hipMemcpyDeviceToHost, stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream)); // the piece's buffers are released on return
+    if (g->timing) HIP_TRY(hipMemcpyAsync(seen, ctr, sizeof seen, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // the piece's buffers are released on return
     clock.note("rows");
     if (g->timing)
         std::fprintf(stderr, "[issl occurrences] %u sites:%s | matches %llu filter passed %llu occurrences %llu\n", n,
@@ -419,7 +407,7 @@ struct PageSpec {
 int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const PageSpec &pages, issl_occurrence *d_rows,
                        hipStream_t stream)
 {
-    EX_HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipSetDevice(g->device));
     if (n == 0 && !(pages.d_starts && pages.n_pages)) return ISSL_OK;
     if (n >= 0xFFFFFFFFull) { // a row names its source in 32 bits
         set_error("more than 2^32 - 2 sites in one call: split the query at a page boundary");
@@ -434,21 +422,21 @@ int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const 
     const bool events = pages.d_events && pages.d_starts;
     const size_t o_named = all.reserve(events ? 8 * n : 0), o_named_tmp = all.reserve(events ? 8 * n : 0),
                  o_named_hist = all.reserve(events ? 4 * radix_hist_words(radix_sort_blocks(n)) : 0);
-    EX_HIP_TRY(hipMalloc(&all.buf.p, all.size));
-    if (events && pages.n_pages) EX_HIP_TRY(hipMemsetAsync(pages.d_events, 0, 4 * pages.n_pages, stream));
+    HIP_TRY(hipMalloc(&all.buf.p, all.size));
+    if (events && pages.n_pages) HIP_TRY(hipMemsetAsync(pages.d_events, 0, 4 * pages.n_pages, stream));
     uint64_t *sorted_all = all.at<uint64_t>(o_sorted);
     unsigned long long *own_all = all.at<unsigned long long>(o_own);
     uint32_t *src = all.at<uint32_t>(o_src), *bad = all.at<uint32_t>(o_bad); // bad[0]: signatures, bad[1]: boundaries
     const uint32_t blocks = static_cast<uint32_t>((n + 255) / 256);
-    EX_HIP_TRY(hipMemsetAsync(bad, 0, 8, stream));
+    HIP_TRY(hipMemsetAsync(bad, 0, 8, stream));
     if (n) hipLaunchKernelGGL(k_occur_check, dim3(blocks), dim3(256), 0, stream, d_sites, static_cast<uint64_t>(n), bad);
     if (pages.d_starts)
         hipLaunchKernelGGL(k_occur_pages_check, dim3(static_cast<uint32_t>(pages.n_pages / 256 + 1)), dim3(256), 0, stream,
                            pages.d_starts, static_cast<uint64_t>(pages.n_pages), static_cast<uint64_t>(n), bad + 1);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     uint32_t is_bad[2] = {};
-    EX_HIP_TRY(hipMemcpyAsync(is_bad, bad, 8, hipMemcpyDeviceToHost, stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpyAsync(is_bad, bad, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     if (is_bad[0]) {
         set_error("a signature carries bits above its 20 bases");
         return ISSL_E_ARG;
@@ -463,14 +451,14 @@ int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const 
         if (int rc = occur_piece(g, d_sites, at, std::min(kPieceSites, n - at), sorted_all, own_all, d_rows, stream)) return rc;
     // -- verdicts
     StageTimer clock(g->timing, stream);
-    EX_HIP_TRY(hipMemsetAsync(src, 0, 4 * n, stream));
+    HIP_TRY(hipMemsetAsync(src, 0, 4 * n, stream));
     const Pages pg{sorted_all, n, pages.d_starts ? 0 : pages.page_length};
     if (pages.d_starts)
         hipLaunchKernelGGL(k_occur_target_paged, dim3(blocks), dim3(256), 0, stream, d_sites, own_all, pg, pages.d_starts,
                            static_cast<uint64_t>(pages.n_pages), src, events ? all.at<uint64_t>(o_named) : nullptr);
     else
         hipLaunchKernelGGL(k_occur_target, dim3(blocks), dim3(256), 0, stream, d_sites, own_all, pg, src);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const uint64_t *starts = static_cast<const uint64_t *>(g->starts.p);
     const uint32_t n_records = static_cast<uint32_t>(g->records.size());
     if (n_records <= kLdsRecords)
@@ -479,30 +467,26 @@ int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const 
     else
         hipLaunchKernelGGL(k_occur_verdict<false>, dim3(blocks), dim3(256), 0, stream, own_all, src, static_cast<uint64_t>(n), starts,
                            n_records, reinterpret_cast<ulonglong2 *>(d_rows));
-    EX_HIP_TRY(hipGetLastError());
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    HIP_TRY(hipGetLastError());
+    Events<2> ev;
     if (events) { // (the words lie in group order: a stable sort on the named query alone)
         clock.note("verdicts");
         if (g->timing) { // the sort and the count by HIP events, for the timing line
-            EX_HIP_TRY(hipEventCreate(&ev_a));
-            EX_HIP_TRY(hipEventCreate(&ev_b));
-            EX_HIP_TRY(hipEventRecord(ev_a, stream));
+            if (int rc = ev.create()) return rc;
+            HIP_TRY(hipEventRecord(ev.e[0], stream));
         }
         const uint64_t *named = radix_sort_async(all.at<uint64_t>(o_named), all.at<uint64_t>(o_named_tmp), n, 32, 64,
                                                  all.at<uint32_t>(o_named_hist), stream);
         hipLaunchKernelGGL(k_occur_events, dim3(blocks), dim3(256), 0, stream, named, own_all, static_cast<uint64_t>(n), pages.d_starts,
                            static_cast<uint64_t>(pages.n_pages), pages.d_events);
-        EX_HIP_TRY(hipGetLastError());
-        if (ev_b) EX_HIP_TRY(hipEventRecord(ev_b, stream));
+        HIP_TRY(hipGetLastError());
+        if (ev.e[1]) HIP_TRY(hipEventRecord(ev.e[1], stream));
     }
-    EX_HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     clock.note(events ? "events" : "verdicts");
-    if (ev_b) {
+    if (ev.e[1]) {
         float ms = 0;
-        const hipError_t e = hipEventElapsedTime(&ms, ev_a, ev_b);
-        (void)hipEventDestroy(ev_a);
-        (void)hipEventDestroy(ev_b);
-        EX_HIP_TRY(e);
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
         char buf[64];
         std::snprintf(buf, sizeof buf, " (sort and k_occur_events %.4f ms by events)", ms);
         clock.line += buf;
@@ -514,24 +498,24 @@ int occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, const 
 // pages.d_starts: HOST memory here.
 int occurrences_host(issl_genome *g, const uint64_t *sites, size_t n, PageSpec pages, issl_occurrence *rows)
 {
-    EX_HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipSetDevice(g->device));
     if (n == 0 && !(pages.d_starts && pages.n_pages)) return ISSL_OK;
     // a page may run over several pieces and its verdicts are looked up in all of them: all queries at once
     DevBuf d_sites, d_rows, d_starts;
     if (n) {
-        EX_HIP_TRY(hipMalloc(&d_sites.p, 8 * n));
-        EX_HIP_TRY(hipMalloc(&d_rows.p, sizeof(issl_occurrence) * n));
-        EX_HIP_TRY(hipMemcpy(d_sites.p, sites, 8 * n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&d_sites.p, 8 * n));
+        HIP_TRY(hipMalloc(&d_rows.p, sizeof(issl_occurrence) * n));
+        HIP_TRY(hipMemcpy(d_sites.p, sites, 8 * n, hipMemcpyHostToDevice));
     }
     if (pages.d_starts) {
-        EX_HIP_TRY(hipMalloc(&d_starts.p, 8 * (pages.n_pages + 1)));
-        EX_HIP_TRY(hipMemcpy(d_starts.p, pages.d_starts, 8 * (pages.n_pages + 1), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&d_starts.p, 8 * (pages.n_pages + 1)));
+        HIP_TRY(hipMemcpy(d_starts.p, pages.d_starts, 8 * (pages.n_pages + 1), hipMemcpyHostToDevice));
         pages.d_starts = static_cast<const uint64_t *>(d_starts.p);
     }
     if (int rc = occurrences_device(g, static_cast<const uint64_t *>(d_sites.p), n, pages, static_cast<issl_occurrence *>(d_rows.p),
                                     nullptr))
         return rc;
-    if (n) EX_HIP_TRY(hipMemcpy(rows, d_rows.p, sizeof(issl_occurrence) * n, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(rows, d_rows.p, sizeof(issl_occurrence) * n, hipMemcpyDeviceToHost));
     return ISSL_OK;
 }
 
@@ -542,20 +526,14 @@ extern "C" {
 
 int issl_genome_occurrences(issl_genome *g, const uint64_t *sites, size_t n, size_t page_length, issl_occurrence *rows)
 {
-    if (!g || (n && (!sites || !rows))) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || (n && (!sites || !rows))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] { return issl::occurrences_host(g, sites, n, issl::PageSpec{page_length, nullptr, 0}, rows); });
 }
 
 int issl_genome_occurrences_device(issl_genome *g, const uint64_t *d_sites, size_t n, size_t page_length, issl_occurrence *d_rows,
                                    void *stream)
 {
-    if (!g || (n && (!d_sites || !d_rows))) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || (n && (!d_sites || !d_rows))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] {
         return issl::occurrences_device(g, d_sites, n, issl::PageSpec{page_length, nullptr, 0}, d_rows, static_cast<hipStream_t>(stream));
     });
@@ -564,20 +542,14 @@ int issl_genome_occurrences_device(issl_genome *g, const uint64_t *d_sites, size
 int issl_genome_occurrences_paged(issl_genome *g, const uint64_t *sites, size_t n, const uint64_t *page_starts, size_t n_pages,
                                   issl_occurrence *rows)
 {
-    if (!g || (n && (!sites || !rows)) || (!page_starts && (n || n_pages))) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || (n && (!sites || !rows)) || (!page_starts && (n || n_pages))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] { return issl::occurrences_host(g, sites, n, issl::PageSpec{0, page_starts, n_pages}, rows); });
 }
 
 int issl_genome_occurrences_paged_device(issl_genome *g, const uint64_t *d_sites, size_t n, const uint64_t *d_page_starts,
                                          size_t n_pages, issl_occurrence *d_rows, void *stream)
 {
-    if (!g || (n && (!d_sites || !d_rows)) || (!d_page_starts && (n || n_pages))) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || (n && (!d_sites || !d_rows)) || (!d_page_starts && (n || n_pages))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] {
         return issl::occurrences_device(g, d_sites, n, issl::PageSpec{0, d_page_starts, n_pages}, d_rows,
                                         static_cast<hipStream_t>(stream));
@@ -587,10 +559,8 @@ int issl_genome_occurrences_paged_device(issl_genome *g, const uint64_t *d_sites
 int issl_genome_occurrences_paged_events_device(issl_genome *g, const uint64_t *d_sites, size_t n, const uint64_t *d_page_starts,
                                                 size_t n_pages, issl_occurrence *d_rows, uint32_t *d_page_events, void *stream)
 {
-    if (!g || (n && (!d_sites || !d_rows)) || (!d_page_starts && (n || n_pages)) || (!d_page_events && n_pages)) {
-        issl::set_error("null argument");
-        return ISSL_E_ARG;
-    }
+    if (!g || (n && (!d_sites || !d_rows)) || (!d_page_starts && (n || n_pages)) || (!d_page_events && n_pages))
+        return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] {
         return issl::occurrences_device(g, d_sites, n, issl::PageSpec{0, d_page_starts, n_pages, d_page_events}, d_rows,
                                         static_cast<hipStream_t>(stream));

@@ -22,22 +22,6 @@ int supported_geometry(const Geometry &g)
     return ISSL_E_UNSUPPORTED;
 }
 
-int select_device(int device)
-{
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count <= 0) {
-        set_error("no HIP device available: the ISSL scorer has no CPU fallback");
-        return ISSL_E_DEVICE;
-    }
-    if (device < 0 || device >= count) {
-        set_error("device " + std::to_string(device) + " out of range (" + std::to_string(count) + " visible)");
-        return ISSL_E_ARG;
-    }
-    HIP_TRY(hipSetDevice(device));
-    return ISSL_OK;
-}
-
 static void free_workspace(Workspace &w)
 {
     void *ptrs[] = {w.ng, w.gfill, w.gstart, w.gword, w.gidx, w.gbucket, w.gsig, w.items, w.plan, w.range_start, w.counters, w.scan_count, w.scan_span, w.sticky, w.stamps, w.gcur_big, w.gcur_big2, w.terms, w.sorted, w.gcount,
@@ -682,20 +666,17 @@ int dump_hits(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, d
 // ---- off-target report ------------------------------------------------------------------------
 // A device buffer of the call (the piece's profiles, the piece's records): grown, never shrunk, freed at the end.
 namespace {
-struct CallBuffer {
-    void *p = nullptr;
+struct CallBuffer : DevBuf {
     size_t bytes = 0;
     int reserve(size_t want)
     {
         if (want <= bytes) return ISSL_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
+        release();
         bytes = 0;
         HIP_TRY(hipMalloc(&p, want));
         bytes = want;
         return ISSL_OK;
     }
-    ~CallBuffer() { if (p) (void)hipFree(p); }
 };
 } // namespace
 

@@ -17,7 +17,6 @@
 #include "issl_genome_handle.hpp"
 #include "issl_guides.hpp"
 #include "issl_host.hpp"
-#include "issl_match.hpp"
 #include "issl_results.hpp"
 #include "issl_results_text.hpp"
 
@@ -30,12 +29,6 @@ struct issl_results {
 
 namespace issl {
 namespace {
-
-// Events around the launches of one build, destroyed with the scope.
-struct Events {
-    hipEvent_t e[5] = {};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 struct Inputs {
     const issl_guide_set *gs;
@@ -120,17 +113,17 @@ int prepare_text(const Inputs &in, ResultPool &pool, std::vector<issl_text_span>
 template <class T> int upload(DevBuf &buf, const std::vector<T> &v, hipStream_t stream)
 {
     if (v.empty()) return ISSL_OK;
-    EX_HIP_TRY(hipMalloc(&buf.p, sizeof(T) * v.size()));
-    EX_HIP_TRY(hipMemcpyAsync(buf.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMalloc(&buf.p, sizeof(T) * v.size()));
+    HIP_TRY(hipMemcpyAsync(buf.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, stream));
     return ISSL_OK;
 }
 
 int invert(DevBuf &buf, const uint32_t *d_list, uint64_t n_list, uint32_t n, hipStream_t stream)
 {
-    EX_HIP_TRY(hipMalloc(&buf.p, 4ull * n));
-    EX_HIP_TRY(hipMemsetAsync(buf.p, 0xFF, 4ull * n, stream));
+    HIP_TRY(hipMalloc(&buf.p, 4ull * n));
+    HIP_TRY(hipMemsetAsync(buf.p, 0xFF, 4ull * n, stream));
     launch_results_invert(d_list, static_cast<uint32_t>(n_list), static_cast<uint32_t *>(buf.p), n, stream);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return ISSL_OK;
 }
 
@@ -141,20 +134,20 @@ int results_build(const Inputs &in, issl_results **out)
     if (int rc = prepare_text(in, pool, headers, ss, chr)) return rc;
     const std::string header_row = (in.cfg->flags & ISSL_RESULTS_NO_HEADER) ? std::string() : results_header_row(in.cfg->delimiter);
 
-    if (int rc = use_device(in.gs->device)) return rc;
+    if (int rc = select_device(in.gs->device, "the extraction")) return rc;
     std::unique_ptr<issl_results> r(new issl_results());
     r->device = in.gs->device;
     r->n_rows = in.n_rows;
     const uint32_t n_set = static_cast<uint32_t>(in.gs->n_guides); // (a set has at most 2^32 - 1 matches)
     const uint32_t n = static_cast<uint32_t>(in.n_rows);           // the rows of the text: [first_row, first_row + n) of the set
     hipStream_t stream = nullptr; // the null stream: behind whatever the caller's streams have enqueued for the inputs
-    EX_HIP_TRY(hipMalloc(&r->offsets.p, 8ull * (n + 1ull)));
+    HIP_TRY(hipMalloc(&r->offsets.p, 8ull * (n + 1ull)));
     if (n == 0) {
         r->n_bytes = header_row.size();
         const uint64_t first = header_row.size();
-        EX_HIP_TRY(hipMalloc(&r->text.p, ((r->n_bytes + 15) & ~15ull) + 16));
-        if (!header_row.empty()) EX_HIP_TRY(hipMemcpy(r->text.p, header_row.data(), header_row.size(), hipMemcpyHostToDevice));
-        EX_HIP_TRY(hipMemcpy(r->offsets.p, &first, 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&r->text.p, ((r->n_bytes + 15) & ~15ull) + 16));
+        if (!header_row.empty()) HIP_TRY(hipMemcpy(r->text.p, header_row.data(), header_row.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(r->offsets.p, &first, 8, hipMemcpyHostToDevice));
         *out = r.release();
         return ISSL_OK;
     }
@@ -162,11 +155,11 @@ int results_build(const Inputs &in, issl_results **out)
     DevBuf d_pool, d_headers, d_ss, d_chr, fold_of, sel_of, score_of, sums;
     const uint64_t pool_bytes = pool.fixed_len + pool.extra.size();
     if (pool_bytes) {
-        EX_HIP_TRY(hipMalloc(&d_pool.p, pool_bytes));
+        HIP_TRY(hipMalloc(&d_pool.p, pool_bytes));
         if (pool.fixed_len)
-            EX_HIP_TRY(hipMemcpyAsync(d_pool.p, in.ss_text, pool.fixed_len, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(d_pool.p, in.ss_text, pool.fixed_len, hipMemcpyHostToDevice, stream));
         if (!pool.extra.empty())
-            EX_HIP_TRY(hipMemcpyAsync(static_cast<char *>(d_pool.p) + pool.fixed_len, pool.extra.data(), pool.extra.size(),
+            HIP_TRY(hipMemcpyAsync(static_cast<char *>(d_pool.p) + pool.fixed_len, pool.extra.data(), pool.extra.size(),
                                       hipMemcpyHostToDevice, stream));
     }
     if (int rc = upload(d_headers, headers, stream)) return rc;
@@ -211,44 +204,44 @@ int results_build(const Inputs &in, issl_results **out)
 
     const uint32_t groups = result_groups(n);
     uint64_t *offsets = static_cast<uint64_t *>(r->offsets.p);
-    EX_HIP_TRY(hipMalloc(&sums.p, 8ull * (groups + 1ull)));
-    Events ev;
-    for (hipEvent_t &x : ev.e) EX_HIP_TRY(hipEventCreate(&x));
-    EX_HIP_TRY(hipEventRecord(ev.e[0], stream));
+    HIP_TRY(hipMalloc(&sums.p, 8ull * (groups + 1ull)));
+    Events<5> ev;
+    if (int rc = ev.create()) return rc;
+    HIP_TRY(hipEventRecord(ev.e[0], stream));
     launch_results_measure(a, offsets, static_cast<uint64_t *>(sums.p), stream);
-    EX_HIP_TRY(hipGetLastError());
-    EX_HIP_TRY(hipEventRecord(ev.e[1], stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[1], stream));
     launch_results_scan(static_cast<uint64_t *>(sums.p), groups, header_row.size(), offsets, n, stream);
-    EX_HIP_TRY(hipGetLastError());
-    EX_HIP_TRY(hipEventRecord(ev.e[2], stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[2], stream));
     uint64_t total = 0;
-    EX_HIP_TRY(hipMemcpyAsync(&total, static_cast<uint64_t *>(sums.p) + groups, 8, hipMemcpyDeviceToHost, stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpyAsync(&total, static_cast<uint64_t *>(sums.p) + groups, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     if (total < header_row.size() + 49ull * n) { // (a row is at least the 23-mer, 25 delimiters and the line end)
         set_error("the rows measure " + std::to_string(total) + " bytes for " + std::to_string(n) + " guides");
         return ISSL_E_DEVICE;
     }
     r->n_bytes = total;
-    EX_HIP_TRY(hipMalloc(&r->text.p, (total + 15) & ~15ull));
+    HIP_TRY(hipMalloc(&r->text.p, (total + 15) & ~15ull));
     if (!header_row.empty())
-        EX_HIP_TRY(hipMemcpyAsync(r->text.p, header_row.data(), header_row.size(), hipMemcpyHostToDevice, stream));
-    EX_HIP_TRY(hipEventRecord(ev.e[3], stream));
+        HIP_TRY(hipMemcpyAsync(r->text.p, header_row.data(), header_row.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(ev.e[3], stream));
     launch_results_emit(a, offsets, static_cast<const uint64_t *>(sums.p), static_cast<char *>(r->text.p),
                         (in.cfg->flags & ISSL_RESULTS_DIRECT) != 0, stream);
-    EX_HIP_TRY(hipGetLastError());
-    EX_HIP_TRY(hipEventRecord(ev.e[4], stream));
-    EX_HIP_TRY(hipStreamSynchronize(stream)); // (the tables above go with this scope)
-    EX_HIP_TRY(hipEventElapsedTime(&r->ms_measure, ev.e[0], ev.e[1]));
-    EX_HIP_TRY(hipEventElapsedTime(&r->ms_scan, ev.e[1], ev.e[2]));
-    EX_HIP_TRY(hipEventElapsedTime(&r->ms_emit, ev.e[3], ev.e[4]));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[4], stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // (the tables above go with this scope)
+    HIP_TRY(hipEventElapsedTime(&r->ms_measure, ev.e[0], ev.e[1]));
+    HIP_TRY(hipEventElapsedTime(&r->ms_scan, ev.e[1], ev.e[2]));
+    HIP_TRY(hipEventElapsedTime(&r->ms_emit, ev.e[3], ev.e[4]));
     *out = r.release();
     return ISSL_OK;
 }
 
 int results_copy(const issl_results *r, char *out)
 {
-    EX_HIP_TRY(hipSetDevice(r->device));
-    EX_HIP_TRY(hipMemcpy(out, r->text.p, r->n_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipMemcpy(out, r->text.p, r->n_bytes, hipMemcpyDeviceToHost));
     return ISSL_OK;
 }
 
@@ -431,10 +424,7 @@ int issl_repr_f64_device(const double *d_values, size_t n, char *d_text, uint32_
     if (n == 0) return ISSL_OK;
     return issl::abi_call([&]() -> int {
         int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-            issl::set_error("no HIP device available: the formatter has no CPU fallback");
-            return ISSL_E_DEVICE;
-        }
+        if (int rc = issl::count_devices("the formatter", &count)) return rc;
         issl::launch_repr(d_values, n, d_text, d_len, stream);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {

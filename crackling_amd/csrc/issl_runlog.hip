@@ -301,25 +301,7 @@ __global__ __launch_bounds__(kThreads) void k_runlog_scored(const uint32_t *__re
     t.flush(page_failed, 1, slot0 < n_pages_cap ? slot0 : 0);
 }
 
-struct OwnedStream {
-    hipStream_t s = nullptr;
-    OwnedStream() = default;
-    OwnedStream(const OwnedStream &) = delete;
-    OwnedStream &operator=(const OwnedStream &) = delete;
-    ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
-};
-
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-
 uint32_t chunks_of(uint64_t n) { return static_cast<uint32_t>((n + kChunk - 1) / kChunk); }
-uint32_t blocks_of(uint64_t n) { return static_cast<uint32_t>((n + kThreads - 1) / kThreads); }
 
 } // namespace
 } // namespace issl
@@ -355,7 +337,7 @@ int runlog_batches(const Inputs &in, issl_runlog **out)
         *out = r.release();
         return ISSL_OK;
     }
-    if (int rc = use_device(src.device)) return rc;
+    if (int rc = select_device(src.device, "the extraction")) return rc;
     const uint64_t batch = in.batch_size == 0 || in.batch_size >= n ? n : in.batch_size;
     const uint32_t n_batches = static_cast<uint32_t>((n + batch - 1) / batch);
     const uint32_t n_fold = static_cast<uint32_t>(src.n_fold), n_selected = static_cast<uint32_t>(src.n_selected), n_scored = in.n_scored;
@@ -367,29 +349,28 @@ int runlog_batches(const Inputs &in, issl_runlog **out)
     }
     const uint32_t fold_chunks = chunks_of(n_fold);
     OwnedStream stream;
-    EX_HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
     Arena work;
     const size_t o_pages = work.reserve(4 * scan_words(n_batches + 1ull)), o_missing = work.reserve(4 * scan_words(fold_chunks + 1ull));
-    EX_HIP_TRY(hipMalloc(&work.buf.p, work.size));
-    EX_HIP_TRY(hipMalloc(&r->batches.p, sizeof(issl_runlog_batch) * static_cast<size_t>(n_batches)));
-    EX_HIP_TRY(hipMalloc(&r->page_failed.p, 4 * page_cap));
+    HIP_TRY(hipMalloc(&work.buf.p, work.size));
+    HIP_TRY(hipMalloc(&r->batches.p, sizeof(issl_runlog_batch) * static_cast<size_t>(n_batches)));
+    HIP_TRY(hipMalloc(&r->page_failed.p, 4 * page_cap));
     uint32_t *pages = work.at<uint32_t>(o_pages), *missing = work.at<uint32_t>(o_missing);
     issl_runlog_batch *batches = static_cast<issl_runlog_batch *>(r->batches.p);
     uint32_t *counters = static_cast<uint32_t *>(r->batches.p), *page_failed = static_cast<uint32_t *>(r->page_failed.p);
     const uint64_t *codes = reinterpret_cast<const uint64_t *>(src.rows);
 
-    EventPair ev;
-    EX_HIP_TRY(hipEventCreate(&ev.a));
-    EX_HIP_TRY(hipEventCreate(&ev.b));
-    EX_HIP_TRY(hipEventRecord(ev.a, stream.s));
-    EX_HIP_TRY(hipMemsetAsync(r->batches.p, 0, sizeof(issl_runlog_batch) * static_cast<size_t>(n_batches), stream.s));
-    EX_HIP_TRY(hipMemsetAsync(r->page_failed.p, 0, 4 * page_cap, stream.s));
-    EX_HIP_TRY(hipMemsetAsync(pages + n_batches, 0, 4, stream.s));
-    EX_HIP_TRY(hipMemsetAsync(missing + fold_chunks, 0, 4, stream.s));
-    hipLaunchKernelGGL(k_runlog_edges, dim3(blocks_of(n_batches)), dim3(kThreads), 0, stream.s, n, batch, n_batches, src.fold_list, n_fold,
+    Events<2> ev;
+    if (int rc = ev.create()) return rc;
+    HIP_TRY(hipEventRecord(ev.e[0], stream.s));
+    HIP_TRY(hipMemsetAsync(r->batches.p, 0, sizeof(issl_runlog_batch) * static_cast<size_t>(n_batches), stream.s));
+    HIP_TRY(hipMemsetAsync(r->page_failed.p, 0, 4 * page_cap, stream.s));
+    HIP_TRY(hipMemsetAsync(pages + n_batches, 0, 4, stream.s));
+    HIP_TRY(hipMemsetAsync(missing + fold_chunks, 0, 4, stream.s));
+    hipLaunchKernelGGL(k_runlog_edges, dim3(blocks_for(n_batches, kThreads)), dim3(kThreads), 0, stream.s, n, batch, n_batches, src.fold_list, n_fold,
                        src.selection, n_selected, in.d_scored, n_scored, in.page_length, batches, pages);
     launch_scan(pages, n_batches + 1ull, stream.s);
-    hipLaunchKernelGGL(k_runlog_page_spans, dim3(blocks_of(n_batches)), dim3(kThreads), 0, stream.s, pages, n_batches, batches);
+    hipLaunchKernelGGL(k_runlog_page_spans, dim3(blocks_for(n_batches, kThreads)), dim3(kThreads), 0, stream.s, pages, n_batches, batches);
     hipLaunchKernelGGL(k_runlog_rows, dim3(chunks_of(n)), dim3(kThreads), 0, stream.s, codes, n, batch, src.consensus_n, counters);
     if (n_fold) {
         hipLaunchKernelGGL(k_runlog_folds, dim3(fold_chunks), dim3(kThreads), 0, stream.s, src.fold_list, n_fold, in.folds, codes, batch,
@@ -402,13 +383,13 @@ int runlog_batches(const Inputs &in, issl_runlog **out)
     if (n_scored)
         hipLaunchKernelGGL(k_runlog_scored, dim3(chunks_of(n_scored)), dim3(kThreads), 0, stream.s, in.d_scored, n_scored, in.d_mit,
                            in.d_cfd, in.rule, batch, in.page_length, batches, static_cast<uint32_t>(page_cap), page_failed);
-    EX_HIP_TRY(hipGetLastError());
-    EX_HIP_TRY(hipEventRecord(ev.b, stream.s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[1], stream.s));
     uint32_t totals[2] = {0, 0};
-    EX_HIP_TRY(hipMemcpyAsync(&totals[0], pages + n_batches, 4, hipMemcpyDeviceToHost, stream.s));
-    EX_HIP_TRY(hipMemcpyAsync(&totals[1], missing + fold_chunks, 4, hipMemcpyDeviceToHost, stream.s));
-    EX_HIP_TRY(hipStreamSynchronize(stream.s)); // the one wait: the counts are there
-    EX_HIP_TRY(hipEventElapsedTime(&r->ms, ev.a, ev.b));
+    HIP_TRY(hipMemcpyAsync(&totals[0], pages + n_batches, 4, hipMemcpyDeviceToHost, stream.s));
+    HIP_TRY(hipMemcpyAsync(&totals[1], missing + fold_chunks, 4, hipMemcpyDeviceToHost, stream.s));
+    HIP_TRY(hipStreamSynchronize(stream.s)); // the one wait: the counts are there
+    HIP_TRY(hipEventElapsedTime(&r->ms, ev.e[0], ev.e[1]));
     if (totals[0] > page_cap || totals[1] > n_fold) {
         set_error("log counts on the device: " + std::to_string(totals[0]) + " pages, at most " + std::to_string(page_cap) +
                   " expected; " + std::to_string(totals[1]) + " rows not found in a fold list of " + std::to_string(n_fold));
@@ -418,11 +399,11 @@ int runlog_batches(const Inputs &in, issl_runlog **out)
     r->n_pages = totals[0];
     r->n_not_found = totals[1];
     if (totals[1]) {
-        EX_HIP_TRY(hipMalloc(&r->not_found.p, 4ull * totals[1]));
+        HIP_TRY(hipMalloc(&r->not_found.p, 4ull * totals[1]));
         hipLaunchKernelGGL(k_runlog_not_found, dim3(fold_chunks), dim3(kThreads), 0, stream.s, src.fold_list, n_fold, in.folds, codes,
                            missing, totals[1], static_cast<uint32_t *>(r->not_found.p));
-        EX_HIP_TRY(hipGetLastError());
-        EX_HIP_TRY(hipStreamSynchronize(stream.s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream.s));
     }
     *out = r.release();
     return ISSL_OK;
@@ -430,11 +411,11 @@ int runlog_batches(const Inputs &in, issl_runlog **out)
 
 int runlog_copy(const issl_runlog *r, issl_runlog_batch *batches, uint32_t *page_failed, uint32_t *not_found)
 {
-    EX_HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipSetDevice(r->device));
     if (batches && r->n_batches)
-        EX_HIP_TRY(hipMemcpy(batches, r->batches.p, sizeof(issl_runlog_batch) * r->n_batches, hipMemcpyDeviceToHost));
-    if (page_failed && r->n_pages) EX_HIP_TRY(hipMemcpy(page_failed, r->page_failed.p, 4 * r->n_pages, hipMemcpyDeviceToHost));
-    if (not_found && r->n_not_found) EX_HIP_TRY(hipMemcpy(not_found, r->not_found.p, 4 * r->n_not_found, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(batches, r->batches.p, sizeof(issl_runlog_batch) * r->n_batches, hipMemcpyDeviceToHost));
+    if (page_failed && r->n_pages) HIP_TRY(hipMemcpy(page_failed, r->page_failed.p, 4 * r->n_pages, hipMemcpyDeviceToHost));
+    if (not_found && r->n_not_found) HIP_TRY(hipMemcpy(not_found, r->not_found.p, 4 * r->n_not_found, hipMemcpyDeviceToHost));
     return ISSL_OK;
 }
 

@@ -293,7 +293,7 @@ int issl_method_from_string(const char *s) { return method_from_string(s); }
 int issl_verdicts(const double *mit, const double *cfd, size_t n, double threshold, const char *method,
                   uint8_t *accepted)
 {
-    if (!method || (n && (!mit || !cfd || !accepted))) { set_error("null argument"); return ISSL_E_ARG; }
+    if (!method || (n && (!mit || !cfd || !accepted))) return issl::fail(ISSL_E_ARG, "null argument");
     return abi_call([&] {
         const int printed = method_from_string(method); // exact match, :121-143
         const bool has_mit = printed == ISSL_METHOD_MIT || printed == ISSL_METHOD_AND || printed == ISSL_METHOD_OR ||

@@ -27,6 +27,7 @@
 
 #include "issl_annotation.hpp"
 #include "issl_genome_handle.hpp"
+#include "issl_match.hpp"
 
 struct issl_annotation {
     int device = -1;
@@ -232,8 +233,8 @@ int build_device(issl_annotation *a, const AnnotationIntervals &iv)
 {
     const uint32_t m = static_cast<uint32_t>(iv.tr.size()), n_keys = 2 * m, n_seqs = static_cast<uint32_t>(a->t.seqs.size());
     hipStream_t stream = nullptr;
-    EX_HIP_TRY(hipMalloc(&a->seq_first.p, 4ull * (n_seqs + 1)));
-    EX_HIP_TRY(hipMemset(a->seq_first.p, 0, 4ull * (n_seqs + 1)));
+    HIP_TRY(hipMalloc(&a->seq_first.p, 4ull * (n_seqs + 1)));
+    HIP_TRY(hipMemset(a->seq_first.p, 0, 4ull * (n_seqs + 1)));
     if (m == 0) return ISSL_OK;
     // -- the distinct breakpoints
     const uint32_t blocks = (n_keys + 255) / 256, sort_blocks = radix_sort_blocks(n_keys);
@@ -241,68 +242,68 @@ int build_device(issl_annotation *a, const AnnotationIntervals &iv)
     const size_t o_keys = ar.reserve(8ull * n_keys), o_tmp = ar.reserve(8ull * n_keys), o_hist = ar.reserve(4 * radix_hist_words(sort_blocks)),
                  o_first = ar.reserve(4 * scan_words(blocks + 1ull)), o_lo = ar.reserve(8ull * m), o_hi = ar.reserve(8ull * m),
                  o_tr = ar.reserve(4ull * m), o_total = ar.reserve(8);
-    EX_HIP_TRY(hipMalloc(&ar.buf.p, ar.size));
+    HIP_TRY(hipMalloc(&ar.buf.p, ar.size));
     uint64_t *keys = ar.at<uint64_t>(o_keys), *tmp = ar.at<uint64_t>(o_tmp), *d_lo = ar.at<uint64_t>(o_lo), *d_hi = ar.at<uint64_t>(o_hi);
     uint32_t *hist = ar.at<uint32_t>(o_hist), *first = ar.at<uint32_t>(o_first), *d_tr = ar.at<uint32_t>(o_tr);
     unsigned long long *d_total = ar.at<unsigned long long>(o_total);
-    EX_HIP_TRY(hipMemcpy(d_lo, iv.lo.data(), 8ull * m, hipMemcpyHostToDevice));
-    EX_HIP_TRY(hipMemcpy(d_hi, iv.hi.data(), 8ull * m, hipMemcpyHostToDevice));
-    EX_HIP_TRY(hipMemcpy(d_tr, iv.tr.data(), 4ull * m, hipMemcpyHostToDevice));
-    EX_HIP_TRY(hipMemcpy(keys, d_lo, 8ull * m, hipMemcpyDeviceToDevice));
-    EX_HIP_TRY(hipMemcpy(keys + m, d_hi, 8ull * m, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(d_lo, iv.lo.data(), 8ull * m, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_hi, iv.hi.data(), 8ull * m, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_tr, iv.tr.data(), 4ull * m, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(keys, d_lo, 8ull * m, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(keys + m, d_hi, 8ull * m, hipMemcpyDeviceToDevice));
     const uint64_t *sorted = radix_sort_async(keys, tmp, n_keys, 0, kCoordBits + bits_for(std::max<uint64_t>(2, n_seqs)), hist, stream);
-    EX_HIP_TRY(hipMemsetAsync(first + blocks, 0, 4, stream));
+    HIP_TRY(hipMemsetAsync(first + blocks, 0, 4, stream));
     hipLaunchKernelGGL(k_tr_heads, dim3(blocks), dim3(256), 0, stream, sorted, n_keys, first);
     launch_scan(first, blocks + 1ull, stream);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     uint32_t n_bp = 0;
-    EX_HIP_TRY(hipMemcpy(&n_bp, first + blocks, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n_bp, first + blocks, 4, hipMemcpyDeviceToHost));
     a->n_bp = n_bp;
-    EX_HIP_TRY(hipMalloc(&a->bp.p, 8ull * n_bp));
+    HIP_TRY(hipMalloc(&a->bp.p, 8ull * n_bp));
     uint64_t *bp = static_cast<uint64_t *>(a->bp.p);
     hipLaunchKernelGGL(k_tr_unique, dim3(blocks), dim3(256), 0, stream, sorted, n_keys, first, bp);
     hipLaunchKernelGGL(k_tr_seq_first, dim3((n_seqs + 256) / 256), dim3(256), 0, stream, bp, n_bp, n_seqs,
                        static_cast<uint32_t *>(a->seq_first.p));
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     // -- cover lists: count, scan, fill
     const uint32_t iv_blocks = (m + 255) / 256, bp_blocks = (n_bp + 255) / 256;
     DevBuf cnt, cursor, list, genes;
-    EX_HIP_TRY(hipMalloc(&cnt.p, 4 * scan_words(n_bp + 1ull)));
-    EX_HIP_TRY(hipMalloc(&cursor.p, 4ull * n_bp));
-    EX_HIP_TRY(hipMemsetAsync(cnt.p, 0, 4ull * (n_bp + 1ull), stream));
-    EX_HIP_TRY(hipMemsetAsync(cursor.p, 0, 4ull * n_bp, stream));
-    EX_HIP_TRY(hipMemsetAsync(d_total, 0, 8, stream));
+    HIP_TRY(hipMalloc(&cnt.p, 4 * scan_words(n_bp + 1ull)));
+    HIP_TRY(hipMalloc(&cursor.p, 4ull * n_bp));
+    HIP_TRY(hipMemsetAsync(cnt.p, 0, 4ull * (n_bp + 1ull), stream));
+    HIP_TRY(hipMemsetAsync(cursor.p, 0, 4ull * n_bp, stream));
+    HIP_TRY(hipMemsetAsync(d_total, 0, 8, stream));
     uint32_t *d_cnt = static_cast<uint32_t *>(cnt.p);
     hipLaunchKernelGGL(k_tr_cover<false>, dim3(iv_blocks), dim3(256), 0, stream, d_lo, d_hi, d_tr, m, bp, n_bp, d_cnt, nullptr, nullptr,
                        d_total);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     unsigned long long total = 0;
-    EX_HIP_TRY(hipMemcpy(&total, d_total, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&total, d_total, 8, hipMemcpyDeviceToHost));
     if (total > 0xFFFFFFFFull) {
         set_error("cover lists of " + std::to_string(total) + " entries: more than 2^32 - 1");
         return ISSL_E_UNSUPPORTED;
     }
     launch_scan(d_cnt, n_bp + 1ull, stream);
-    EX_HIP_TRY(hipMalloc(&list.p, 4ull * std::max<unsigned long long>(total, 1)));
+    HIP_TRY(hipMalloc(&list.p, 4ull * std::max<unsigned long long>(total, 1)));
     hipLaunchKernelGGL(k_tr_cover<true>, dim3(iv_blocks), dim3(256), 0, stream, d_lo, d_hi, d_tr, m, bp, n_bp,
                        static_cast<uint32_t *>(cursor.p), d_cnt, static_cast<uint32_t *>(list.p), nullptr);
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     // -- answers
     const size_t n_tr = a->t.tr_gene.size(), n_genes = a->t.gene_count.size();
-    EX_HIP_TRY(hipMalloc(&genes.p, 4ull * (n_tr + n_genes + 1)));
+    HIP_TRY(hipMalloc(&genes.p, 4ull * (n_tr + n_genes + 1)));
     uint32_t *d_tr_gene = static_cast<uint32_t *>(genes.p), *d_gene_count = d_tr_gene + n_tr;
-    EX_HIP_TRY(hipMemcpy(d_tr_gene, a->t.tr_gene.data(), 4ull * n_tr, hipMemcpyHostToDevice));
-    if (n_genes) EX_HIP_TRY(hipMemcpy(d_gene_count, a->t.gene_count.data(), 4ull * n_genes, hipMemcpyHostToDevice));
-    EX_HIP_TRY(hipMalloc(&a->answers.p, 16ull * n_bp));
+    HIP_TRY(hipMemcpy(d_tr_gene, a->t.tr_gene.data(), 4ull * n_tr, hipMemcpyHostToDevice));
+    if (n_genes) HIP_TRY(hipMemcpy(d_gene_count, a->t.gene_count.data(), 4ull * n_genes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&a->answers.p, 16ull * n_bp));
     hipLaunchKernelGGL(k_tr_answers, dim3(bp_blocks), dim3(256), 0, stream, d_cnt, static_cast<const uint32_t *>(list.p), n_bp, d_tr_gene,
                        d_gene_count, static_cast<uint4 *>(a->answers.p));
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     // the segments between neighbouring breakpoints of a sequence
     std::vector<uint32_t> sf(n_seqs + 1);
-    EX_HIP_TRY(hipMemcpy(sf.data(), a->seq_first.p, 4ull * (n_seqs + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sf.data(), a->seq_first.p, 4ull * (n_seqs + 1), hipMemcpyDeviceToHost));
     for (uint32_t s = 0; s < n_seqs; ++s)
         if (sf[s + 1] > sf[s]) a->n_segments += sf[s + 1] - sf[s] - 1;
-    EX_HIP_TRY(hipDeviceSynchronize()); // the lists are released on return
+    HIP_TRY(hipDeviceSynchronize()); // the lists are released on return
     return ISSL_OK;
 }
 
@@ -311,22 +312,22 @@ int open_annotation(const char *gff, size_t len, int device, issl_annotation **o
     std::unique_ptr<issl_annotation> a(new issl_annotation());
     const char *timing = std::getenv("ISSL_ANNOTATION_TIMING");
     const bool timed = timing && timing[0] == '1';
-    const double t0 = StageTimer::now_ms();
+    const double t0 = now_ms();
     if (int rc = parse_annotation(gff, len, a->t)) return rc;
-    const double t1 = StageTimer::now_ms();
+    const double t1 = now_ms();
     AnnotationIntervals iv;
     if (int rc = annotation_intervals(a->t, iv)) return rc;
-    const double t2 = StageTimer::now_ms();
-    if (int rc = use_device(device)) return rc;
+    const double t2 = now_ms();
+    if (int rc = select_device(device, "the extraction")) return rc;
     a->device = device;
     a->n_exons = a->t.exons.size();
     std::vector<AnnotationExon>().swap(a->t.exons);
     for (size_t s = 0; s < a->t.seqs.size(); ++s) a->seq_index.emplace(a->t.seqs[s], static_cast<uint32_t>(s));
-    const double t3 = StageTimer::now_ms();
+    const double t3 = now_ms();
     if (int rc = build_device(a.get(), iv)) return rc; // ends in a synchronise
     if (timed)
         std::fprintf(stderr, "[issl annotation] parse %.3f ms intervals %.3f ms device build %.3f ms | %zu intervals %llu breakpoints\n", t1 - t0,
-                     t2 - t1, StageTimer::now_ms() - t3, iv.tr.size(), static_cast<unsigned long long>(a->n_bp));
+                     t2 - t1, now_ms() - t3, iv.tr.size(), static_cast<unsigned long long>(a->n_bp));
     *out = a.release();
     return ISSL_OK;
 }
@@ -339,7 +340,7 @@ View view_of(const issl_annotation *a)
 
 int hits_device(issl_annotation *a, const uint32_t *d_seq, const int64_t *d_start, size_t n, issl_transcript_hits *d_out, hipStream_t stream)
 {
-    EX_HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipSetDevice(a->device));
     if (n == 0) return ISSL_OK;
     const uint64_t blocks = (n + 255) / 256;
     if (blocks > 0x7FFFFFFFull) {
@@ -348,24 +349,24 @@ int hits_device(issl_annotation *a, const uint32_t *d_seq, const int64_t *d_star
     }
     hipLaunchKernelGGL(k_tr_hits, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, stream, view_of(a), d_seq,
                        reinterpret_cast<const long long *>(d_start), static_cast<uint64_t>(n), reinterpret_cast<uint4 *>(d_out));
-    EX_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return ISSL_OK;
 }
 
 int hits_host(issl_annotation *a, const uint32_t *seq, const int64_t *start, size_t n, issl_transcript_hits *out)
 {
-    EX_HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipSetDevice(a->device));
     if (n == 0) return ISSL_OK;
     DevBuf d_seq, d_start, d_out;
-    EX_HIP_TRY(hipMalloc(&d_seq.p, 4 * n));
-    EX_HIP_TRY(hipMalloc(&d_start.p, 8 * n));
-    EX_HIP_TRY(hipMalloc(&d_out.p, 16 * n));
-    EX_HIP_TRY(hipMemcpy(d_seq.p, seq, 4 * n, hipMemcpyHostToDevice));
-    EX_HIP_TRY(hipMemcpy(d_start.p, start, 8 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&d_seq.p, 4 * n));
+    HIP_TRY(hipMalloc(&d_start.p, 8 * n));
+    HIP_TRY(hipMalloc(&d_out.p, 16 * n));
+    HIP_TRY(hipMemcpy(d_seq.p, seq, 4 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_start.p, start, 8 * n, hipMemcpyHostToDevice));
     if (int rc = hits_device(a, static_cast<const uint32_t *>(d_seq.p), static_cast<const int64_t *>(d_start.p), n,
                              static_cast<issl_transcript_hits *>(d_out.p), nullptr))
         return rc;
-    EX_HIP_TRY(hipMemcpy(out, d_out.p, 16 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.p, 16 * n, hipMemcpyDeviceToHost));
     return ISSL_OK;
 }
 
@@ -373,7 +374,7 @@ int hits_host(issl_annotation *a, const uint32_t *seq, const int64_t *start, siz
 int hits_occurrences_device(issl_annotation *a, const issl_genome *g, const issl_occurrence *d_rows, size_t n, issl_transcript_hits *d_out,
                             hipStream_t stream)
 {
-    EX_HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipSetDevice(a->device));
     if (n == 0) return ISSL_OK;
     if (g->device != a->device) {
         set_error("the genome and the annotation live on different devices");
@@ -399,20 +400,14 @@ int hits_occurrences_device(issl_annotation *a, const issl_genome *g, const issl
     }
     rec_seq[n_records] = lookup("*");
     DevBuf d_rec_seq;
-    EX_HIP_TRY(hipMalloc(&d_rec_seq.p, 4 * rec_seq.size()));
-    EX_HIP_TRY(hipMemcpyAsync(d_rec_seq.p, rec_seq.data(), 4 * rec_seq.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMalloc(&d_rec_seq.p, 4 * rec_seq.size()));
+    HIP_TRY(hipMemcpyAsync(d_rec_seq.p, rec_seq.data(), 4 * rec_seq.size(), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_tr_hits_rows, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, stream, view_of(a),
                        reinterpret_cast<const ulonglong2 *>(d_rows), static_cast<uint64_t>(n), static_cast<const uint32_t *>(d_rec_seq.p),
                        static_cast<uint32_t>(n_records), reinterpret_cast<uint4 *>(d_out));
-    EX_HIP_TRY(hipGetLastError());
-    EX_HIP_TRY(hipStreamSynchronize(stream)); // the table is released on return
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream)); // the table is released on return
     return ISSL_OK;
-}
-
-int null_argument()
-{
-    set_error("null argument");
-    return ISSL_E_ARG;
 }
 
 } // namespace
@@ -423,38 +418,25 @@ extern "C" {
 int issl_annotation_open(const char *gff, size_t len, int device, issl_annotation **out)
 {
     if (out) *out = nullptr;
-    if (!out || (!gff && len)) return issl::null_argument();
+    if (!out || (!gff && len)) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] { return issl::open_annotation(gff ? gff : "", len, device, out); });
 }
 
 int issl_annotation_open_file(const char *path, int device, issl_annotation **out)
 {
     if (out) *out = nullptr;
-    if (!out || !path) return issl::null_argument();
+    if (!out || !path) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
-        std::string text;
-        FILE *fp = std::fopen(path, "rb");
-        if (!fp) {
-            issl::set_error(std::string("cannot open annotation '") + path + "'");
-            return ISSL_E_IO;
-        }
-        char buf[1 << 16];
-        size_t k;
-        while ((k = std::fread(buf, 1, sizeof buf, fp)) > 0) text.append(buf, k);
-        const bool bad = std::ferror(fp) != 0;
-        std::fclose(fp);
-        if (bad) {
-            issl::set_error(std::string("cannot read annotation '") + path + "'");
-            return ISSL_E_IO;
-        }
-        return issl::open_annotation(text.data(), text.size(), device, out);
+        std::vector<char> text;
+        if (int rc = issl::read_whole_file(path, text, "annotation ")) return rc;
+        return issl::open_annotation(text.empty() ? "" : text.data(), text.size(), device, out);
     });
 }
 
 int issl_annotation_info(const issl_annotation *a, uint64_t *n_seqs, uint64_t *n_transcripts, uint64_t *n_genes, uint64_t *n_exons,
                          uint64_t *n_segments)
 {
-    if (!a || !n_seqs || !n_transcripts || !n_genes || !n_exons || !n_segments) return issl::null_argument();
+    if (!a || !n_seqs || !n_transcripts || !n_genes || !n_exons || !n_segments) return issl::fail(ISSL_E_ARG, "null argument");
     *n_seqs = a->t.seqs.size();
     *n_transcripts = a->t.tr_seq.size();
     *n_genes = a->t.gene_count.size();
@@ -465,7 +447,7 @@ int issl_annotation_info(const issl_annotation *a, uint64_t *n_seqs, uint64_t *n
 
 int issl_annotation_seq(const issl_annotation *a, uint64_t k, const char **name, size_t *name_len)
 {
-    if (!a || !name || !name_len) return issl::null_argument();
+    if (!a || !name || !name_len) return issl::fail(ISSL_E_ARG, "null argument");
     if (k >= a->t.seqs.size()) {
         issl::set_error("sequence out of range");
         return ISSL_E_ARG;
@@ -477,7 +459,7 @@ int issl_annotation_seq(const issl_annotation *a, uint64_t k, const char **name,
 
 int issl_annotation_lookup(const issl_annotation *a, const char *name, size_t name_len, uint32_t *seq)
 {
-    if (!a || !seq || (!name && name_len)) return issl::null_argument();
+    if (!a || !seq || (!name && name_len)) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] {
         const auto it = a->seq_index.find(std::string(name ? name : "", name_len));
         *seq = it == a->seq_index.end() ? 0xFFFFFFFFu : it->second;
@@ -487,21 +469,21 @@ int issl_annotation_lookup(const issl_annotation *a, const char *name, size_t na
 
 int issl_annotation_hits(issl_annotation *a, const uint32_t *seq, const int64_t *start, size_t n, issl_transcript_hits *out)
 {
-    if (!a || (n && (!seq || !start || !out))) return issl::null_argument();
+    if (!a || (n && (!seq || !start || !out))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] { return issl::hits_host(a, seq, start, n, out); });
 }
 
 int issl_annotation_hits_device(issl_annotation *a, const uint32_t *d_seq, const int64_t *d_start, size_t n, issl_transcript_hits *d_out,
                                 void *stream)
 {
-    if (!a || (n && (!d_seq || !d_start || !d_out))) return issl::null_argument();
+    if (!a || (n && (!d_seq || !d_start || !d_out))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] { return issl::hits_device(a, d_seq, d_start, n, d_out, static_cast<hipStream_t>(stream)); });
 }
 
 int issl_annotation_hits_occurrences_device(issl_annotation *a, const issl_genome *g, const issl_occurrence *d_rows, size_t n,
                                             issl_transcript_hits *d_out, void *stream)
 {
-    if (!a || !g || (n && (!d_rows || !d_out))) return issl::null_argument();
+    if (!a || !g || (n && (!d_rows || !d_out))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&] { return issl::hits_occurrences_device(a, g, d_rows, n, d_out, static_cast<hipStream_t>(stream)); });
 }
 

@@ -3,7 +3,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
-#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -106,16 +105,10 @@ static uint32_t dense_index(uint64_t mask)
     return idx;
 }
 
-static double wall_ms()
-{
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
 // upload_timing knob (ISSL_UPLOAD_TIMING=1): one diagnostic line per upload stage on stderr
 static void upload_note(const issl_index *ix, const char *what, double t0)
 {
-    if (ix->tuning.upload_timing) std::fprintf(stderr, "[issl upload] %s %.1f ms\n", what, wall_ms() - t0);
+    if (ix->tuning.upload_timing) std::fprintf(stderr, "[issl upload] %s %.1f ms\n", what, now_ms() - t0);
 }
 
 // Non-null when the slice lists are to be built on the device (the host index then has no arrays).
@@ -286,7 +279,7 @@ class FileUploader {
             bool issued_here = false;
             if (!j->failed.load() && !abandon_.load()) {
                 if (!pin_[slot] && !no_pin_[slot]) { // first use: pin it (side by side with the other readers)
-                    const double t0 = wall_ms();
+                    const double t0 = now_ms();
                     if (hipHostMalloc(&pin_[slot], chunk_, hipHostMallocDefault) != hipSuccess ||
                         hipEventCreateWithFlags(&ev_[slot], hipEventDisableTiming) != hipSuccess) {
                         (void)hipGetLastError();
@@ -294,7 +287,7 @@ class FileUploader {
                         pin_[slot] = nullptr;
                         no_pin_[slot] = true;
                     }
-                    pin_us_ += static_cast<long long>((wall_ms() - t0) * 1e3);
+                    pin_us_ += static_cast<long long>((now_ms() - t0) * 1e3);
                 }
                 if (!pin_[slot]) { // no pinned memory to be had: this chunk straight from the mapping
                     if (hipMemcpy(j->dst + c * chunk_, j->src + c * chunk_, len, hipMemcpyHostToDevice) != hipSuccess) j->failed = 1;
@@ -350,7 +343,7 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
     const HostIndex &h = *ix->host;
     const Geometry &g = h.geo;
     const uint64_t nb = g.n_buckets();
-    const double t_tables = wall_ms();
+    const double t_tables = now_ms();
     const hipMemcpyKind dbi_kind = (dbi && dbi->on_device) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     uint8_t *base = static_cast<uint8_t *>(ix->d_image);
     // The big sections of a file-mapped index are queued first: the readers pin their slots and fill them while this
@@ -415,7 +408,7 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
         seen = static_cast<uint32_t *>(seen_mem.p);
     }
     upload_note(ix, "bucket tables, score table (the file's sections are on their way)", t_tables);
-    double t0 = wall_ms();
+    double t0 = now_ms();
     if (ix->hdr.off_sub_start) {
         // Sorted layouts.  Site table and counts into the image, then one slice at a time: the slice's list (in the
         // image, or -- lists in pinned host memory -- in a temporary 8 B/site device copy), the successor-byte order
@@ -427,7 +420,7 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
         else if (int crc = from_file.wait(t_sites)) return crc;
         if (dbi) HIP_TRY(hipMemcpy(d_site_occ, dbi->occ, 4 * n, dbi_kind)); // (k_fill_maps writes the same again)
         upload_note(ix, "sites", t0);
-        t0 = wall_ms();
+        t0 = now_ms();
         // lists in pinned host memory, or nowhere (lists_absent): either way a slice's list exists on the device only while
         // the slice is worked on, in one 8 B/site temporary
         const bool lists_kept_cold = (ix->hdr.cold_on_host & 1u) != 0;
@@ -456,7 +449,7 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
         // its way (the copy returns when the slice has landed; the kernels are asynchronous on the null stream, the
         // copies run on a stream of their own).
         const bool stream_lists = !lists_cold && !dbi;
-        t0 = wall_ms();
+        t0 = now_ms();
         for (uint64_t sl = 0; sl < g.n_slices; ++sl) {
             uint64_t *const t_list_mem = lent_list ? lent_list : static_cast<uint64_t *>(list_mem.p);
             const uint64_t *d_list = lists_cold ? t_list_mem : d_entries + sl * n;
@@ -492,7 +485,7 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
         st.release();
         upload_note(ix, stream_lists ? "entries, slice by slice, beside the sorted layout (successor-byte order of every bucket + stream maps)"
                                      : "sorted layout (successor-byte order of every bucket + stream maps)", t0);
-        t0 = wall_ms();
+        t0 = now_ms();
         launch_pack_scan_stream(ix->view, scan_out, nullptr, nullptr, flag, nullptr, nullptr);
         HIP_TRY(hipGetLastError());
         launch_tag_sites(d_sites, d_site_occ, n); // (last: from here on `sites` carries a 24-bit copy of the counts)
@@ -502,14 +495,14 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
         if (dbi) HIP_TRY(hipMemcpy(base + ix->hdr.off_sites, dbi->sigs, 8 * g.n_sites, dbi_kind));
         else if (int crc = from_file.wait(t_sites)) return crc;
         upload_note(ix, "sites", t0);
-        t0 = wall_ms();
+        t0 = now_ms();
         if (dbi) { // isslCreateIndex.cpp:218-234 on the device
             int brc = launch_build_entries(reinterpret_cast<const uint64_t *>(base + ix->hdr.off_sites), d_occ, g.n_sites,
                                            0, static_cast<uint32_t>(g.n_slices), static_cast<uint32_t>(g.slice_width),
                                            reinterpret_cast<uint64_t *>(base + ix->hdr.off_entries));
             if (brc) return brc;
             upload_note(ix, "slice lists built on the device", t0);
-            t0 = wall_ms();
+            t0 = now_ms();
             launch_pack_scan_stream(ix->view, scan_out,
                                     ix->hdr.off_esig ? reinterpret_cast<uint64_t *>(base + ix->hdr.off_esig) : nullptr, nullptr, flag,
                                     seen, nullptr);
@@ -525,7 +518,7 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
                 HIP_TRY(hipGetLastError());
             }
             upload_note(ix, "entries, slice by slice, beside the packing of the scan stream", t0);
-            t0 = wall_ms();
+            t0 = now_ms();
         }
     } else {
         // List-order layout with sites and lists in pinned host memory: the scan stream is packed one slice at a time from temporary device
@@ -543,7 +536,7 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
         else std::memcpy(c_sites, dbi ? dbi->sigs : h.sites, 8 * n);
         HIP_TRY(hipMemcpy(t_sites, c_sites, 8 * n, hipMemcpyHostToDevice));
         upload_note(ix, "sites (pinned host copy + temporary device copy)", t0);
-        t0 = wall_ms();
+        t0 = now_ms();
         for (uint64_t sl = 0; sl < g.n_slices; ++sl) {
             if (dbi) {
                 int brc = launch_build_entries(t_sites, d_occ, n, static_cast<uint32_t>(sl), static_cast<uint32_t>(sl + 1),
@@ -563,13 +556,13 @@ static int finish_upload(issl_index *ix, const DeviceBuildInput *dbi = nullptr)
             HIP_TRY(hipDeviceSynchronize());
         }
         upload_note(ix, "slice lists into pinned host memory", t0);
-        t0 = wall_ms();
+        t0 = now_ms();
     }
     uint32_t err = 0;
     HIP_TRY(hipMemcpy(&err, flag, 4, hipMemcpyDeviceToHost));
     upload_note(ix, "scan stream", t0);
     if (ix->tuning.upload_timing) std::fprintf(stderr, "[issl upload] (pinning the ring: %.1f ms, summed over the readers)\n", from_file.pin_ms());
-    const double t_ring = wall_ms();
+    const double t_ring = now_ms();
     from_file.release();
     upload_note(ix, "pinned ring given back", t_ring);
     if (err & 1u) {
@@ -674,13 +667,13 @@ static int upload(issl_index *idx, int device, void *buf, size_t bytes, const De
     }
     int rc = supported_geometry(idx->geo);
     if (rc) return rc;
-    double t0 = wall_ms();
-    rc = select_device(device);
+    double t0 = now_ms();
+    rc = select_device(device, "the ISSL scorer");
     if (rc) return rc;
     release_device(idx);
     (void)hipFree(nullptr); // creates the context
     upload_note(idx, "device runtime start", t0);
-    t0 = wall_ms();
+    t0 = now_ms();
     std::vector<uint64_t> m;
     std::vector<double> v;
     idx->host->unique_scores(m, v);
@@ -774,7 +767,7 @@ static int upload(issl_index *idx, int device, void *buf, size_t bytes, const De
         release_device(idx);
         if (rc == kSortNoRoom) { // the temporaries of the sort did not fit after all: the next, smaller layout
             why = "no device memory for the temporaries of the sorted layout";
-            t0 = wall_ms();
+            t0 = now_ms();
             continue;
         }
         if (rc == kSortNeedsListOrder) {
@@ -830,8 +823,8 @@ int planned_image_bytes(const issl_index *idx, size_t *out)
 
 int attach_common(int device, void *dev_buf, size_t bytes, void *cold_host, size_t cold_bytes, issl_index **out)
 {
-    if (!dev_buf || !out) { set_error("null argument"); return ISSL_E_ARG; }
-    int rc = select_device(device);
+    if (!dev_buf || !out) return issl::fail(ISSL_E_ARG, "null argument");
+    int rc = select_device(device, "the ISSL scorer");
     if (rc) return rc;
     if (bytes < kHeaderBytes || (reinterpret_cast<uintptr_t>(dev_buf) & 255u)) {
         set_error("device image too small or not 256-byte aligned");

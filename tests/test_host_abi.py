@@ -311,6 +311,40 @@ def test_cli_without_its_library_fails_loudly(golden, tmp_path):
     assert r.returncode == 1 and b"Usage:" in r.stderr
 
 
+def _other_dlopen_executables():
+    """name -> arguments that pass its usage check (g: the golden index, fasta: a small FASTA file, out: a path to write)."""
+    sample = ROOT / "tests" / "golden" / "transcripts" / "sample"
+    return {
+        "isslReportOfftargets": lambda g, fasta, out: [str(g.issl), str(g.guides_txt), "4"],
+        "isslLocateOfftargets": lambda g, fasta, out: [str(g.guides_txt), str(fasta)],
+        "cracklingGuides": lambda g, fasta, out: [str(fasta)],
+        "cracklingBowtie": lambda g, fasta, out: [str(g.guides_txt), str(fasta)],
+        "countHitTranscripts": lambda g, fasta, out: ["-a", str(sample / "annotation.gff"), "-c", str(sample / "crackling.csv"), "-o", str(out)],
+    }
+
+
+@pytest.mark.parametrize("name", sorted(_other_dlopen_executables()))
+def test_cli_without_its_library_fails_loudly_every_executable(name, golden_uniform, tmp_path):
+    """The other five executables load libissl_hip.so through the same loader (csrc/cli_api.hpp), each under its own name:
+    a copy of the executable alone says what it tried and exits 1 with nothing on stdout; ISSL_LIBRARY points it at the
+    library again (and then it fails for want of a GPU, here)."""
+    import shutil
+    exe = tmp_path / name
+    shutil.copy(ROOT / "bin" / name, exe)
+    fasta = tmp_path / "g.fa"
+    fasta.write_text(">r1\nACGTACGTACGTACGTACGTACGTAGGTTCCATGCATGCATGCATGCATGCAGG\n")
+    out = tmp_path / "out.csv"
+    args = [str(exe)] + _other_dlopen_executables()[name](golden_uniform, fasta, out)
+    env = {k: v for k, v in os.environ.items() if k not in ("LD_LIBRARY_PATH", "ISSL_LIBRARY", "ISSL_SERVER")}
+    r = subprocess.run(args, capture_output=True, env=env, cwd=str(tmp_path))
+    assert r.returncode == 1 and r.stdout == b"" and b"cannot load libissl_hip.so" in r.stderr and b"ISSL_LIBRARY" in r.stderr
+    assert r.stderr.startswith(name.encode() + b": ") and not out.exists()
+    r = subprocess.run(args, capture_output=True, env=dict(env, ISSL_LIBRARY=_lib.LIB_PATH), cwd=str(tmp_path))
+    assert b"cannot load" not in r.stderr
+    if not _has_gpu():
+        assert r.returncode == 1 and b"no HIP device" in r.stderr
+
+
 def _has_gpu():
     try:
         import torch
