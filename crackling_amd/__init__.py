@@ -14,6 +14,8 @@ from .scorer import (  # noqa: F401
     GuideSet,
     IsslIndex,
     IsslNode,
+    LANDING_DTYPE,
+    LANDING_PROFILE_DTYPE,
     LOCATION_DTYPE,
     METHODS,
     OCCURRENCE_DTYPE,
@@ -68,6 +70,6 @@ __all__ = [
     "TRANSCRIPT_HITS_DTYPE", "Annotation", "TranscriptHits", "format_hits",
     "BOWTIE_PAMS", "BowtieStep", "OCCURRENCE_DTYPE", "bowtie_input", "format_columns", "read_bowtie_output",
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",
-    "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
+    "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LANDING_DTYPE", "LANDING_PROFILE_DTYPE", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH",
 ]

@@ -71,6 +71,24 @@ class Location(C.Structure):
     _fields_ = [("pos", C.c_uint64), ("record", C.c_uint32), ("strand", C.c_uint32)]
 
 
+class TranscriptHitsRow(C.Structure):
+    """issl_transcript_hits: 16 bytes."""
+    _fields_ = [("hit", C.c_uint32), ("total", C.c_uint32), ("status", C.c_uint32), ("first", C.c_uint32)]
+
+
+class Landing(C.Structure):
+    """issl_landing: 64 bytes, no padding."""
+    _fields_ = [("site", C.c_uint64), ("pos", C.c_uint64), ("record", C.c_uint32), ("strand", C.c_uint32), ("guide", C.c_uint32),
+                ("rank", C.c_uint32), ("id", C.c_uint32), ("occ", C.c_uint32), ("dist", C.c_uint16), ("slice", C.c_uint16),
+                ("pad", C.c_uint32), ("hits", TranscriptHitsRow)]
+
+
+class LandingProfile(C.Structure):
+    """issl_landing_profile: 144 bytes."""
+    _fields_ = [("located", C.c_uint64 * PROFILE_BINS), ("in_exon", C.c_uint64 * PROFILE_BINS), ("absent", C.c_uint32 * PROFILE_BINS),
+                ("pad", C.c_uint32)]
+
+
 class Guide(C.Structure):
     """issl_guide: 32 bytes, no padding."""
     _fields_ = [("guide23", C.c_uint64), ("start", C.c_uint64), ("record", C.c_uint32), ("strand", C.c_uint32),
@@ -207,6 +225,10 @@ _protos = {
     "issl_annotation_hits_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
     "issl_annotation_hits_occurrences_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
     "issl_annotation_close": (C.c_int, [_P]),
+    "issl_offtarget_landings": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_offtarget_landings_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_offtarget_landing_profile": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P]),
+    "issl_offtarget_landing_profile_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P]),
     "issl_results_build": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t,
                                      C.POINTER(ResultsConfig), C.POINTER(_P)]),
     "issl_results_build_rows": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t,

@@ -1,5 +1,6 @@
-// What the units on a resident genome share (issl_locate.hip: locations of sites; issl_occur.hip: the Bowtie step): the
-// handle, and the preparation of a piece of query sites -- signatures -> text-order keys, sorted with their query index,
+// What the units on a resident genome share (issl_locate.hip: locations of sites; issl_occur.hip: the Bowtie step;
+// issl_landing.hip: off-target landings): the handle, a piece of locate's scan as it stands before its finish, and the
+// preparation of a piece of query sites -- signatures -> text-order keys, sorted with their query index,
 // runs of equal keys collapsed to ranks, one bit per distinct key in a bitmap -- with the probe the scan of the text
 // asks.  Kernels and device functions live in an anonymous namespace, one copy per translation unit, like issl_match.hpp.
 #pragma once
@@ -14,6 +15,26 @@
 #include "issl_match.hpp"
 
 namespace issl {
+
+// ---- a piece of issl_locate.hip, for the units that join its hits with something else (issl_landing.hip) -----------
+// What locate_prepare leaves behind for the finish of a piece: query i of the piece owns the hit words
+// words[rstart[qrank[i]] .. + offs[i + 1] - offs[i]), sorted by (position, strand), and the piece's locations
+// offs[i] .. offs[i + 1) of `total`.  The arenas own the memory; it lives as long as the Piece.
+struct Piece {
+    Arena query, hit;
+    uint32_t n = 0;
+    uint64_t n_words = 0, total = 0;
+    const uint64_t *words = nullptr; // sorted hit words: rank << (pos_bits + 1) | text position << 1 | strand
+    uint32_t *offs = nullptr, *qrank = nullptr, *rstart = nullptr;
+};
+// Everything of a piece of n_sites <= 2^22 query sites but the locations.  Site i is d_sites[i * site_stride] (1: an array
+// of signatures; 5: the `site` fields of issl_offtarget records).  d_offsets[0..n] = base + the piece's offsets, or NULL.
+// Waits for the number of hit words and for the number of locations.
+int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t site_stride, size_t n_sites, uint64_t base,
+                   uint64_t *d_offsets, hipStream_t stream, Piece &pc);
+// A genome without a possible match, or an empty query.
+bool nothing_to_find(const issl_genome *g, size_t n);
+
 namespace {
 
 constexpr uint32_t kPieceBits = 22;                 // query index inside a piece: key (41 bits) | index fits a word
@@ -24,11 +45,13 @@ constexpr uint64_t kHashMul = 0x9E3779B97F4A7C15ull;
 
 // ---- query prep ---------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void k_query_words(const uint64_t *__restrict__ sites, uint32_t n, uint64_t *__restrict__ words)
+// Site i is sites[i * stride]: the stride is in 8-byte words.
+__global__ __launch_bounds__(256) void k_query_words(const uint64_t *__restrict__ sites, uint32_t stride, uint32_t n,
+                                                     uint64_t *__restrict__ words)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint64_t sig = sites[i];
+    const uint64_t sig = sites[static_cast<uint64_t>(i) * stride];
     uint64_t key = 0;
 #pragma unroll
     for (int p = 0; p < 20; ++p) key |= ((sig >> (2 * p)) & 3ull) << (2 * (19 - p));
@@ -125,9 +148,9 @@ struct QueryPrep {
         o_ctr = a.reserve(64);
     }
 
-    // wa: room for the n words, the caller's.  The sort ends in wa or in the arena's buffer; with into_wa the words are
+    // wa: room for the n words, the caller's; site i is d_sites[i * stride].  The sort ends in wa or in the arena's buffer; with into_wa the words are
     // copied to wa when it ended in the other one.
-    int enqueue(const Arena &a, const uint64_t *d_sites, uint64_t *wa, bool into_wa, hipStream_t stream)
+    int enqueue(const Arena &a, const uint64_t *d_sites, uint64_t *wa, bool into_wa, hipStream_t stream, uint32_t stride = 1)
     {
         uint64_t *wb = a.at<uint64_t>(o_wb), *ukeys = a.at<uint64_t>(o_ukeys);
         uint32_t *first = a.at<uint32_t>(o_first), *bitmap = a.at<uint32_t>(o_map);
@@ -136,7 +159,7 @@ struct QueryPrep {
         HIP_TRY(hipMemsetAsync(bitmap, 0, size_t(1) << (map_bits - 3), stream));
         HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
         HIP_TRY(hipMemsetAsync(first + q_blocks, 0, 4, stream));
-        hipLaunchKernelGGL(k_query_words, dim3(q_blocks), dim3(256), 0, stream, d_sites, n, wa);
+        hipLaunchKernelGGL(k_query_words, dim3(q_blocks), dim3(256), 0, stream, d_sites, stride, n, wa);
         sorted = radix_sort_async(wa, wb, n, kPieceBits, kPieceBits + 41, a.at<uint32_t>(o_hist), stream);
         if (into_wa && sorted != wa) {
             HIP_TRY(hipMemcpyAsync(wa, sorted, 8ull * n, hipMemcpyDeviceToDevice, stream));

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -118,5 +119,36 @@ int offtargets_host(issl_index *idx, const uint64_t *guides, size_t n, int max_d
                     size_t cap, size_t *n_total);
 int offtargets_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, uint64_t *d_offsets,
                       issl_offtarget *d_recs, size_t cap, size_t *n_total, hipStream_t stream);
+
+// A device buffer of the call (the piece's profiles, the piece's records): grown, never shrunk, freed at the end.
+struct CallBuffer : DevBuf {
+    size_t bytes = 0;
+    int reserve(size_t want)
+    {
+        if (want <= bytes) return ISSL_OK;
+        release();
+        bytes = 0;
+        HIP_TRY(hipMalloc(&p, want));
+        bytes = want;
+        return ISSL_OK;
+    }
+};
+
+// The off-target records of one batch of guides, left in device memory for a unit that reads them there
+// (issl_landing.hip): records d_recs[0 .. n_recs) in issl_offtargets' order, their `guide` fields counted from
+// guide_base; guide i of the batch owns d_recs[d_rec_off[i] .. d_rec_off[i + 1]).  d_rec_off is the workspace's and
+// holds until the handle's next batch.
+struct RecordBatch {
+    const uint64_t *d_guides = nullptr;
+    size_t n_guides = 0, guide_base = 0;
+    const issl_offtarget *d_recs = nullptr;
+    uint32_t n_recs = 0;
+    const uint32_t *d_rec_off = nullptr;
+};
+// One batch of guides in device memory, enqueued on `stream`; the records land in `buf`.
+int records_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, CallBuffer &buf, RecordBatch &out, hipStream_t stream);
+// Guides in host memory, cut as issl_offtargets cuts them: use(batch) once per piece, on the default stream.
+int records_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, CallBuffer &buf,
+                 const std::function<int(const RecordBatch &)> &use);
 
 } // namespace issl

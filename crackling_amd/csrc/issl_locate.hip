@@ -20,6 +20,7 @@
 //                a repeated one too -- the length of its rank's run, launch_scan turns them into offsets
 //   finish       k_locate_finish: one thread per location to write: its query by a search in the offsets, its word, the
 //                record by a search in the start table (in LDS up to 4096 records), one 16-byte store
+//                (issl_landing.hip puts its join in this place: locate_prepare and Piece are declared in issl_genome.hpp)
 // The host waits three times: for the number of hit words (sizes the buffers of the sort), for the number of
 // locations (the capacity rule is the host's: nothing is launched when they do not fit) and for the end.
 #include <hip/hip_runtime.h>
@@ -206,18 +207,12 @@ __global__ __launch_bounds__(256) void k_locate_finish(const uint64_t *__restric
 
 // ---- host --------------------------------------------------------------------------------------------------------
 
-// What a piece leaves behind for its finish.
-struct Piece {
-    Arena query, hit;
-    uint32_t n = 0;
-    uint64_t n_words = 0, total = 0;
-    const uint64_t *words = nullptr; // sorted hit words
-    uint32_t *offs = nullptr, *qrank = nullptr, *rstart = nullptr;
-};
+} // namespace
 
-// Everything of a piece but the locations: d_offsets[0..n] = base + the piece's offsets, pc.total = its locations.
-int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t n_sites, uint64_t base, uint64_t *d_offsets,
-                   hipStream_t stream, Piece &pc)
+// Everything of a piece but the locations: d_offsets[0..n] = base + the piece's offsets (when asked for), pc.total = its
+// locations.  Declared in issl_genome.hpp: issl_landing.hip joins the same pieces with the off-target records.
+int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t site_stride, size_t n_sites, uint64_t base,
+                   uint64_t *d_offsets, hipStream_t stream, Piece &pc)
 {
     const uint32_t n = static_cast<uint32_t>(n_sites);
     pc.n = n;
@@ -232,7 +227,7 @@ int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t n_sites
     uint32_t *rstart = qa.at<uint32_t>(o_rstart), *rend = qa.at<uint32_t>(o_rend), *cnt = qa.at<uint32_t>(o_cnt);
     HIP_TRY(hipMemsetAsync(rstart, 0, static_cast<size_t>(o_cnt - o_rstart), stream)); // rstart and rend
     // -- query prep: the sorted words are read where the sort left them
-    if (int rc = prep.enqueue(qa, d_sites, qa.at<uint64_t>(o_wa), false, stream)) return rc;
+    if (int rc = prep.enqueue(qa, d_sites, qa.at<uint64_t>(o_wa), false, stream, static_cast<uint32_t>(site_stride))) return rc;
     const Probe &probe = prep.probe;
     uint32_t *qrank = prep.qrank;
     unsigned long long *ctr = prep.ctr; // 0 hit words, 1 emit cursor, 2 matches, 3 passed, 4 locations
@@ -270,7 +265,8 @@ int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t n_sites
     // -- per-query counts -> offsets
     hipLaunchKernelGGL(k_query_counts, dim3(n / 256 + 1), dim3(256), 0, stream, qrank, rstart, rend, n, cnt, ctr + 4);
     launch_scan(cnt, n + 1ull, stream);
-    hipLaunchKernelGGL(k_write_offsets, dim3(n / 256 + 1), dim3(256), 0, stream, cnt, n + 1, base, d_offsets);
+    if (d_offsets)
+        hipLaunchKernelGGL(k_write_offsets, dim3(n / 256 + 1), dim3(256), 0, stream, cnt, n + 1, base, d_offsets);
     unsigned long long total = 0;
     HIP_TRY(hipMemcpyAsync(&total, ctr + 4, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -288,6 +284,11 @@ int locate_prepare(const issl_genome *g, const uint64_t *d_sites, size_t n_sites
     pc.rstart = rstart;
     return ISSL_OK;
 }
+
+// A genome without a possible match, or an empty query: offsets of zeros.
+bool nothing_to_find(const issl_genome *g, size_t n) { return n == 0 || g->len < 23; }
+
+namespace {
 
 // The piece's locations to d_locs[0 .. pc.total).  Returns when they are written.
 int locate_finish(const issl_genome *g, const Piece &pc, issl_location *d_locs, hipStream_t stream)
@@ -311,9 +312,6 @@ int locate_finish(const issl_genome *g, const Piece &pc, issl_location *d_locs, 
     return ISSL_OK;
 }
 
-// A genome without a possible match, or an empty query: offsets of zeros.
-bool nothing_to_find(const issl_genome *g, size_t n) { return n == 0 || g->len < 23; }
-
 int locate_device(issl_genome *g, const uint64_t *d_sites, size_t n, uint64_t *d_offsets, issl_location *d_locs, size_t cap,
                   size_t *n_total, hipStream_t stream)
 {
@@ -331,7 +329,7 @@ int locate_device(issl_genome *g, const uint64_t *d_sites, size_t n, uint64_t *d
         const size_t cnt = std::min(kPieceSites, n - at);
         Piece pc;
         bases.push_back(total);
-        if (int rc = locate_prepare(g, d_sites + at, cnt, total, d_offsets + at, stream, pc)) return rc;
+        if (int rc = locate_prepare(g, d_sites + at, 1, cnt, total, d_offsets + at, stream, pc)) return rc;
         total += pc.total;
         if (total > 0xFFFFFFFFull) {
             set_error("more than 2^32 - 1 locations in one call (" + std::to_string(total) + "): split the query");
@@ -345,7 +343,7 @@ int locate_device(issl_genome *g, const uint64_t *d_sites, size_t n, uint64_t *d
     for (size_t at = 0, k = 0; at < n; at += kPieceSites, ++k) {
         const size_t cnt = std::min(kPieceSites, n - at);
         Piece pc;
-        if (int rc = locate_prepare(g, d_sites + at, cnt, bases[k], d_offsets + at, stream, pc)) return rc;
+        if (int rc = locate_prepare(g, d_sites + at, 1, cnt, bases[k], d_offsets + at, stream, pc)) return rc;
         if (int rc = locate_finish(g, pc, d_locs + bases[k], stream)) return rc;
     }
     return ISSL_OK;
@@ -371,7 +369,7 @@ int locate_host(issl_genome *g, const uint64_t *sites, size_t n, uint64_t *offse
             const size_t cnt = std::min(kPieceSites, n - at);
             Piece pc;
             HIP_TRY(hipMemcpy(d_sites.p, sites + at, 8 * cnt, hipMemcpyHostToDevice));
-            if (int rc = locate_prepare(g, static_cast<const uint64_t *>(d_sites.p), cnt, base, static_cast<uint64_t *>(d_offs.p),
+            if (int rc = locate_prepare(g, static_cast<const uint64_t *>(d_sites.p), 1, cnt, base, static_cast<uint64_t *>(d_offs.p),
                                         nullptr, pc))
                 return rc;
             if (pass == 0) HIP_TRY(hipMemcpy(offsets + at, d_offs.p, 8 * (cnt + 1), hipMemcpyDeviceToHost));

@@ -664,21 +664,7 @@ int dump_hits(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, d
 }
 
 // ---- off-target report ------------------------------------------------------------------------
-// A device buffer of the call (the piece's profiles, the piece's records): grown, never shrunk, freed at the end.
-namespace {
-struct CallBuffer : DevBuf {
-    size_t bytes = 0;
-    int reserve(size_t want)
-    {
-        if (want <= bytes) return ISSL_OK;
-        release();
-        bytes = 0;
-        HIP_TRY(hipMalloc(&p, want));
-        bytes = want;
-        return ISSL_OK;
-    }
-};
-} // namespace
+// (CallBuffer, issl_index.hpp: a device buffer of the call -- the piece's profiles, the piece's records)
 
 // issl_offtarget_profile_device: the scoring pipeline with the profile kernels in the replay's place.  Neither score is
 // asked of k_verify (ISSL_METHOD_UNKNOWN): the distance and the count are all the profile reads.
@@ -797,6 +783,47 @@ int offtargets_host(issl_index *idx, const uint64_t *guides, size_t n, int max_d
     if (rc) return rc;
     *n_total = run;
     return ISSL_OK;
+}
+
+// ---- off-target records left on the device (issl_offtarget_landings*, issl_landing.hip) ----------------------------
+// One batch: offtargets_batch, then the records into `buf`.  Everything is enqueued on `stream`; the records are there
+// for what is enqueued behind them.
+static int records_batch(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, size_t guide_base, CallBuffer &buf,
+                         RecordBatch &out, hipStream_t stream)
+{
+    Workspace &ws = idx->lane.ws;
+    uint32_t records = 0;
+    int rc = offtargets_batch(idx, d_guides, n, max_dist, 0, 0, nullptr, nullptr, 0, &records, stream);
+    if (rc) return rc;
+    if (records) {
+        if ((rc = buf.reserve(sizeof(issl_offtarget) * size_t(records)))) return rc;
+        launch_report_emit(idx->view, ws, d_guides, records, static_cast<uint32_t>(guide_base), static_cast<issl_offtarget *>(buf.p), stream);
+        HIP_TRY(hipGetLastError());
+    }
+    out = RecordBatch{d_guides, n, guide_base, static_cast<const issl_offtarget *>(buf.p), records, ws.goff};
+    return ISSL_OK;
+}
+
+int records_device(issl_index *idx, const uint64_t *d_guides, size_t n, int max_dist, CallBuffer &buf, RecordBatch &out, hipStream_t stream)
+{
+    HIP_TRY(hipSetDevice(idx->device));
+    int rc = finish_batches(idx, stream);
+    if (rc) return rc;
+    rc = ensure_workspace(idx, std::min(n, kMaxBatch), idx->lane);
+    if (rc) return rc;
+    return records_batch(idx, d_guides, n, max_dist, 0, buf, out, stream);
+}
+
+int records_host(issl_index *idx, const uint64_t *guides, size_t n, int max_dist, CallBuffer &buf,
+                 const std::function<int(const RecordBatch &)> &use)
+{
+    return for_each_piece(idx, guides, n, max_dist, [&](size_t at, size_t cnt) -> int {
+        Workspace &ws = idx->lane.ws;
+        HIP_TRY(hipMemcpy(ws.d_guides, guides + at, 8 * cnt, hipMemcpyHostToDevice));
+        RecordBatch batch;
+        if (int rc = records_batch(idx, ws.d_guides, cnt, max_dist, at, buf, batch, nullptr)) return rc;
+        return use(batch);
+    });
 }
 
 // issl_score_device_async: one batch enqueued on a lane's internal stream.

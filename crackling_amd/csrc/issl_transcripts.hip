@@ -25,34 +25,14 @@
 #include <unordered_map>
 #include <vector>
 
-#include "issl_annotation.hpp"
-#include "issl_genome_handle.hpp"
+#include "issl_annotation_device.hpp"
+#include "issl_hiputil.hpp"
 #include "issl_match.hpp"
-
-struct issl_annotation {
-    int device = -1;
-    issl::AnnotationTables t; // exons released after the build
-    std::unordered_map<std::string, uint32_t> seq_index;
-    uint64_t n_exons = 0, n_bp = 0, n_segments = 0;
-    issl::DevBuf bp, seq_first, answers; // n_bp keys, n_seqs + 1 indices, n_bp rows
-};
 
 namespace issl {
 namespace {
 
 constexpr uint32_t kWaveSpan = 64; // ranges and lists of this length or more are walked by the wave
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-// First index in a[lo, hi) with a[i] >= x (hi when there is none).
-__device__ __forceinline__ uint32_t first_not_below(const uint64_t *__restrict__ a, uint32_t lo, uint32_t hi, uint64_t x)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // ---- distinct breakpoints ------------------------------------------------------------------------------------------
 
@@ -182,25 +162,6 @@ __global__ __launch_bounds__(256) void k_tr_answers(const uint32_t *__restrict__
 }
 
 // ---- queries -------------------------------------------------------------------------------------------------------
-
-struct View {
-    const uint64_t *bp;
-    const uint32_t *seq_first;
-    const uint4 *answers;
-    uint32_t n_seqs;
-};
-
-__device__ __forceinline__ uint4 answer_at(const View &v, uint32_t seq, long long start)
-{
-    const uint4 none = make_uint4(0u, 0u, 0u, kNone);
-    if (seq >= v.n_seqs || start < 0) return none;
-    const uint64_t top = (uint64_t(1) << kCoordBits) - 1; // beyond every breakpoint
-    const uint64_t coord = static_cast<uint64_t>(start) < top ? static_cast<uint64_t>(start) : top;
-    const uint64_t key = (static_cast<uint64_t>(seq) << kCoordBits) | coord;
-    const uint32_t b = v.seq_first[seq], e = v.seq_first[seq + 1];
-    const uint32_t ub = first_not_below(v.bp, b, e, key + 1); // first breakpoint above the position
-    return ub == b ? none : v.answers[ub - 1];
-}
 
 __global__ __launch_bounds__(256) void k_tr_hits(View v, const uint32_t *__restrict__ seq, const long long *__restrict__ start, uint64_t n,
                                                  uint4 *__restrict__ out)
@@ -332,12 +293,6 @@ int open_annotation(const char *gff, size_t len, int device, issl_annotation **o
     return ISSL_OK;
 }
 
-View view_of(const issl_annotation *a)
-{
-    return View{static_cast<const uint64_t *>(a->bp.p), static_cast<const uint32_t *>(a->seq_first.p),
-                static_cast<const uint4 *>(a->answers.p), static_cast<uint32_t>(a->t.seqs.size())};
-}
-
 int hits_device(issl_annotation *a, const uint32_t *d_seq, const int64_t *d_start, size_t n, issl_transcript_hits *d_out, hipStream_t stream)
 {
     HIP_TRY(hipSetDevice(a->device));
@@ -370,7 +325,6 @@ int hits_host(issl_annotation *a, const uint32_t *seq, const int64_t *start, siz
     return ISSL_OK;
 }
 
-// The sequence of every record of the genome under the name Bowtie2 gives it (the header up to the first blank), and of '*'.
 int hits_occurrences_device(issl_annotation *a, const issl_genome *g, const issl_occurrence *d_rows, size_t n, issl_transcript_hits *d_out,
                             hipStream_t stream)
 {
@@ -385,6 +339,21 @@ int hits_occurrences_device(issl_annotation *a, const issl_genome *g, const issl
         set_error("more than 2^39 rows in one call");
         return ISSL_E_UNSUPPORTED;
     }
+    DevBuf d_rec_seq;
+    if (int rc = record_sequences(a, g, d_rec_seq)) return rc;
+    const size_t n_records = g->records.size();
+    hipLaunchKernelGGL(k_tr_hits_rows, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, stream, view_of(a),
+                       reinterpret_cast<const ulonglong2 *>(d_rows), static_cast<uint64_t>(n), static_cast<const uint32_t *>(d_rec_seq.p),
+                       static_cast<uint32_t>(n_records), reinterpret_cast<uint4 *>(d_out));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream)); // the table is released on return
+    return ISSL_OK;
+}
+
+} // namespace
+
+int record_sequences(const issl_annotation *a, const issl_genome *g, DevBuf &d_rec_seq)
+{
     const size_t n_records = g->records.size();
     std::vector<uint32_t> rec_seq(n_records + 1, kNone);
     auto lookup = [&](const std::string &name) {
@@ -399,18 +368,11 @@ int hits_occurrences_device(issl_annotation *a, const issl_genome *g, const issl
         else rec_seq[r] = lookup(name.substr(b, name.find_first_of(blanks, b) - b));
     }
     rec_seq[n_records] = lookup("*");
-    DevBuf d_rec_seq;
     HIP_TRY(hipMalloc(&d_rec_seq.p, 4 * rec_seq.size()));
-    HIP_TRY(hipMemcpyAsync(d_rec_seq.p, rec_seq.data(), 4 * rec_seq.size(), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_tr_hits_rows, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, stream, view_of(a),
-                       reinterpret_cast<const ulonglong2 *>(d_rows), static_cast<uint64_t>(n), static_cast<const uint32_t *>(d_rec_seq.p),
-                       static_cast<uint32_t>(n_records), reinterpret_cast<uint4 *>(d_out));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream)); // the table is released on return
+    HIP_TRY(hipMemcpy(d_rec_seq.p, rec_seq.data(), 4 * rec_seq.size(), hipMemcpyHostToDevice)); // rec_seq ends with the call
     return ISSL_OK;
 }
 
-} // namespace
 } // namespace issl
 
 extern "C" {

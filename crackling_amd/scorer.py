@@ -27,6 +27,13 @@ OCCURRENCE_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("n_perfect", "<
 # issl_guide (32 bytes)
 GUIDE_DTYPE = np.dtype([("guide23", "<u8"), ("start", "<u8"), ("record", "<u4"), ("strand", "<u4"), ("seen", "<u4"), ("reserved", "<u4")])
 PROFILE_DTYPE = np.dtype([("sites", "<u4", (_lib.PROFILE_BINS,)), ("pad", "<u4"), ("occurrences", "<u8", (_lib.PROFILE_BINS,))])
+# issl_landing (64 bytes) and issl_landing_profile (144 bytes); `hits` is transcripts.TRANSCRIPT_HITS_DTYPE
+LANDING_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"), ("strand", "<u4"), ("guide", "<u4"), ("rank", "<u4"),
+                          ("id", "<u4"), ("occ", "<u4"), ("dist", "<u2"), ("slice", "<u2"), ("pad", "<u4"),
+                          ("hits", [("hit", "<u4"), ("total", "<u4"), ("status", "<u4"), ("first", "<u4")])])
+LANDING_PROFILE_DTYPE = np.dtype([("located", "<u8", (_lib.PROFILE_BINS,)), ("in_exon", "<u8", (_lib.PROFILE_BINS,)),
+                                  ("absent", "<u4", (_lib.PROFILE_BINS,)), ("pad", "<u4")])
+assert LANDING_DTYPE.itemsize == 64 and LANDING_PROFILE_DTYPE.itemsize == 144
 
 
 def _method_code(method):
@@ -336,6 +343,57 @@ class IsslIndex:
                                          d_recs.data_ptr() if cap else None, cap, C.byref(n),
                                          C.c_void_p(stream) if stream else None))
         return n.value
+
+    # -- off-target landings -------------------------------------------------------------------
+    def landings(self, guides, genome, annotation=None, max_dist=4):
+        """Where the guides' off-targets lie in `genome` (a Genome on this index's device) and, with `annotation` (an
+        Annotation on it), which transcripts each place cuts.  -> (offsets uint64[n + 1], rows): guide i owns
+        rows[offsets[i]:offsets[i + 1]], a structured array (LANDING_DTYPE) with the guide's off-targets in record order
+        and every off-target's places sorted by (record, pos, strand).  Without an annotation hits is status 1."""
+        sigs = self._sigs(guides)
+        offsets = np.zeros(len(sigs) + 1, dtype=np.uint64)
+        n = C.c_size_t()
+        args = (self._h, genome._h, annotation._h if annotation is not None else None, sigs.ctypes.data, len(sigs), int(max_dist),
+                offsets.ctypes.data)
+        check(lib.issl_offtarget_landings(*args, None, 0, C.byref(n)))
+        rows = np.empty(n.value, dtype=LANDING_DTYPE)
+        if n.value:
+            check(lib.issl_offtarget_landings(*args, rows.ctypes.data, n.value, C.byref(n)))
+        return offsets, rows
+
+    def landing_profile(self, guides, genome, annotation=None, max_dist=4):
+        """-> LANDING_PROFILE_DTYPE array, one row per guide: per distance the landings of the guide's off-targets, those
+        of them inside an exon (0 without an annotation) and the off-target sites that do not occur in `genome`.  No
+        landing reaches the host."""
+        sigs = self._sigs(guides)
+        out = np.zeros(len(sigs), dtype=LANDING_PROFILE_DTYPE)
+        check(lib.issl_offtarget_landing_profile(self._h, genome._h, annotation._h if annotation is not None else None,
+                                                 sigs.ctypes.data, len(sigs), int(max_dist), out.ctypes.data))
+        return out
+
+    def landings_device(self, d_guides, genome, d_offsets, d_rows, annotation=None, max_dist=4, stream=None):
+        """d_offsets: int64 CUDA tensor of n + 1 words; d_rows: uint8 CUDA tensor (64 bytes per landing, LANDING_DTYPE) or
+        None for the counting call.  -> the number of landings; nothing is written when they do not fit d_rows."""
+        n_guides = d_guides.numel()
+        if d_offsets.numel() * d_offsets.element_size() < 8 * (n_guides + 1):
+            raise ValueError("d_offsets holds fewer than n + 1 64-bit words")
+        n = C.c_size_t()
+        cap = d_rows.numel() * d_rows.element_size() // LANDING_DTYPE.itemsize if d_rows is not None else 0
+        check(lib.issl_offtarget_landings_device(self._h, genome._h, annotation._h if annotation is not None else None,
+                                                 d_guides.data_ptr() if n_guides else None, n_guides, int(max_dist),
+                                                 d_offsets.data_ptr(), d_rows.data_ptr() if cap else None, cap, C.byref(n),
+                                                 C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def landing_profile_device(self, d_guides, genome, d_out, annotation=None, max_dist=4, stream=None):
+        """d_out: uint8 CUDA tensor of 144 bytes per guide (LANDING_PROFILE_DTYPE once copied to the host)."""
+        n_guides = d_guides.numel()
+        if d_out.numel() * d_out.element_size() < LANDING_PROFILE_DTYPE.itemsize * n_guides:
+            raise ValueError("d_out holds fewer than 144 bytes per guide")
+        check(lib.issl_offtarget_landing_profile_device(self._h, genome._h, annotation._h if annotation is not None else None,
+                                                        d_guides.data_ptr() if n_guides else None, n_guides, int(max_dist),
+                                                        d_out.data_ptr() if n_guides else None,
+                                                        C.c_void_p(stream) if stream else None))
 
     def stats(self):
         st = _lib.Stats()

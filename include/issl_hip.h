@@ -797,6 +797,64 @@ int issl_annotation_hits_occurrences_device(issl_annotation *a, const issl_genom
                                             size_t n, issl_transcript_hits *d_out, void *stream);
 int issl_annotation_close(issl_annotation *a);
 
+/* ---- off-target landings: where a guide's off-targets lie, and what they cut ------------------------------------------- */
+/* The off-target report, the genome handle and the annotation joined on the device.  A LANDING is one occurrence in the
+ * genome of one off-target of one guide: an issl_offtarget record of the guide, one issl_location of that record's site,
+ * and the transcript answer at that location -- exactly what issl_annotation_hits returns for (name, pos + 1), name being
+ * the record's header from its first non-blank character up to the next blank (the rule of
+ * issl_annotation_hits_occurrences_device; not '.'->'_' translated).  Without an annotation (NULL) the answer is
+ * {0, 0, 1, 0xFFFFFFFF}: status 1, untested.
+ *   order     guides in batch order; inside a guide its off-targets in record order (the reference's scoring order, as
+ *             issl_offtargets lists them); inside an off-target its landings sorted by (record, pos, strand), as
+ *             issl_genome_locate lists them.  A site named by several records gets its list under each of them.  An
+ *             off-target that does not occur in this genome (index and genome from different inputs) has no landing
+ *   capacity  guide i owns out[offsets[i] .. offsets[i + 1]).  offsets (n + 1 words) and *n_total are always complete; when
+ *             *n_total > cap NO row is written and the call still returns ISSL_OK (out == NULL with cap == 0 is the
+ *             counting call) -- the rules of issl_offtargets and issl_genome_locate
+ *   pieces    the host calls take any n and cut the batch as issl_offtargets does; a piece of more than 2^22 records is
+ *             located in pieces of 2^22 sites.  At most one piece of records and landings is on the device at a time.  The
+ *             device calls take one batch
+ *   errors    NULL arguments: ISSL_E_ARG.  max_dist outside 0..6: ISSL_E_ARG.  An index that is not uploaded:
+ *             ISSL_E_STATE, as issl_offtargets.  The handles not on one device: ISSL_E_ARG, the message names the devices.
+ *             More than 2^32 - 1 landings in a call: ISSL_E_UNSUPPORTED.  No device: ISSL_E_DEVICE.  n == 0: ISSL_OK with
+ *             offsets[0] = 0
+ * The output is deterministic: the same bytes on every run.  The handles are used by one thread at a time. */
+typedef struct {
+    uint64_t site;              /* the off-target's packed signature */
+    uint64_t pos;               /* issl_location.pos */
+    uint32_t record, strand;    /* issl_location.record / .strand */
+    uint32_t guide;             /* index into the guide batch */
+    uint32_t rank;              /* index of the off-target among the guide's records: recs[offsets[guide] + rank] of issl_offtargets */
+    uint32_t id, occ;           /* issl_offtarget.id / .occ */
+    uint16_t dist, slice;
+    uint32_t pad;               /* 0 */
+    issl_transcript_hits hits;
+} issl_landing;                 /* 64 bytes, no padding */
+
+/* Per guide and distance d <= max_dist; bins above max_dist are zero.  For the genome an index was built from,
+ * located[d] == issl_profile.occurrences[d] and absent[d] == 0. */
+typedef struct {
+    uint64_t located[ISSL_PROFILE_BINS]; /* landings of off-targets at distance d */
+    uint64_t in_exon[ISSL_PROFILE_BINS]; /* of them, those with hits.hit > 0 (any status); 0 without an annotation */
+    uint32_t absent[ISSL_PROFILE_BINS];  /* off-target sites at distance d without a landing */
+    uint32_t pad;                        /* 0 */
+} issl_landing_profile;                  /* 144 bytes */
+
+/* Guides, offsets and rows in host memory.  Blocking. */
+int issl_offtarget_landings(issl_index *idx, issl_genome *g, issl_annotation *a /* may be NULL */, const uint64_t *guides, size_t n,
+                            int max_dist, uint64_t *offsets /* n + 1 */, issl_landing *out, size_t cap, size_t *n_total);
+/* Same with guides, offsets and rows in device memory, one batch, on `stream` (may be NULL); *n_total is host memory and
+ * the call returns when the batch is done. */
+int issl_offtarget_landings_device(issl_index *idx, issl_genome *g, issl_annotation *a, const uint64_t *d_guides, size_t n,
+                                   int max_dist, uint64_t *d_offsets, issl_landing *d_out, size_t cap, size_t *n_total, void *stream);
+/* One profile per guide; no landing is materialised, on the host or on the device: every guide's landings are reduced
+ * where the join would write them.  Blocking. */
+int issl_offtarget_landing_profile(issl_index *idx, issl_genome *g, issl_annotation *a, const uint64_t *guides, size_t n,
+                                   int max_dist, issl_landing_profile *out);
+/* Same with guides and profiles in device memory, one batch, on `stream`; returns when it is done. */
+int issl_offtarget_landing_profile_device(issl_index *idx, issl_genome *g, issl_annotation *a, const uint64_t *d_guides, size_t n,
+                                          int max_dist, issl_landing_profile *d_out, void *stream);
+
 /* ---- the result table: Crackling's output file from the resident stages ---------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:263-268 (the header row) and :842-852 (one CSV row of the 26 columns of
  * Constants.py:42-70 per candidate guide, csv.writer with dialect 'unix', QUOTE_MINIMAL, quote character '"'): the text is
