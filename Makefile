@@ -1,6 +1,6 @@
 # Build of the MI355X ISSL scorer: libissl_hip.so (C ABI, include/issl_hip.h; libissl_hip.map keeps every other symbol
 # out of its dynamic table), the three drop-in executables, isslReportOfftargets, isslLocateOfftargets, isslLandOfftargets,
-# isslIndexFromFasta,
+# isslSearchGenome, isslIndexFromFasta,
 # cracklingGuides, cracklingBowtie and countHitTranscripts.  hipcc cross-compiles for gfx950 without a GPU present.
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
@@ -11,12 +11,12 @@ CXXFLAGS = -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result
 HIPFLAGS = $(CXXFLAGS) --offload-arch=$(ARCH)
 LIB      = crackling_amd/libissl_hip.so
 
-all: $(LIB) bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOfftargets bin/isslLandOfftargets bin/isslCreateIndex bin/extractOfftargets bin/isslIndexFromFasta bin/cracklingGuides bin/cracklingBowtie bin/countHitTranscripts
+all: $(LIB) bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOfftargets bin/isslLandOfftargets bin/isslSearchGenome bin/isslCreateIndex bin/extractOfftargets bin/isslIndexFromFasta bin/cracklingGuides bin/cracklingBowtie bin/countHitTranscripts
 
 # The library: one object per source under build/obj/, the same flags for kernels and host code; the header dependencies
 # come from the compiler (-MMD -MP).
 SRCS = issl_kernels.hip issl_bin.hip issl_verify.hip issl_group.hip issl_replay.hip issl_report.hip issl_extract.hip \
-       issl_locate.hip issl_landing.hip issl_occur.hip issl_guides.hip issl_consensus.hip issl_build.hip issl_transcripts.hip issl_results.hip issl_results.cpp issl_folds.hip issl_folds.cpp issl_runlog.hip issl_annotation.cpp issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
+       issl_locate.hip issl_search.hip issl_landing.hip issl_occur.hip issl_guides.hip issl_consensus.hip issl_build.hip issl_transcripts.hip issl_results.hip issl_results.cpp issl_folds.hip issl_folds.cpp issl_runlog.hip issl_annotation.cpp issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
 OBJDIR = build/obj
 OBJS   = $(addprefix $(OBJDIR)/,$(addsuffix .o,$(SRCS)))  # (the suffix stays in the name: issl_results.hip and issl_results.cpp)
 COMPILE = $(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<
@@ -35,13 +35,14 @@ $(LIB): $(OBJS) $(CSRC)/libissl_hip.map
 
 # The host-only executables: libissl_hip.so is loaded with dlopen (cli_api.hpp: the search for the library, the symbols each
 # one needs, the ABI check) -- by isslScoreOfftargets only when the process has to score by itself, not when a resident
-# server answers (cli_score.cpp).  One recipe for the seven, each behind its own source:
+# server answers (cli_score.cpp).  One recipe for the eight, each behind its own source:
 #   isslScoreOfftargets   the drop-in scorer                 isslReportOfftargets  the off-target report (records or --profile)
 #   isslLocateOfftargets  where the off-targets lie          cracklingGuides       the candidate guides of FASTA inputs
 #   cracklingBowtie       the Bowtie step for a guide list   countHitTranscripts   transcript hit counts for Crackling's output
 #   isslLandOfftargets    off-target landings: guide, site, place in the genome, transcript hits (records or --profile)
+#   isslSearchGenome      index-free search: any PAM pattern, any length up to 32, up to k mismatches (rows or --profile)
 DLOPEN_EXES = bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOfftargets bin/cracklingGuides bin/cracklingBowtie \
-              bin/countHitTranscripts bin/isslLandOfftargets
+              bin/countHitTranscripts bin/isslLandOfftargets bin/isslSearchGenome
 bin/isslScoreOfftargets: $(CSRC)/cli_score.cpp $(CSRC)/issl_host.hpp
 bin/isslReportOfftargets: $(CSRC)/cli_report.cpp
 bin/isslLocateOfftargets: $(CSRC)/cli_locate.cpp
@@ -49,6 +50,7 @@ bin/cracklingGuides: $(CSRC)/cli_guides.cpp
 bin/cracklingBowtie: $(CSRC)/cli_bowtie.cpp
 bin/countHitTranscripts: $(CSRC)/cli_transcripts.cpp
 bin/isslLandOfftargets: $(CSRC)/cli_landing.cpp
+bin/isslSearchGenome: $(CSRC)/cli_search.cpp $(CSRC)/issl_search_text.hpp
 $(DLOPEN_EXES): $(CSRC)/cli_api.hpp include/issl_hip.h $(LIB)
 	@mkdir -p bin
 	g++ $(CXXFLAGS) -o $@ $(filter %.cpp,$^) -lpthread -ldl

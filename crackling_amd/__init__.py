@@ -21,6 +21,8 @@ from .scorer import (  # noqa: F401
     OCCURRENCE_DTYPE,
     OFFTARGET_DTYPE,
     PROFILE_DTYPE,
+    SEARCH_HIT_DTYPE,
+    SEARCH_QUERY_DTYPE,
     encode_guides,
     extract_offtargets,
     decode_guides,
@@ -28,6 +30,7 @@ from .scorer import (  # noqa: F401
     format_scores_native,
     run_scorer_binary,
     parse_scorer_output,
+    search_prepare,
     verdicts,
 )
 
@@ -71,5 +74,5 @@ __all__ = [
     "BOWTIE_PAMS", "BowtieStep", "OCCURRENCE_DTYPE", "bowtie_input", "format_columns", "read_bowtie_output",
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",
     "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LANDING_DTYPE", "LANDING_PROFILE_DTYPE", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
-    "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH",
+    "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH", "SEARCH_HIT_DTYPE", "SEARCH_QUERY_DTYPE", "search_prepare",
 ]

@@ -71,6 +71,22 @@ class Location(C.Structure):
     _fields_ = [("pos", C.c_uint64), ("record", C.c_uint32), ("strand", C.c_uint32)]
 
 
+class SearchPattern(C.Structure):
+    """issl_search_pattern: 32 bytes."""
+    _fields_ = [("allow", C.c_uint32 * 4), ("length", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class SearchQuery(C.Structure):
+    """issl_search_query: 16 bytes."""
+    _fields_ = [("sig", C.c_uint64), ("care", C.c_uint64)]
+
+
+class SearchHit(C.Structure):
+    """issl_search_hit: 32 bytes, no padding."""
+    _fields_ = [("site", C.c_uint64), ("pos", C.c_uint64), ("record", C.c_uint32), ("query", C.c_uint32), ("mism", C.c_uint32),
+                ("strand", C.c_uint8), ("dist", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
 class TranscriptHitsRow(C.Structure):
     """issl_transcript_hits: 16 bytes."""
     _fields_ = [("hit", C.c_uint32), ("total", C.c_uint32), ("status", C.c_uint32), ("first", C.c_uint32)]
@@ -193,6 +209,11 @@ _protos = {
     "issl_genome_record": (C.c_int, [_P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "issl_genome_locate": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "issl_genome_locate_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_search_prepare": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.c_size_t, _P, _P]),
+    "issl_genome_search": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_genome_search_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_genome_search_profile": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P]),
+    "issl_genome_search_profile_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P, _P]),
     "issl_genome_occurrences": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P]),
     "issl_genome_occurrences_device": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "issl_genome_occurrences_paged": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P]),

@@ -1,0 +1,109 @@
+// bin/isslSearchGenome -- where queries bind in a genome with up to max_dist mismatches, for any PAM pattern:
+//
+//   isslSearchGenome [--profile] <pattern> <query file> <max_dist> <FASTA ...|directory>
+//
+// pattern: 1 to 32 IUPAC codes (ACGTRYSWKMBDHVN), e.g. NNNNNNNNNNNNNNNNNNNNNGG or TTTVNNNNNNNNNNNNNNNNNNNN.  The query file has
+// one query per line over ACGTN ("\n" or "\r\n" line ends, a trailing blank line is ignored), every line of the pattern's
+// length; N is a position that is not compared.  The definitions are those of issl_genome_search (include/issl_hip.h).
+// One line per hit, the queries in file order, a query's hits by record, position and strand:
+//   <query text>\t<record name>\t<pos>\t<+|->\t<dist>\t<site>\n
+// pos is the 0-based start of the window inside the record on the forward strand for both strands; the site is what the
+// query is compared with ('-': the reverse complement of the window), its mismatching positions in lower case.
+// With --profile one line per query: <query text>\t<hits at distance 0>\t...\t<hits at max_dist>\n
+// The FASTA arguments follow bin/extractOfftargets: one input or several, a lone directory stands for its non-hidden
+// entries.  stdout carries data only, diagnostics go to stderr, exit status 1 on any error.
+//   ISSL_DEVICE=<n>       HIP device to use (default 0)
+//   ISSL_LIBRARY=<path>   libissl_hip.so to load (default: ../crackling_amd/ next to the executable, then the loader's path)
+// The executable does not link the library: it is loaded with dlopen, as isslLocateOfftargets does.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#define ISSL_CLI_NAME "isslSearchGenome"
+#define ISSL_CLI_API(X)                                                                                                   \
+    X(issl_last_error) X(issl_abi_version) X(issl_genome_open_files) X(issl_genome_record)                                  \
+    X(issl_genome_search) X(issl_genome_search_profile) X(issl_genome_close)
+#include "cli_api.hpp"
+#include "issl_search_text.hpp"
+
+int main(int argc, char **argv)
+{
+    namespace st = issl::search_text;
+    bool profile = false;
+    std::vector<const char *> pos;
+    for (int i = 1; i < argc; ++i) {
+        if (!std::strcmp(argv[i], "--profile")) profile = true;
+        else pos.push_back(argv[i]);
+    }
+    if (pos.size() < 4) {
+        std::fprintf(stderr, "Usage: %s [--profile] <pattern> <query file> <max_dist> <FASTA ...|directory>\n", argv[0]);
+        return 1;
+    }
+    // the pattern, max_dist and the query file first, then the library, the genome and the device
+    issl_search_pattern pat;
+    std::string err;
+    if (!st::parse_pattern(pos[0], &pat, err)) {
+        std::fprintf(stderr, "%s\n", err.c_str());
+        return 1;
+    }
+    char *end = nullptr;
+    const long max_dist = std::strtol(pos[2], &end, 10);
+    if (end == pos[2] || *end || max_dist < 0 || max_dist > static_cast<long>(pat.length)) {
+        std::fprintf(stderr, "max_dist '%s': a number from 0 to the pattern's length %u\n", pos[2], pat.length);
+        return 1;
+    }
+    std::string text, packed;
+    if (!read_text_file(pos[1], text)) {
+        std::fprintf(stderr, "cannot open '%s'\n", pos[1]);
+        return 1;
+    }
+    size_t n = 0;
+    if (!st::split_query_lines(text, pat.length, packed, n, err)) {
+        std::fprintf(stderr, "'%s' %s\n", pos[1], err.c_str());
+        return 1;
+    }
+    std::vector<issl_search_query> queries(n);
+    if (!st::prepare(pos[0], packed.data(), n, pat.length, &pat, queries.data(), err)) {
+        std::fprintf(stderr, "'%s' %s\n", pos[1], err.c_str());
+        return 1;
+    }
+    if (!load_api()) return 1;
+    const char *dev = std::getenv("ISSL_DEVICE");
+    issl_genome *g = nullptr;
+    if (api.issl_genome_open_files(pos.data() + 3, static_cast<int>(pos.size() - 3), dev ? std::atoi(dev) : 0, &g)) return fail("cannot open genome");
+    StdoutText so;
+    bool ok = true;
+    const uint32_t L = pat.length, D = static_cast<uint32_t>(max_dist);
+    if (profile) {
+        std::vector<uint64_t> counts(n * (D + 1));
+        if (api.issl_genome_search_profile(g, &pat, queries.data(), n, static_cast<int>(D), counts.data())) return fail("search failed");
+        for (size_t k = 0; ok && k < n; ++k) {
+            st::append_profile_line(so.text, packed.data() + k * L, L, counts.data() + k * (D + 1), D);
+            ok = so.wrote();
+        }
+    } else {
+        std::vector<uint64_t> offsets(n + 1);
+        std::vector<issl_search_hit> hits;
+        size_t total = 0;
+        if (api.issl_genome_search(g, &pat, queries.data(), n, static_cast<int>(D), offsets.data(), nullptr, 0, &total)) return fail("search failed");
+        if (total) {
+            hits.resize(total);
+            if (api.issl_genome_search(g, &pat, queries.data(), n, static_cast<int>(D), offsets.data(), hits.data(), hits.size(), &total))
+                return fail("search failed");
+        }
+        for (size_t j = 0; ok && j < hits.size(); ++j) {
+            const char *name = nullptr;
+            size_t name_len = 0;
+            uint64_t length = 0;
+            if (api.issl_genome_record(g, hits[j].record, &name, &name_len, &length)) return fail("record out of range");
+            st::append_hit_line(so.text, packed.data() + static_cast<size_t>(hits[j].query) * L, L, name, name_len, hits[j]);
+            ok = so.wrote();
+        }
+    }
+    ok = ok && so.finish();
+    if (!ok) { std::fprintf(stderr, "short write on stdout\n"); return 1; }
+    api.issl_genome_close(g);
+    return 0;
+}

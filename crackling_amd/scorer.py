@@ -19,6 +19,9 @@ METHODS = {"unknown": 0, "mit": 1, "cfd": 2, "and": 3, "or": 4, "avg": 5}
 # issl_offtarget (40 bytes) and issl_profile (88 bytes) of include/issl_hip.h
 OFFTARGET_DTYPE = np.dtype([("site", "<u8"), ("mit", "<f8"), ("cfd", "<f8"), ("guide", "<u4"), ("id", "<u4"), ("occ", "<u4"),
                             ("dist", "<u2"), ("slice", "<u2")])
+SEARCH_QUERY_DTYPE = np.dtype([("sig", "<u8"), ("care", "<u8")])  # issl_search_query (16 bytes)
+SEARCH_HIT_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
+                             ("strand", "u1"), ("dist", "u1"), ("reserved", "u1", (2,))])  # issl_search_hit (32 bytes)
 LOCATION_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("strand", "<u4")])  # issl_location (16 bytes)
 # issl_occurrence (32 bytes)
 OCCURRENCE_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("n_perfect", "<u4"), ("aligned", "u1"), ("repeated", "u1"),
@@ -473,6 +476,34 @@ class IsslNode:
             pass
 
 
+def search_prepare(pattern, queries):
+    """issl_search_prepare: pattern (str / bytes of 1 to 32 IUPAC codes) and queries (a list of str / bytes of its length
+    over ACGTN) -> (the pattern struct, the queries as a SEARCH_QUERY_DTYPE array).  No device needed."""
+    pattern = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+    texts = [t.encode() if isinstance(t, str) else bytes(t) for t in queries]
+    for k, t in enumerate(texts):
+        if len(t) != len(pattern):
+            raise ValueError(f"query {k} has {len(t)} characters, the pattern has {len(pattern)}")
+    pat = _lib.SearchPattern()
+    out = np.zeros(len(texts), dtype=SEARCH_QUERY_DTYPE)
+    blob = b"".join(texts)
+    check(lib.issl_search_prepare(pattern, blob if texts else None, len(texts), len(pattern), C.byref(pat),
+                                  out.ctypes.data if texts else None))
+    return pat, out
+
+
+def _search_pattern(pattern):
+    return pattern if isinstance(pattern, _lib.SearchPattern) else search_prepare(pattern, [])[0]
+
+
+def _search_args(pattern, queries):
+    if isinstance(queries, np.ndarray) and queries.dtype == SEARCH_QUERY_DTYPE:
+        return _search_pattern(pattern), np.ascontiguousarray(queries)
+    if isinstance(pattern, _lib.SearchPattern):
+        raise TypeError("query texts need the pattern's text")
+    return search_prepare(pattern, queries)
+
+
 class Genome:
     """A genome resident on the GPU that says where sites lie (issl_genome_* of include/issl_hip.h): the records of the
     FASTA inputs as the extraction joins them, 1 B per base of HBM.  A location is a match of the extraction: `pos` is
@@ -538,6 +569,53 @@ class Genome:
                                             d_locs.data_ptr() if cap else None, cap, C.byref(n),
                                             C.c_void_p(stream) if stream else None))
         return n.value
+
+    def search(self, pattern, queries, max_dist=4):
+        """Index-free search (issl_genome_search of include/issl_hip.h).  pattern: 1 to 32 IUPAC codes, or the struct of
+        search_prepare(); queries: a list of str / bytes of the pattern's length over ACGTN (N: not compared), or the
+        array of search_prepare().  -> (offsets uint64[n + 1], hits): query k owns hits[offsets[k]:offsets[k + 1]], a
+        structured array (SEARCH_HIT_DTYPE) sorted by (record, pos, strand).  `pos` is the window's 0-based start on the
+        forward strand for both strands; `site` is what the query was compared with (strand 1: the reverse complement of
+        the window), `mism` its mismatching positions."""
+        pat, q = _search_args(pattern, queries)
+        offsets = np.zeros(len(q) + 1, dtype=np.uint64)
+        n = C.c_size_t()
+        args = (self._h, C.byref(pat), q.ctypes.data if len(q) else None, len(q), int(max_dist), offsets.ctypes.data)
+        check(lib.issl_genome_search(*args, None, 0, C.byref(n)))
+        hits = np.zeros(n.value, dtype=SEARCH_HIT_DTYPE)
+        if n.value:
+            check(lib.issl_genome_search(*args, hits.ctypes.data, n.value, C.byref(n)))
+        return offsets, hits
+
+    def search_profile(self, pattern, queries, max_dist=4):
+        """-> uint64 array [n, max_dist + 1]: the hits of query k at distance d, counted on the device."""
+        pat, q = _search_args(pattern, queries)
+        counts = np.zeros((len(q), int(max_dist) + 1), dtype=np.uint64)
+        check(lib.issl_genome_search_profile(self._h, C.byref(pat), q.ctypes.data if len(q) else None, len(q), int(max_dist),
+                                             counts.ctypes.data if len(q) else None))
+        return counts
+
+    def search_device(self, pattern, d_queries, d_offsets, d_hits, max_dist=4, stream=None):
+        """pattern: as for search(); d_queries: CUDA tensor of 16 bytes per query (SEARCH_QUERY_DTYPE, e.g. int64 [n, 2]);
+        d_offsets: int64 CUDA tensor of n + 1 words; d_hits: uint8 CUDA tensor (32 bytes per hit, SEARCH_HIT_DTYPE) or None
+        for the counting call.  -> the number of hits; nothing is written when they do not fit d_hits."""
+        pat = _search_pattern(pattern)
+        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
+        n = C.c_size_t()
+        cap = d_hits.numel() * d_hits.element_size() // SEARCH_HIT_DTYPE.itemsize if d_hits is not None else 0
+        check(lib.issl_genome_search_device(self._h, C.byref(pat), d_queries.data_ptr() if nq else None, nq, int(max_dist),
+                                            d_offsets.data_ptr(), d_hits.data_ptr() if cap else None, cap, C.byref(n),
+                                            C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def search_profile_device(self, pattern, d_queries, d_counts, max_dist=4, stream=None):
+        """d_counts: int64 CUDA tensor of n * (max_dist + 1) words.  Returns when they are written."""
+        pat = _search_pattern(pattern)
+        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
+        if d_counts.numel() * d_counts.element_size() < 8 * nq * (int(max_dist) + 1):
+            raise ValueError("d_counts holds fewer than n * (max_dist + 1) words")
+        check(lib.issl_genome_search_profile_device(self._h, C.byref(pat), d_queries.data_ptr() if nq else None, nq, int(max_dist),
+                                                    d_counts.data_ptr() if nq else None, C.c_void_p(stream) if stream else None))
 
     def occurrences(self, sites, page_length=0, page_starts=None):
         """The Bowtie step (Crackling.py:600-725) as exact counts.  sites: 20-mer strings or a uint64 array of packed

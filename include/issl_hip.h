@@ -517,6 +517,58 @@ int issl_genome_locate_device(issl_genome *g, const uint64_t *d_sites, size_t n,
                               size_t cap, size_t *n_total, void *stream);
 int issl_genome_close(issl_genome *g);
 
+/* ---- genome search: any PAM pattern, any guide length, up to k mismatches ---------------------------------------- */
+/* An index-free answer on a genome handle: where does a query bind with at most max_dist mismatches, for a nuclease whose
+ * PAM and guide length a pattern describes.  Nothing of the extraction's rules is built in: no 20-mer, no N[AG]G, no
+ * exclusion of sites that start with T, and the minus strand gives the protospacer's own span.
+ *   pattern   a string of length L, 1 <= L <= 32, in IUPAC codes A C G T R Y S W K M B D H V N, either letter case;
+ *             position i allows the bases its code stands for
+ *   query     a string of the same length L over A C G T N, either case; N: this position is not compared.  A query of
+ *             only N is legal: it lists every window the pattern admits, each at distance 0
+ *   window    w = seq[pos : pos + L] of ONE record of the handle's text (upper-cased, as the handle holds it), all L
+ *             characters in ACGT; anything else, the record separator included, disqualifies the window, so no window
+ *             spans two records
+ *   strand    strand 0 reads t = w, strand 1 reads t = the reverse complement of w
+ *   hit       strand s of the window at pos is a hit of query q when t[i] is allowed by pattern[i] for every i, and
+ *             dist = #{ i : q[i] != 'N' and q[i] != t[i] } <= max_dist.  The pattern test and the comparison are
+ *             independent of each other.  One window can be a hit on both strands: two rows
+ *   pos       0-based start of w in the record, in forward coordinates FOR BOTH STRANDS: issl_location.pos's coordinate
+ *   site      t packed as issl_encode_guides packs it: base i in bits 2i and 2i + 1, bits above 2L zero
+ *   mism      bit i is set when q[i] != 'N' and q[i] != t[i]
+ *   max_dist  0 <= max_dist <= L
+ * Query k owns hits[offsets[k] .. offsets[k + 1]), sorted by (record, pos, strand); `query` is k.  The other rules are
+ * those of issl_genome_locate: offsets (n + 1 words) and *n_total are always complete; when *n_total > cap NO row is
+ * written and the call still returns ISSL_OK (hits == NULL with cap == 0 is the counting call); the bytes are the same on
+ * every run and do not depend on how the call is cut into pieces; a query named twice gets the same list twice; n == 0:
+ * ISSL_OK with offsets[0] = 0.  More than 2^32 - 1 hits in one call: ISSL_E_UNSUPPORTED.  No device: ISSL_E_DEVICE (no CPU
+ * fallback).  NULL arguments, L outside 1..32, a character outside the two alphabets, max_dist outside 0..L, pattern bits
+ * at or above L, a position that allows no base, and (host queries) query bits at or above 2L: ISSL_E_ARG before any device
+ * work; the message names the offending position.  With the extraction's forward pattern VNNNNNNNNNNNNNNNNNNNNRG the
+ * strand-0 hits of guide + "NNN" and the strand-1 hits of "NNN" + guide are the rows of issl_offtarget_landings.
+ * ISSL_LOCATE_TIMING=1 prints one stderr line per piece of 2^22 queries with the stage times. */
+typedef struct { uint32_t allow[4]; uint32_t length; uint32_t reserved[3]; } issl_search_pattern; /* 32 B; allow[b] bit i: base b (A,C,G,T) allowed at i */
+typedef struct { uint64_t sig; uint64_t care; } issl_search_query;   /* 16 B; sig: N packs as 0; care: bits 2i,2i+1 set where compared */
+typedef struct { uint64_t site; uint64_t pos; uint32_t record; uint32_t query; uint32_t mism;
+                 uint8_t strand; uint8_t dist; uint8_t reserved[2]; } issl_search_hit;            /* 32 B, no padding, reserved = 0 */
+
+/* Pattern text (NUL-terminated) and n query texts of its length, query k at queries + k * stride, into the structs the
+ * search takes.  Host only, no device needed.  queries may be NULL when n == 0. */
+int issl_search_prepare(const char *pattern, const char *queries, size_t n, size_t stride,
+                        issl_search_pattern *pat, issl_search_query *out);
+/* pat is host memory in every call.  Queries, offsets and hits in host memory.  Blocking. */
+int issl_genome_search(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *queries, size_t n, int max_dist,
+                       uint64_t *offsets, issl_search_hit *hits, size_t cap, size_t *n_total);
+/* Same with queries, offsets and hits in the memory of the handle's device, on `stream` (may be NULL); *n_total is host
+ * memory and the call returns when it is done.  The queries are not checked. */
+int issl_genome_search_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *d_queries, size_t n, int max_dist,
+                              uint64_t *d_offsets, issl_search_hit *d_hits, size_t cap, size_t *n_total, void *stream);
+/* counts[k * (max_dist + 1) + d]: hits of query k at distance d.  Reduced on the device: no row reaches the host, and
+ * the limit of 2^32 - 1 hits does not apply. */
+int issl_genome_search_profile(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *queries, size_t n, int max_dist,
+                               uint64_t *counts /* n * (max_dist + 1): hits of query k at distance d */);
+int issl_genome_search_profile_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *d_queries, size_t n,
+                                      int max_dist, uint64_t *d_counts, void *stream);
+
 /* ---- the Bowtie step: exact occurrences of a guide's eight reads ----------------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:600-725 on a genome handle.  For every guide the reference aligns eight reads,
  * the guide's 20-mer followed by AGG, CGG, GGG, TGG, AAG, CAG, GAG, TAG (variants 0..7), and counts the reads that align

@@ -21,7 +21,17 @@ filling call.  The yardstick beside them is the `match` stage of the fused build
 time to a resident set without timing, then once more under ISSL_GUIDES_TIMING=1 for the stage times (parse on the host;
 upload, count, emit, sort, runs, order, finish on the device) with free HBM sampled for the high-water mark per match.
 The yardstick is `match` + `sort` of the fused build in the same run: it reads the same text twice and sorts a
-comparable number of 64-bit words; the ratio of the device stages behind the upload to it is reported."""
+comparable number of 64-bit words; the ratio of the device stages behind the upload to it is reported.
+
+--search: instead of the chain, the genome is opened as a resident crackling_amd.Genome under ISSL_LOCATE_TIMING=1 and
+--search-queries queries (guide + NNN, the guides read off the genome's own text at seeded positions) are searched under
+the pattern NNNNNNNNNNNNNNNNNNNNNGG with max_dist 4: the stage times of the filling call (count, emit, sort, offsets,
+finish), the scan's counters (windows, window-strands the pattern admits, hits), windows per second of the count pass and
+comparisons per second (admitted window-strands x queries / count time).  Two yardsticks from the same run: the `match`
+stage of the fused build, which reads the same bytes twice (count + emit over it for the smallest query count), and the
+vector-issue bound of the compare loop -- --search-valu wave64 VALU instructions per 64 comparisons (read off the code
+object: tools/isa_stats.py k_search --dump) at 2 cycles each on 1024 SIMDs at 2.4 GHz, the rate DESIGN 3.1 uses for
+k_scan -- for the largest."""
 import argparse
 import filecmp
 import json
@@ -166,6 +176,41 @@ def locate_leg(fa, n_sites, seed):
     return {"open_s": open_s, "n_bases": plain.n_bases, "records": len(plain.records), "queries": res}
 
 
+def search_leg(fa, n_queries, seed, valu_per_compare):
+    import crackling_amd as ca
+    pattern, max_dist = "N" * 21 + "GG", 4
+    os.environ["ISSL_LOCATE_TIMING"] = "1"   # read when the handle is made
+    timed = ca.Genome.open([str(fa)])
+    os.environ.pop("ISSL_LOCATE_TIMING")
+
+    def queries_of(n, s):
+        sites = sample_sites(fa, n, s)
+        text = np.frombuffer(b"ACGT", dtype=np.uint8)[((sites[:, None] >> (2 * np.arange(20, dtype=np.uint64))) & np.uint64(3)).astype(np.int64)]
+        return ca.search_prepare(pattern, [bytes(row) + b"NNN" for row in text])
+
+    stderr_of(lambda: timed.search(*queries_of(8, seed), max_dist))  # code objects
+    bound = 1024 * 2.4e9 / (2 * valu_per_compare) * 64  # comparisons per second at the vector-issue rate of DESIGN 3.1
+    res = []
+    for n in n_queries:
+        pat, q = queries_of(n, seed + n)
+        t = time.perf_counter()
+        (offsets, hits), err = stderr_of(lambda: timed.search(pat, q, max_dist))
+        wall = time.perf_counter() - t
+        lines = [ln for ln in err.splitlines() if ln.startswith("[issl search]")]
+        fill = lines[len(lines) // 2:]   # the filling call's lines (the counting call's come first)
+        stages = {m.group(1): float(m.group(2)) for ln in fill for m in re.finditer(r" (\w+) ([0-9.]+) ms", ln)}
+        ctr = {m.group(1): int(m.group(2)) for ln in fill for m in re.finditer(r"(windows|admitted|hits) (\d+)", ln)}
+        count_s = stages["count"] / 1e3
+        comparisons = ctr["admitted"] * len(q)
+        res.append({"queries": int(len(q)), "hits": int(len(hits)), "wall_ms_counting_and_filling_call_timed_handle": wall * 1e3,
+                    "filling_call_stages_ms": stages, "scan_counters": ctr, "windows_per_s_count_pass": ctr["windows"] / count_s,
+                    "comparisons": comparisons, "comparisons_per_s_count_pass": comparisons / count_s,
+                    "fraction_of_vector_issue_bound": comparisons / count_s / bound})
+    timed.close()
+    return {"pattern": pattern, "max_dist": max_dist, "n_bases": timed.n_bases, "records": len(timed.records),
+            "valu_per_64_comparisons": valu_per_compare, "vector_issue_bound_comparisons_per_s": bound, "runs": res}
+
+
 def guides_leg(fa, torch):
     import crackling_amd as ca
     ca.GuideSet.extract([b">w\n" + b"ACGTTGCAGGTACCAGTAGGCAGG" * 100 + b"\n"]).close()   # code objects
@@ -188,7 +233,7 @@ def guides_leg(fa, torch):
             "hbm_high_water_per_match": hbm.peak / max(n_matches, 1), "resident_bytes_of_the_set": resident}
 
 
-def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, locate_sites=None, guides=False):
+def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, locate_sites=None, guides=False, search=None):
     import torch
     import crackling_amd as ca
     fa = work / f"genome_{kind}_{mbp:g}.fa"
@@ -218,6 +263,13 @@ def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, loc
         res["locate"] = locate_leg(fa, locate_sites, seed)
         res["locate"]["yardstick_match_stage_ms"] = stages.get("match", 0.0) * 1e3
         res["chain"] = "not run with --locate"
+    elif search:
+        res["search"] = search_leg(fa, search[0], seed, search[1])
+        match_ms = stages.get("match", 0.0) * 1e3
+        first = res["search"]["runs"][0]["filling_call_stages_ms"]
+        res["search"]["yardstick_match_stage_ms"] = match_ms
+        res["search"]["count_plus_emit_over_match_stage_smallest_query_count"] = (first["count"] + first.get("emit", 0.0)) / max(match_ms, 1e-9)
+        res["chain"] = "not run with --search"
     elif guides:
         res["guides"] = guides_leg(fa, torch)
         yard = (stages.get("match", 0.0) + stages.get("sort", 0.0)) * 1e3
@@ -259,6 +311,9 @@ def main():
     ap.add_argument("--locate", action="store_true", help="locate query sites in the resident genome instead of running the chain")
     ap.add_argument("--locate-sites", type=int, nargs="+", default=[1000, 1000000])
     ap.add_argument("--guides", action="store_true", help="extract the candidate guides of the genome instead of running the chain")
+    ap.add_argument("--search", action="store_true", help="search queries in the resident genome (any-PAM search) instead of running the chain")
+    ap.add_argument("--search-queries", type=int, nargs="+", default=[1, 100, 10000])
+    ap.add_argument("--search-valu", type=float, default=10.0, help="wave64 VALU instructions per 64 comparisons in k_search's compare loop")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -270,9 +325,9 @@ def main():
     results = []
     with tempfile.TemporaryDirectory(dir=a.workdir) as tmp:
         for mbp in a.mbp:
-            no_chain = a.locate or a.guides
+            no_chain = a.locate or a.guides or a.search
             r = run(mbp, a.kind, a.seed, a.width, pathlib.Path(tmp), 0.0 if no_chain else a.chain_max_mbp, 0.0 if no_chain else a.write_max_mbp, a.timeout,
-                    a.locate_sites if a.locate else None, a.guides)
+                    a.locate_sites if a.locate else None, a.guides, (a.search_queries, a.search_valu) if a.search else None)
             print(json.dumps(r), flush=True)
             results.append(r)
     if a.out:
