@@ -87,6 +87,17 @@ class SearchHit(C.Structure):
                 ("strand", C.c_uint8), ("dist", C.c_uint8), ("reserved", C.c_uint8 * 2)]
 
 
+class SearchBulges(C.Structure):
+    """issl_search_bulges: 16 bytes."""
+    _fields_ = [("guide_start", C.c_uint32), ("guide_length", C.c_uint32), ("max_dna", C.c_uint32), ("max_rna", C.c_uint32)]
+
+
+class BulgeHit(C.Structure):
+    """issl_bulge_hit: 32 bytes, no padding."""
+    _fields_ = [("site", C.c_uint64), ("pos", C.c_uint64), ("record", C.c_uint32), ("query", C.c_uint32), ("mism", C.c_uint32),
+                ("strand", C.c_uint8), ("dist", C.c_uint8), ("bulge", C.c_int8), ("at", C.c_uint8)]
+
+
 class TranscriptHitsRow(C.Structure):
     """issl_transcript_hits: 16 bytes."""
     _fields_ = [("hit", C.c_uint32), ("total", C.c_uint32), ("status", C.c_uint32), ("first", C.c_uint32)]
@@ -214,6 +225,10 @@ _protos = {
     "issl_genome_search_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "issl_genome_search_profile": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P]),
     "issl_genome_search_profile_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P, _P]),
+    "issl_genome_search_bulges": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_genome_search_bulges_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_genome_search_bulges_profile": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P]),
+    "issl_genome_search_bulges_profile_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P]),
     "issl_genome_occurrences": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P]),
     "issl_genome_occurrences_device": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "issl_genome_occurrences_paged": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P]),

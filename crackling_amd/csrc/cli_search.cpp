@@ -1,6 +1,6 @@
 // bin/isslSearchGenome -- where queries bind in a genome with up to max_dist mismatches, for any PAM pattern:
 //
-//   isslSearchGenome [--profile] <pattern> <query file> <max_dist> <FASTA ...|directory>
+//   isslSearchGenome [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R] <pattern> <query file> <max_dist> <FASTA ...|directory>
 //
 // pattern: 1 to 32 IUPAC codes (ACGTRYSWKMBDHVN), e.g. NNNNNNNNNNNNNNNNNNNNNGG or TTTVNNNNNNNNNNNNNNNNNNNN.  The query file has
 // one query per line over ACGTN ("\n" or "\r\n" line ends, a trailing blank line is ignored), every line of the pattern's
@@ -10,6 +10,14 @@
 // pos is the 0-based start of the window inside the record on the forward strand for both strands; the site is what the
 // query is compared with ('-': the reverse complement of the window), its mismatching positions in lower case.
 // With --profile one line per query: <query text>\t<hits at distance 0>\t...\t<hits at max_dist>\n
+// With --guide START:LEN the search allows bulges beside the mismatches (issl_genome_search_bulges): START:LEN are the
+// pattern positions where the protospacer lies, --dna-bulge D and --rna-bulge R (0..3, 1 when not given) the most bases of
+// the site and of the query that pair with nothing.  One line per row, a query's rows by record, position, strand, bulge:
+//   <query aligned>\t<record name>\t<pos>\t<+|->\t<dist>\t<bulge>\t<site aligned>\n
+// bulge is 0, D1..D3 or R1..R3; the query carries '-' x d and the site '-' x r at the break point; the site's mismatching
+// bases are in lower case, its unpaired bases in upper case.  Nothing is filtered: a locus that matches without a bulge is
+// listed under the shifted windows of the other bulges too.  --profile then prints <query text> and the R + D + 1 groups
+// (R3.., 0, ..D3) of max_dist + 1 counts, tab-separated.  --dna-bulge or --rna-bulge without --guide is a usage error.
 // The FASTA arguments follow bin/extractOfftargets: one input or several, a lone directory stands for its non-hidden
 // entries.  stdout carries data only, diagnostics go to stderr, exit status 1 on any error.
 //   ISSL_DEVICE=<n>       HIP device to use (default 0)
@@ -24,22 +32,51 @@
 #define ISSL_CLI_NAME "isslSearchGenome"
 #define ISSL_CLI_API(X)                                                                                                   \
     X(issl_last_error) X(issl_abi_version) X(issl_genome_open_files) X(issl_genome_record)                                  \
-    X(issl_genome_search) X(issl_genome_search_profile) X(issl_genome_close)
+    X(issl_genome_search) X(issl_genome_search_profile) X(issl_genome_search_bulges) X(issl_genome_search_bulges_profile)             \
+    X(issl_genome_close)
 #include "cli_api.hpp"
 #include "issl_search_text.hpp"
 
 int main(int argc, char **argv)
 {
     namespace st = issl::search_text;
-    bool profile = false;
+    bool profile = false, usage = false;
+    const char *guide = nullptr, *dna = nullptr, *rna = nullptr;
     std::vector<const char *> pos;
     for (int i = 1; i < argc; ++i) {
-        if (!std::strcmp(argv[i], "--profile")) profile = true;
+        const char **value = !std::strcmp(argv[i], "--guide") ? &guide : !std::strcmp(argv[i], "--dna-bulge") ? &dna
+                             : !std::strcmp(argv[i], "--rna-bulge") ? &rna : nullptr;
+        if (value) {
+            if (i + 1 < argc) *value = argv[++i];
+            else usage = true;
+        } else if (!std::strcmp(argv[i], "--profile")) profile = true;
         else pos.push_back(argv[i]);
     }
-    if (pos.size() < 4) {
-        std::fprintf(stderr, "Usage: %s [--profile] <pattern> <query file> <max_dist> <FASTA ...|directory>\n", argv[0]);
+    if (usage || pos.size() < 4 || ((dna || rna) && !guide)) {
+        std::fprintf(stderr, "Usage: %s [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R] <pattern> <query file> <max_dist> <FASTA ...|directory>\n",
+                     argv[0]);
         return 1;
+    }
+    // the span and the limits as numbers; what they may be is the library's check (check_bulges), made below
+    issl_search_bulges bg{0, 0, 1, 1};
+    if (guide) {
+        auto number = [](const char *text, char stop, uint32_t *out, const char **rest) {
+            char *e = nullptr;
+            const unsigned long v = std::strtoul(text, &e, 10);
+            if (e == text || *text == '-' || *text == '+' || *e != stop || v > 0xFFFFFFFFul) return false;
+            *out = static_cast<uint32_t>(v);
+            if (rest) *rest = e + 1;
+            return true;
+        };
+        const char *rest = nullptr;
+        if (!number(guide, ':', &bg.guide_start, &rest) || !number(rest, 0, &bg.guide_length, nullptr)) {
+            std::fprintf(stderr, "--guide '%s': START:LEN, two numbers\n", guide);
+            return 1;
+        }
+        if ((dna && !number(dna, 0, &bg.max_dna, nullptr)) || (rna && !number(rna, 0, &bg.max_rna, nullptr))) {
+            std::fprintf(stderr, "--dna-bulge and --rna-bulge take a number from 0 to 3\n");
+            return 1;
+        }
     }
     // the pattern, max_dist and the query file first, then the library, the genome and the device
     issl_search_pattern pat;
@@ -59,6 +96,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "cannot open '%s'\n", pos[1]);
         return 1;
     }
+    if (guide && !st::check_bulges(&pat, &bg, err)) {
+        std::fprintf(stderr, "%s\n", err.c_str());
+        return 1;
+    }
     size_t n = 0;
     if (!st::split_query_lines(text, pat.length, packed, n, err)) {
         std::fprintf(stderr, "'%s' %s\n", pos[1], err.c_str());
@@ -76,7 +117,34 @@ int main(int argc, char **argv)
     StdoutText so;
     bool ok = true;
     const uint32_t L = pat.length, D = static_cast<uint32_t>(max_dist);
-    if (profile) {
+    if (guide && profile) {
+        const uint32_t bins = (bg.max_rna + bg.max_dna + 1) * (D + 1);
+        std::vector<uint64_t> counts(n * bins);
+        if (api.issl_genome_search_bulges_profile(g, &pat, &bg, queries.data(), n, static_cast<int>(D), counts.data())) return fail("search failed");
+        for (size_t k = 0; ok && k < n; ++k) {
+            st::append_profile_line(so.text, packed.data() + k * L, L, counts.data() + k * bins, bins - 1);
+            ok = so.wrote();
+        }
+    } else if (guide) {
+        std::vector<uint64_t> offsets(n + 1);
+        std::vector<issl_bulge_hit> hits;
+        size_t total = 0;
+        if (api.issl_genome_search_bulges(g, &pat, &bg, queries.data(), n, static_cast<int>(D), offsets.data(), nullptr, 0, &total))
+            return fail("search failed");
+        if (total) {
+            hits.resize(total);
+            if (api.issl_genome_search_bulges(g, &pat, &bg, queries.data(), n, static_cast<int>(D), offsets.data(), hits.data(), hits.size(), &total))
+                return fail("search failed");
+        }
+        for (size_t j = 0; ok && j < hits.size(); ++j) {
+            const char *name = nullptr;
+            size_t name_len = 0;
+            uint64_t length = 0;
+            if (api.issl_genome_record(g, hits[j].record, &name, &name_len, &length)) return fail("record out of range");
+            st::append_bulge_line(so.text, packed.data() + static_cast<size_t>(hits[j].query) * L, L, bg.guide_start, name, name_len, hits[j]);
+            ok = so.wrote();
+        }
+    } else if (profile) {
         std::vector<uint64_t> counts(n * (D + 1));
         if (api.issl_genome_search_profile(g, &pat, queries.data(), n, static_cast<int>(D), counts.data())) return fail("search failed");
         for (size_t k = 0; ok && k < n; ++k) {

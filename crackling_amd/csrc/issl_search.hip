@@ -22,6 +22,7 @@
 // The profile is k_search<kProfile>: one pass, a hit adds to counts[query][dist] with one atomic per wave, query and
 // distance; no row exists anywhere.
 // The host waits for the number of hit words (sizes the buffers of the sort) and for the end of a piece.
+// pack16, the offsets kernel and the argument checks are issl_search_device.hpp's: issl_bulge.hip takes them too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,51 +36,19 @@
 #include "issl_host.hpp"
 #include "issl_match.hpp"
 #include "issl_radix.hpp"
+#include "issl_search_device.hpp"
 #include "issl_search_text.hpp"
 
 namespace issl {
 namespace {
 
-using search_text::SearchArgs;
 using search_text::kEven;
 using search_text::admits;
 using search_text::gather_even_bits;
 using search_text::mismatches;
 using search_text::reverse_complement;
 using search_text::window_word;
-constexpr uint32_t kTileWords = kPosPerBlock / 16 + 2; // 16 bases per word; the halo of up to 31 bases is two more words
 constexpr size_t kPieceQueries = size_t(1) << 22;       // 22 bits of query + 41 of position + 1 of strand = one word
-constexpr uint32_t kQueryGroup = 4;                     // queries a wave fetches at once (64 bytes of scalar loads)
-struct QueryGroup { issl_search_query q[kQueryGroup]; };
-enum Mode { kCount = 0, kEmit = 1, kProfile = 2 };
-
-static_assert(sizeof(issl_search_pattern) == 32 && sizeof(issl_search_query) == 16 && sizeof(issl_search_hit) == 32,
-              "the layouts of include/issl_hip.h");
-static_assert(kPosPerBlock == 256 * 16, "a thread owns the 16 windows that start in its word");
-
-// 16 bytes of text at `at` (a multiple of 16) -> 2-bit codes and one bit per base that is not A C G T; what lies behind
-// the text is such a base.
-__device__ __forceinline__ void pack16(const uint8_t *__restrict__ s, uint64_t at, uint64_t len, uint32_t &code, uint32_t &bad)
-{
-    code = 0;
-    bad = 0;
-    if (at + 16 <= len) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(s + at);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (uint32_t i = 0; i < 16; ++i) {
-            const uint32_t c = base_code(static_cast<uint8_t>(w[i >> 2] >> (8 * (i & 3))));
-            code |= (c & 3u) << (2 * i);
-            bad |= (c >> 2) << i;
-        }
-    } else {
-        for (uint32_t i = 0; i < 16; ++i) {
-            const uint32_t c = at + i < len ? base_code(s[at + i]) : 4u;
-            code |= (c & 3u) << (2 * i);
-            bad |= (c >> 2) << i;
-        }
-    }
-}
 
 // ctr[0]: hits; ctr[1]: the cursor of k_search<kEmit>; ctr[2]: window-strands the pattern admits; ctr[3]: windows of L
 // bases A C G T (the figures of the timing line, kCount only).
@@ -216,21 +185,6 @@ __global__ __launch_bounds__(256) void k_search(const uint8_t *__restrict__ s, u
     }
 }
 
-// out[k] = base + the first sorted word of a query >= k, for k = 0..n.
-__global__ __launch_bounds__(256) void k_search_offsets(const uint64_t *__restrict__ words, uint32_t n_words, uint32_t shift, uint32_t n,
-                                                        uint64_t base, uint64_t *__restrict__ out)
-{
-    const uint64_t k = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (k > n) return;
-    uint32_t lo = 0, hi = n_words;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if ((words[mid] >> shift) < k) lo = mid + 1;
-        else hi = mid;
-    }
-    out[k] = base + lo;
-}
-
 // Row j is sorted word j: the window is read again, as text.
 __global__ __launch_bounds__(256) void k_search_finish(const uint64_t *__restrict__ words, uint32_t total, const uint8_t *__restrict__ s,
                                                        SearchArgs a, const issl_search_query *__restrict__ q, uint32_t q_base,
@@ -257,15 +211,7 @@ __global__ __launch_bounds__(256) void k_search_finish(const uint64_t *__restric
 
 // ---- host --------------------------------------------------------------------------------------------------------
 
-int too_many(uint64_t hits)
-{
-    set_error("more than 2^32 - 1 hits in one call (" + std::to_string(hits) + "): split the query or lower max_dist");
-    return ISSL_E_UNSUPPORTED;
-}
-
 bool nothing_to_search(const issl_genome *g, const SearchArgs &a, size_t n) { return n == 0 || g->len < a.length; }
-
-uint32_t text_blocks(const issl_genome *g) { return static_cast<uint32_t>((g->len + kPosPerBlock - 1) / kPosPerBlock); }
 
 struct SearchPiece {
     Arena hit;
@@ -396,40 +342,6 @@ int profile_run(issl_genome *g, const SearchArgs &a, const issl_search_query *d_
         if (g->timing) std::fprintf(stderr, "[issl search] %zu queries:%s\n", n, clock.line.c_str());
     }
     HIP_TRY(hipStreamSynchronize(stream));
-    return ISSL_OK;
-}
-
-// The checks every entry point makes before any device work.  ISSL_OK: *a is what the kernels take.
-int check_call(const issl_search_pattern *pat, int max_dist, size_t n, SearchArgs *a)
-{
-    std::string err;
-    if (!search_text::check_pattern(pat, max_dist, err)) {
-        set_error(err);
-        return ISSL_E_ARG;
-    }
-    if (n > 0xFFFFFFFFull) {
-        set_error("more than 2^32 - 1 queries in one call");
-        return ISSL_E_UNSUPPORTED;
-    }
-    *a = search_text::make_args(*pat, max_dist);
-    return ISSL_OK;
-}
-
-int check_host_queries(const issl_search_query *queries, size_t n, uint32_t length)
-{
-    std::string err;
-    if (search_text::check_queries(queries, n, length, err)) return ISSL_OK;
-    set_error(err);
-    return ISSL_E_ARG;
-}
-
-// Host queries -> device memory of the handle.
-int upload_queries(issl_genome *g, const issl_search_query *queries, size_t n, DevBuf &d_q)
-{
-    HIP_TRY(hipSetDevice(g->device));
-    if (n == 0) return ISSL_OK;
-    HIP_TRY(hipMalloc(&d_q.p, sizeof(issl_search_query) * n));
-    HIP_TRY(hipMemcpy(d_q.p, queries, sizeof(issl_search_query) * n, hipMemcpyHostToDevice));
     return ISSL_OK;
 }
 

@@ -4,6 +4,8 @@
 // (cli_search.cpp) and tools/search_sanitize.cpp (a CPU program under AddressSanitizer + UBSan) include the same header.
 // The arithmetic on packed words that the kernels do (window_word, reverse_complement, admits, ...) lives here too, as
 // host and device code, so that the CPU program checks the very functions the kernels call against plain character loops.
+// The same holds for the bulge search (issl_genome_search_bulges*, issl_bulge.hip): its two mismatch words, the bound, the
+// minimum over the break points, check_bulges and the derived patterns are here, under tools/bulge_sanitize.cpp.
 // L = 32 uses all 64 bits of a packed word: nothing here shifts by 64.
 #pragma once
 #include <cstddef>
@@ -116,6 +118,77 @@ ISSL_ST_HD uint32_t distance(uint64_t t, uint64_t sig, uint64_t care_odd)
     const uint32_t ml = ((xl << 1) | xl) & static_cast<uint32_t>(care_odd);
     const uint32_t mh = ((xh << 1) | xh) & static_cast<uint32_t>(care_odd >> 32);
     return static_cast<uint32_t>(__builtin_popcount(ml) + __builtin_popcount(mh));
+}
+
+// ---- bulges (issl_genome_search_bulges*): a window of L + b bases aligned to the query at two shifts --------------------
+// b = d > 0: d bases of the site pair with nothing (DNA bulge); b = -r < 0: r bases of the query pair with nothing (RNA
+// bulge).  Left of the break point g0 + i query position j meets t[j], right of it t[j + b].  A and B are the mismatch
+// words of the two shifts over the WHOLE query, one bit per position (bit 2j), so that
+//   dist(d, i)  = popc(A & low(g0 + i)) + popc(B & ~low(g0 + i))
+//   dist(-r, i) = popc(A & low(g0 + i)) + popc(B & ~low(g0 + i + r))
+// and popc(A & B) - r is a lower bound of every one of them: the r skipped positions are all that A & B can count and the
+// sum does not.  What B holds below position r of an RNA bulge is never inside a mask.
+
+// One b of a call: the break points i_lo..i_hi and what the kernels need to place a row.
+struct BulgeArgs {
+    int32_t b;       // -R..D
+    uint32_t r;      // query positions without a partner: -b for an RNA bulge, else 0
+    uint32_t g0;     // guide_start
+    uint32_t i_lo, i_hi; // 0, 0 for b = 0; 1..G-1 for a DNA bulge; 1..G-1-r for an RNA bulge
+    uint32_t slot;   // b + R: its place in the hit word and in the profile
+    uint32_t slots;  // R + D + 1
+};
+
+// The low 2n bits, n in 0..32.
+ISSL_ST_HD uint64_t low_pairs(uint32_t n) { return n >= 32 ? ~0ull : (1ull << (2 * n)) - 1; }
+
+// t as query position j meets it right of the break point: base j of the result is t[j + b].
+ISSL_ST_HD uint64_t bulge_shift(uint64_t t, int32_t b) { return b >= 0 ? t >> (2 * b) : t << (2 * -b); }
+
+// The bound of the hot loop of k_bulge, in 32-bit halves as distance() counts.  popc(A & B) - r holds for every b, but
+// for an RNA bulge the r it gives away lets one comparison in a hundred through on random text.  The tight form counts in
+// SITE coordinates, where every position has exactly one partner at either shift: site position s meets query position s
+// left of the break point and s + r right of it, so with B' = B >> 2r (the query shifted down instead of the text up)
+//   dist(-r, i) = popc(A & low(g0 + i)) + popc(B' & ~low(g0 + i)) >= popc(A & B')
+// -- the DNA form, nothing subtracted.  One function for both:
+//   DNA  tb = t >> 2d, sig_b = sig,       care_both = care
+//   RNA  tb = t,       sig_b = sig >> 2r, care_both = care & (care >> 2r)
+// (bulge_bound_text, bulge_bound_query; sig_b and care_both are wave-uniform).  Returns popc(A & B) resp. popc(A & B'),
+// care_both_odd = care_both & ~kEven; never above any dist(b, i), equal to the distance for b = 0.
+ISSL_ST_HD uint64_t bulge_bound_text(uint64_t t, int32_t b) { return b > 0 ? t >> (2 * b) : t; }
+ISSL_ST_HD uint64_t bulge_bound_query(uint64_t x, uint32_t r) { return x >> (2 * r); }
+ISSL_ST_HD uint32_t bulge_both(uint64_t t, uint64_t tb, uint64_t sig, uint64_t sig_b, uint64_t care_both_odd)
+{
+    const uint32_t al = static_cast<uint32_t>(t) ^ static_cast<uint32_t>(sig), ah = static_cast<uint32_t>(t >> 32) ^ static_cast<uint32_t>(sig >> 32);
+    const uint32_t bl = static_cast<uint32_t>(tb) ^ static_cast<uint32_t>(sig_b), bh = static_cast<uint32_t>(tb >> 32) ^ static_cast<uint32_t>(sig_b >> 32);
+    const uint32_t ml = ((al << 1) | al) & ((bl << 1) | bl) & static_cast<uint32_t>(care_both_odd);
+    const uint32_t mh = ((ah << 1) | ah) & ((bh << 1) | bh) & static_cast<uint32_t>(care_both_odd >> 32);
+    return static_cast<uint32_t>(__builtin_popcount(ml) + __builtin_popcount(mh));
+}
+
+// min over i of dist(b, i) and the smallest i that reaches it, from A and B (bit 2j, as mismatches() gives them).  The
+// walk is incremental: moving the break point from i to i + 1 hands position g0 + i from B's side to A's.
+ISSL_ST_HD uint32_t bulge_min(uint64_t A, uint64_t B, const BulgeArgs &g, uint32_t &at)
+{
+    const uint32_t x = g.g0 + g.i_lo;
+    uint32_t cur = static_cast<uint32_t>(__builtin_popcountll(A & low_pairs(x)) + __builtin_popcountll(B & ~low_pairs(x + g.r)));
+    uint32_t best = cur;
+    at = g.i_lo;
+    for (uint32_t i = g.i_lo; i < g.i_hi; ++i) {
+        cur += static_cast<uint32_t>(A >> (2 * (g.g0 + i))) & 1u;
+        cur -= static_cast<uint32_t>(B >> (2 * (g.g0 + i + g.r))) & 1u;
+        if (cur < best) {
+            best = cur;
+            at = i + 1;
+        }
+    }
+    return best;
+}
+
+// The positions of alignment (b, at) that are paired and differ, bit 2j.
+ISSL_ST_HD uint64_t bulge_mism(uint64_t A, uint64_t B, const BulgeArgs &g, uint32_t at)
+{
+    return (A & low_pairs(g.g0 + at)) | (B & ~low_pairs(g.g0 + at + g.r));
 }
 
 // ---- text ----------------------------------------------------------------------------------------------------------
@@ -284,6 +357,76 @@ inline bool check_queries(const issl_search_query *q, size_t n, uint32_t length,
     return true;
 }
 
+// What a bulge search checks of its span and limits, after check_pattern() has passed.
+inline bool check_bulges(const issl_search_pattern *pat, const issl_search_bulges *bg, std::string &err)
+{
+    const uint32_t L = pat->length, g0 = bg->guide_start, G = bg->guide_length, D = bg->max_dna, R = bg->max_rna;
+    if (G < 2 || g0 > L || G > L - g0) {
+        err = "span (" + std::to_string(g0) + ", " + std::to_string(G) + ") out of range: guide_length is at least 2 and the span lies inside the pattern's " +
+              std::to_string(L) + " positions";
+        return false;
+    }
+    if (D > 3 || R > 3) {
+        err = std::string(D > 3 ? "max_dna " : "max_rna ") + std::to_string(D > 3 ? D : R) + ": 0 to 3";
+        return false;
+    }
+    if (L + D > kMaxLength) {
+        err = "max_dna " + std::to_string(D) + " with a pattern of " + std::to_string(L) + ": the window of a DNA bulge has at most 32 bases";
+        return false;
+    }
+    if (R > G - 2) {
+        err = "max_rna " + std::to_string(R) + " with guide_length " + std::to_string(G) + ": at most guide_length - 2";
+        return false;
+    }
+    if (D + R > 0)
+        for (uint32_t i = g0 + 1; i + 1 < g0 + G; ++i)
+            for (uint32_t b = 0; b < 4; ++b)
+                if (!(pat->allow[b] >> i & 1u)) {
+                    err = "pattern position " + std::to_string(i) + " is not N: a break point may lie there (only the span's first and last position and what is outside it carry other codes)";
+                    return false;
+                }
+    return true;
+}
+
+// P' of bulge b: P[:g0 + 1] + N * (G - 2 + b) + P[g0 + G - 1:], the same for every break point; P itself for b = 0.
+inline issl_search_pattern bulge_pattern(const issl_search_pattern &pat, const issl_search_bulges &bg, int32_t b)
+{
+    if (b == 0) return pat;
+    issl_search_pattern out{};
+    out.length = static_cast<uint32_t>(static_cast<int32_t>(pat.length) + b);
+    const uint32_t head = bg.guide_start + 1, tail_from = bg.guide_start + bg.guide_length - 1;
+    const uint32_t tail_to = static_cast<uint32_t>(static_cast<int32_t>(tail_from) + b);
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint64_t tail = static_cast<uint64_t>(pat.allow[k] >> tail_from) << tail_to;
+        out.allow[k] = (pat.allow[k] & low_bits32(head)) | (low_bits32(tail_to) & ~low_bits32(head)) | static_cast<uint32_t>(tail);
+    }
+    return out;
+}
+
+ISSL_ST_HD BulgeArgs make_bulge_args(const issl_search_bulges &bg, int32_t b)
+{
+    BulgeArgs g{};
+    g.b = b;
+    g.r = b < 0 ? static_cast<uint32_t>(-b) : 0u;
+    g.g0 = bg.guide_start;
+    g.i_lo = b ? 1u : 0u;
+    g.i_hi = b ? bg.guide_length - 1 - g.r : 0u;
+    g.slot = static_cast<uint32_t>(b + static_cast<int32_t>(bg.max_rna));
+    g.slots = bg.max_rna + bg.max_dna + 1;
+    return g;
+}
+
+// One row from the window's characters: what the finish pass does per row and a CPU checker per window.  t: the L + b
+// bases the strand reads, packed.  false: no alignment of this b is within max_dist.
+ISSL_ST_HD bool bulge_row(uint64_t t, const issl_search_query &q, const BulgeArgs &g, uint32_t max_dist, uint32_t &dist, uint32_t &at,
+                          uint32_t &mism)
+{
+    const uint64_t A = mismatches(t, q.sig, q.care & kEven), B = mismatches(bulge_shift(t, g.b), q.sig, q.care & kEven);
+    dist = bulge_min(A, B, g, at);
+    mism = gather_even_bits(bulge_mism(A, B, g, at));
+    return dist <= max_dist;
+}
+
 // ---- the lines of bin/isslSearchGenome --------------------------------------------------------------------------
 
 // The query file: one query per line, "\n" or "\r\n" line ends, a trailing blank line is ignored; every line has the
@@ -339,6 +482,40 @@ inline void append_profile_line(std::string &out, const char *query, uint32_t le
     for (uint32_t d = 0; d <= max_dist; ++d) {
         std::snprintf(buf, sizeof buf, "\t%llu", static_cast<unsigned long long>(counts[d]));
         out += buf;
+    }
+    out += '\n';
+}
+
+// "<query aligned>\t<record name>\t<pos>\t<+|->\t<dist>\t<0|D1..D3|R1..R3>\t<site aligned>\n": '-' x d in the query at
+// g0 + at for a DNA bulge, '-' x r in the site at g0 + at for an RNA bulge; the site's mismatching bases in lower case,
+// its unpaired bases in upper case.
+inline void append_bulge_line(std::string &out, const char *query, uint32_t length, uint32_t guide_start, const char *name,
+                              size_t name_len, const issl_bulge_hit &h)
+{
+    const uint32_t brk = guide_start + h.at, d = h.bulge > 0 ? static_cast<uint32_t>(h.bulge) : 0u,
+                   r = h.bulge < 0 ? static_cast<uint32_t>(-h.bulge) : 0u;
+    out.append(query, brk);
+    out.append(d, '-');
+    out.append(query + brk, length - brk);
+    out += '\t';
+    out.append(name, name_len);
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "\t%llu\t%c\t%u\t", static_cast<unsigned long long>(h.pos), h.strand ? '-' : '+',
+                  static_cast<unsigned>(h.dist));
+    out += buf;
+    if (h.bulge == 0) out += '0';
+    else {
+        out += h.bulge > 0 ? 'D' : 'R';
+        out += static_cast<char>('0' + d + r);
+    }
+    out += '\t';
+    const uint32_t site_len = length + d - r;
+    for (uint32_t s = 0; s < site_len; ++s) {
+        if (s == brk) out.append(r, '-');
+        const char c = "ACGT"[(h.site >> (2 * s)) & 3u];
+        const bool paired = s < brk || s >= brk + d;
+        const uint32_t j = s < brk ? s : s - d + r; // the query position it meets
+        out += (paired && (h.mism >> j & 1u)) ? static_cast<char>(c - 'A' + 'a') : c;
     }
     out += '\n';
 }

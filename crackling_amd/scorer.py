@@ -22,6 +22,8 @@ OFFTARGET_DTYPE = np.dtype([("site", "<u8"), ("mit", "<f8"), ("cfd", "<f8"), ("g
 SEARCH_QUERY_DTYPE = np.dtype([("sig", "<u8"), ("care", "<u8")])  # issl_search_query (16 bytes)
 SEARCH_HIT_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
                              ("strand", "u1"), ("dist", "u1"), ("reserved", "u1", (2,))])  # issl_search_hit (32 bytes)
+BULGE_HIT_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
+                            ("strand", "u1"), ("dist", "u1"), ("bulge", "i1"), ("at", "u1")])  # issl_bulge_hit (32 bytes)
 LOCATION_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("strand", "<u4")])  # issl_location (16 bytes)
 # issl_occurrence (32 bytes)
 OCCURRENCE_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("n_perfect", "<u4"), ("aligned", "u1"), ("repeated", "u1"),
@@ -504,6 +506,11 @@ def _search_args(pattern, queries):
     return search_prepare(pattern, queries)
 
 
+def _search_bulges(span, dna_bulge, rna_bulge):
+    start, length = span
+    return _lib.SearchBulges(int(start), int(length), int(dna_bulge), int(rna_bulge))
+
+
 class Genome:
     """A genome resident on the GPU that says where sites lie (issl_genome_* of include/issl_hip.h): the records of the
     FASTA inputs as the extraction joins them, 1 B per base of HBM.  A location is a match of the extraction: `pos` is
@@ -616,6 +623,61 @@ class Genome:
             raise ValueError("d_counts holds fewer than n * (max_dist + 1) words")
         check(lib.issl_genome_search_profile_device(self._h, C.byref(pat), d_queries.data_ptr() if nq else None, nq, int(max_dist),
                                                     d_counts.data_ptr() if nq else None, C.c_void_p(stream) if stream else None))
+
+    def search_bulges(self, pattern, queries, span, max_dist=4, dna_bulge=1, rna_bulge=1):
+        """Search with bulges beside the mismatches (issl_genome_search_bulges of include/issl_hip.h).  pattern and queries:
+        as for search(); span: (start, length), the pattern positions where the protospacer lies, never guessed;
+        dna_bulge / rna_bulge: the most bases of the site / of the query that pair with nothing, 0..3 each.
+        -> (offsets uint64[n + 1], hits): query k owns hits[offsets[k]:offsets[k + 1]], a structured array
+        (BULGE_HIT_DTYPE) sorted by (record, pos, strand, bulge).  One row per (query, record, pos, strand, bulge) with the
+        least distance over the break points; `bulge` is signed (> 0: DNA, < 0: RNA), `at` the break point inside the span,
+        `site` the window of L + bulge bases, `mism` in query coordinates.  Nothing is filtered: a locus that matches
+        without a bulge is listed under the other bulges' shifted windows too."""
+        pat, q = _search_args(pattern, queries)
+        bg = _search_bulges(span, dna_bulge, rna_bulge)
+        offsets = np.zeros(len(q) + 1, dtype=np.uint64)
+        n = C.c_size_t()
+        args = (self._h, C.byref(pat), C.byref(bg), q.ctypes.data if len(q) else None, len(q), int(max_dist), offsets.ctypes.data)
+        check(lib.issl_genome_search_bulges(*args, None, 0, C.byref(n)))
+        hits = np.zeros(n.value, dtype=BULGE_HIT_DTYPE)
+        if n.value:
+            check(lib.issl_genome_search_bulges(*args, hits.ctypes.data, n.value, C.byref(n)))
+        return offsets, hits
+
+    def search_bulges_profile(self, pattern, queries, span, max_dist=4, dna_bulge=1, rna_bulge=1):
+        """-> uint64 array [n, rna_bulge + dna_bulge + 1, max_dist + 1]: the rows of query k with bulge b (at index
+        b + rna_bulge) at minimum distance d, counted on the device."""
+        pat, q = _search_args(pattern, queries)
+        bg = _search_bulges(span, dna_bulge, rna_bulge)
+        counts = np.zeros((len(q), int(rna_bulge) + int(dna_bulge) + 1, int(max_dist) + 1), dtype=np.uint64)
+        check(lib.issl_genome_search_bulges_profile(self._h, C.byref(pat), C.byref(bg), q.ctypes.data if len(q) else None, len(q),
+                                                    int(max_dist), counts.ctypes.data if len(q) else None))
+        return counts
+
+    def search_bulges_device(self, pattern, d_queries, d_offsets, d_hits, span, max_dist=4, dna_bulge=1, rna_bulge=1, stream=None):
+        """search_device() with bulges: d_hits is a uint8 CUDA tensor (32 bytes per row, BULGE_HIT_DTYPE) or None for the
+        counting call.  -> the number of rows; nothing is written when they do not fit d_hits."""
+        pat = _search_pattern(pattern)
+        bg = _search_bulges(span, dna_bulge, rna_bulge)
+        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
+        n = C.c_size_t()
+        cap = d_hits.numel() * d_hits.element_size() // BULGE_HIT_DTYPE.itemsize if d_hits is not None else 0
+        check(lib.issl_genome_search_bulges_device(self._h, C.byref(pat), C.byref(bg), d_queries.data_ptr() if nq else None, nq,
+                                                   int(max_dist), d_offsets.data_ptr(), d_hits.data_ptr() if cap else None, cap,
+                                                   C.byref(n), C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def search_bulges_profile_device(self, pattern, d_queries, d_counts, span, max_dist=4, dna_bulge=1, rna_bulge=1, stream=None):
+        """d_counts: int64 CUDA tensor of n * (rna_bulge + dna_bulge + 1) * (max_dist + 1) words.  Returns when they are
+        written."""
+        pat = _search_pattern(pattern)
+        bg = _search_bulges(span, dna_bulge, rna_bulge)
+        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
+        if d_counts.numel() * d_counts.element_size() < 8 * nq * (int(rna_bulge) + int(dna_bulge) + 1) * (int(max_dist) + 1):
+            raise ValueError("d_counts holds fewer than n * (rna_bulge + dna_bulge + 1) * (max_dist + 1) words")
+        check(lib.issl_genome_search_bulges_profile_device(self._h, C.byref(pat), C.byref(bg), d_queries.data_ptr() if nq else None, nq,
+                                                           int(max_dist), d_counts.data_ptr() if nq else None,
+                                                           C.c_void_p(stream) if stream else None))
 
     def occurrences(self, sites, page_length=0, page_starts=None):
         """The Bowtie step (Crackling.py:600-725) as exact counts.  sites: 20-mer strings or a uint64 array of packed

@@ -569,6 +569,55 @@ int issl_genome_search_profile(issl_genome *g, const issl_search_pattern *pat, c
 int issl_genome_search_profile_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *d_queries, size_t n,
                                       int max_dist, uint64_t *d_counts, void *stream);
 
+/* ---- genome search with DNA and RNA bulges beside the mismatches ------------------------------------------------------- */
+/* Binding with a bulge: one to three bases of the DNA site that pair with nothing in the guide (a DNA bulge), or bases of
+ * the guide that pair with nothing in the site (an RNA bulge).  A bulged hit is defined through issl_genome_search:
+ *   pattern, query, window, strand, t, pos, site packing: as for issl_genome_search.  Pattern and queries have length L
+ *   span      guide_start g0 and guide_length G: the pattern positions where the protospacer lies.  Given by the caller,
+ *             never guessed (N * 21 + NNGRRT shows why).  2 <= G and g0 + G <= L
+ *   limits    max_dna D and max_rna R, each 0..3, with L + D <= 32 and R <= G - 2.  When D + R > 0 the pattern must allow
+ *             all four bases at positions g0 + 1 .. g0 + G - 2; the first and last position of the span, and everything
+ *             outside it, may carry any code
+ *   alignment (b, i), b signed, -R..D.  b = 0 has only i = 0: the pair (pattern, query) itself.  b = d > 0 is a DNA bulge
+ *             of d bases, i = 1..G-1: the pair is P' = P[:g0+i] + 'N'*d + P[g0+i:], q' built likewise.  b = -r < 0 is an
+ *             RNA bulge, i = 1..G-1-r: P' = P[:g0+i] + P[g0+i+r:], q' built likewise.  The window of alignment (b, i) has
+ *             L + b bases; it hits when it is a hit of issl_genome_search for (P', q', max_dist), and dist(b, i) is that
+ *             distance.  By the rule on the span's interior P' is the same for every i of one b
+ *   row       one per (query, record, pos, strand, b) that has at least one hitting alignment.  dist is the minimum of
+ *             dist(b, i) over i, `at` the smallest i that reaches it (0 for b = 0), `bulge` is b, `site` is t packed, L + b
+ *             bases.  mism is in QUERY coordinates: bit j is set when query position j is paired in alignment (b, at), is
+ *             not N, and differs from its partner.  The partner of j for b = d: t[j] for j < g0 + at, otherwise t[j + d];
+ *             for b = -r: t[j] for j < g0 + at, none for g0 + at <= j < g0 + at + r (bit clear), t[j - r] above that
+ *   NO FILTERING: a locus that matches at b = 0 also shows up in the shifted windows of the other b with a distance of
+ *             about |b|.  These rows are listed, as Cas-OFFinder lists them
+ *   order     query k owns hits[offsets[k] .. offsets[k + 1]), sorted by (record, pos, strand, bulge as a signed number)
+ *   max_dist  0..L
+ *   profile   counts[(k * (R + D + 1) + (b + R)) * (max_dist + 1) + dist]: the rows of query k with bulge b at that
+ *             minimum distance.  Reduced on the device
+ * The capacity rule, *n_total, the limit of 2^32 - 1 rows, n == 0, duplicated queries and "the bytes do not depend on the
+ * cut into pieces" (here of 2^19 queries) are as for issl_genome_search.  ISSL_E_ARG before any device work, with a message
+ * that names the offender: a span out of range, D or R above 3, L + D > 32, R > G - 2, a restricted pattern position that
+ * is not N (the message names the position), and everything issl_genome_search refuses.  With D = R = 0 the rows are those
+ * of issl_genome_search with bulge = at = 0. */
+typedef struct { uint32_t guide_start, guide_length, max_dna, max_rna; } issl_search_bulges;       /* 16 B */
+typedef struct { uint64_t site; uint64_t pos; uint32_t record; uint32_t query; uint32_t mism;
+                 uint8_t strand; uint8_t dist; int8_t bulge; uint8_t at; } issl_bulge_hit;         /* 32 B, no padding */
+/* pat and bulges are host memory in every call.  Queries, offsets and hits in host memory.  Blocking. */
+int issl_genome_search_bulges(issl_genome *g, const issl_search_pattern *pat, const issl_search_bulges *bulges,
+                              const issl_search_query *queries, size_t n, int max_dist, uint64_t *offsets, issl_bulge_hit *hits,
+                              size_t cap, size_t *n_total);
+/* Same with queries, offsets and hits in the memory of the handle's device, on `stream` (may be NULL); *n_total is host
+ * memory and the call returns when it is done.  The queries are not checked. */
+int issl_genome_search_bulges_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_bulges *bulges,
+                                     const issl_search_query *d_queries, size_t n, int max_dist, uint64_t *d_offsets,
+                                     issl_bulge_hit *d_hits, size_t cap, size_t *n_total, void *stream);
+int issl_genome_search_bulges_profile(issl_genome *g, const issl_search_pattern *pat, const issl_search_bulges *bulges,
+                                      const issl_search_query *queries, size_t n, int max_dist,
+                                      uint64_t *counts /* n * (R + D + 1) * (max_dist + 1) */);
+int issl_genome_search_bulges_profile_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_bulges *bulges,
+                                             const issl_search_query *d_queries, size_t n, int max_dist, uint64_t *d_counts,
+                                             void *stream);
+
 /* ---- the Bowtie step: exact occurrences of a guide's eight reads ----------------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:600-725 on a genome handle.  For every guide the reference aligns eight reads,
  * the guide's 20-mer followed by AGG, CGG, GGG, TGG, AAG, CAG, GAG, TAG (variants 0..7), and counts the reads that align

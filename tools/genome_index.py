@@ -31,7 +31,11 @@ comparisons per second (admitted window-strands x queries / count time).  Two ya
 stage of the fused build, which reads the same bytes twice (count + emit over it for the smallest query count), and the
 vector-issue bound of the compare loop -- --search-valu wave64 VALU instructions per 64 comparisons (read off the code
 object: tools/isa_stats.py k_search --dump) at 2 cycles each on 1024 SIMDs at 2.4 GHz, the rate DESIGN 3.1 uses for
-k_scan -- for the largest."""
+k_scan -- for the largest.  With --search-bulges V ... the largest query set is also searched with bulges (Genome.search_bulges,
+span (0, 20), D = R = V) and, as the yardstick, through the variant expansion: every alignment (b, i) as a derived
+(pattern, query) set, each a full Genome.search (74 sets at V = 2).  Both on the same handle without timing, alternating
+after one warm-up each; stage times, rows, windows and comparisons per second of the count pass come from one more call
+on the timed handle, --bulge-valu is read off tools/isa_stats.py k_bulge."""
 import argparse
 import filecmp
 import json
@@ -176,7 +180,7 @@ def locate_leg(fa, n_sites, seed):
     return {"open_s": open_s, "n_bases": plain.n_bases, "records": len(plain.records), "queries": res}
 
 
-def search_leg(fa, n_queries, seed, valu_per_compare):
+def search_leg(fa, n_queries, seed, valu_per_compare, bulges=None):
     import crackling_amd as ca
     pattern, max_dist = "N" * 21 + "GG", 4
     os.environ["ISSL_LOCATE_TIMING"] = "1"   # read when the handle is made
@@ -206,9 +210,68 @@ def search_leg(fa, n_queries, seed, valu_per_compare):
                     "filling_call_stages_ms": stages, "scan_counters": ctr, "windows_per_s_count_pass": ctr["windows"] / count_s,
                     "comparisons": comparisons, "comparisons_per_s_count_pass": comparisons / count_s,
                     "fraction_of_vector_issue_bound": comparisons / count_s / bound})
+    out = {"pattern": pattern, "max_dist": max_dist, "n_bases": timed.n_bases, "records": len(timed.records),
+           "valu_per_64_comparisons": valu_per_compare, "vector_issue_bound_comparisons_per_s": bound, "runs": res}
+    if bulges:
+        out["bulges"] = bulge_leg(ca, fa, timed, pattern, max_dist, queries_of(max(n_queries), seed + max(n_queries)), *bulges)
     timed.close()
-    return {"pattern": pattern, "max_dist": max_dist, "n_bases": timed.n_bases, "records": len(timed.records),
-            "valu_per_64_comparisons": valu_per_compare, "vector_issue_bound_comparisons_per_s": bound, "runs": res}
+    return out
+
+
+def bulge_leg(ca, fa, timed, pattern, max_dist, prepared, limits, valu_per_compare, rounds=2):
+    """Genome.search_bulges at D = R = v for every v of `limits`, span (0, 20), against the variant expansion: every
+    alignment (b, i) as a derived (pattern, query) set, each a full Genome.search.  Both on a handle without timing, the
+    derived texts prepared beforehand, one warm-up each, then `rounds` rounds alternating; the stage times and counters
+    come from one more call on the timed handle."""
+    span, G, (pat, q) = (0, 20), 20, prepared
+    texts = ["".join("ACGT"[(int(s) >> (2 * i)) & 3] if (int(c) >> (2 * i)) & 3 else "N" for i in range(len(pattern)))
+             for s, c in zip(q["sig"], q["care"])]
+    plain = ca.Genome.open([str(fa)])
+    res = []
+    for v in limits:
+        sets = []
+        for b in range(-v, v + 1):
+            for i in ([0] if b == 0 else range(1, G) if b > 0 else range(1, G + b)):
+                cut = span[0] + i
+                derive = (lambda t: t[:cut] + "N" * b + t[cut:]) if b >= 0 else (lambda t: t[:cut] + t[cut - b:])
+                sets.append(ca.search_prepare(derive(pattern), [derive(t) for t in texts]))
+        bound = 1024 * 2.4e9 / (2 * valu_per_compare) * 64
+
+        def new_path():
+            t = time.perf_counter()
+            offsets, rows = plain.search_bulges(pat, q, span, max_dist, v, v)
+            return time.perf_counter() - t, len(rows)
+
+        def expansion():
+            t = time.perf_counter()
+            hits = sum(len(plain.search(p, dq, max_dist)[1]) for p, dq in sets)
+            return time.perf_counter() - t, hits
+
+        new_path(), expansion()  # one warm-up each
+        walls = {"search_bulges": [], "expansion": []}
+        rows = hits = 0
+        for _ in range(rounds):
+            w, rows = new_path()
+            walls["search_bulges"].append(w * 1e3)
+            w, hits = expansion()
+            walls["expansion"].append(w * 1e3)
+        _, err = stderr_of(lambda: timed.search_bulges(pat, q, span, max_dist, v, v))
+        lines = [ln for ln in err.splitlines() if ln.startswith("[issl bulges]")]
+        fill = lines[len(lines) // 2:]   # the filling call's lines (the counting call's come first)
+        stages = {m.group(1): float(m.group(2)) for ln in fill for m in re.finditer(r" (\w+) ([0-9.]+) ms", ln)}
+        ctr = {m.group(1): int(m.group(2)) for ln in fill for m in re.finditer(r"(windows|admitted|rows) (\d+)", ln)}
+        count_s = stages["count"] / 1e3
+        comparisons = ctr["admitted"] * len(q)
+        ratio = min(walls["expansion"]) / min(walls["search_bulges"])
+        res.append({"max_dna": v, "max_rna": v, "span": list(span), "queries": int(len(q)), "rows": int(rows),
+                    "expansion_sets": len(sets), "expansion_hits_before_merging": int(hits),
+                    "wall_ms_counting_and_filling_call": walls, "expansion_over_search_bulges_best_of_rounds": ratio,
+                    "pass_mark_at_two_bases": 3.0, "filling_call_stages_ms": stages, "scan_counters": ctr,
+                    "windows_per_s_count_pass": ctr["windows"] / count_s, "comparisons": comparisons,
+                    "comparisons_per_s_count_pass": comparisons / count_s, "valu_per_64_comparisons": valu_per_compare,
+                    "fraction_of_vector_issue_bound": comparisons / count_s / bound})
+    plain.close()
+    return res
 
 
 def guides_leg(fa, torch):
@@ -264,7 +327,7 @@ def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, loc
         res["locate"]["yardstick_match_stage_ms"] = stages.get("match", 0.0) * 1e3
         res["chain"] = "not run with --locate"
     elif search:
-        res["search"] = search_leg(fa, search[0], seed, search[1])
+        res["search"] = search_leg(fa, search[0], seed, search[1], search[2])
         match_ms = stages.get("match", 0.0) * 1e3
         first = res["search"]["runs"][0]["filling_call_stages_ms"]
         res["search"]["yardstick_match_stage_ms"] = match_ms
@@ -314,6 +377,9 @@ def main():
     ap.add_argument("--search", action="store_true", help="search queries in the resident genome (any-PAM search) instead of running the chain")
     ap.add_argument("--search-queries", type=int, nargs="+", default=[1, 100, 10000])
     ap.add_argument("--search-valu", type=float, default=10.0, help="wave64 VALU instructions per 64 comparisons in k_search's compare loop")
+    ap.add_argument("--search-bulges", type=int, nargs="*", default=[], help="with --search: also Genome.search_bulges at D = R = each of these "
+                    "limits for the largest query count, against the variant expansion through Genome.search")
+    ap.add_argument("--bulge-valu", type=float, default=12.75, help="wave64 VALU instructions per 64 comparisons in k_bulge's compare loop")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -327,7 +393,7 @@ def main():
         for mbp in a.mbp:
             no_chain = a.locate or a.guides or a.search
             r = run(mbp, a.kind, a.seed, a.width, pathlib.Path(tmp), 0.0 if no_chain else a.chain_max_mbp, 0.0 if no_chain else a.write_max_mbp, a.timeout,
-                    a.locate_sites if a.locate else None, a.guides, (a.search_queries, a.search_valu) if a.search else None)
+                    a.locate_sites if a.locate else None, a.guides, (a.search_queries, a.search_valu, (a.search_bulges, a.bulge_valu) if a.search_bulges else None) if a.search else None)
             print(json.dumps(r), flush=True)
             results.append(r)
     if a.out:
