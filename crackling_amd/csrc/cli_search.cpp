@@ -37,6 +37,29 @@
 #include "cli_api.hpp"
 #include "issl_search_text.hpp"
 
+// The rows of one search, one line each: search(hits, cap, &total) is the library call -- asked for the total first, then
+// with room for it -- and line(record name, its length, row) appends a row's text.  ok: false after a short write on
+// stdout.  -> false after a failure, which is reported.
+template <class Row, class Search, class Line> bool print_rows(issl_genome *g, StdoutText &so, bool &ok, Search &&search, Line &&line)
+{
+    std::vector<Row> hits;
+    size_t total = 0;
+    if (search(nullptr, 0, &total)) return !fail("search failed");
+    if (total) {
+        hits.resize(total);
+        if (search(hits.data(), hits.size(), &total)) return !fail("search failed");
+    }
+    for (const Row &hit : hits) {
+        const char *name = nullptr;
+        size_t name_len = 0;
+        uint64_t length = 0;
+        if (api.issl_genome_record(g, hit.record, &name, &name_len, &length)) return !fail("record out of range");
+        line(name, name_len, hit);
+        if (!(ok = so.wrote())) break;
+    }
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     namespace st = issl::search_text;
@@ -116,6 +139,7 @@ int main(int argc, char **argv)
     if (api.issl_genome_open_files(pos.data() + 3, static_cast<int>(pos.size() - 3), dev ? std::atoi(dev) : 0, &g)) return fail("cannot open genome");
     StdoutText so;
     bool ok = true;
+    std::vector<uint64_t> offsets(n + 1);
     const uint32_t L = pat.length, D = static_cast<uint32_t>(max_dist);
     if (guide && profile) {
         const uint32_t bins = (bg.max_rna + bg.max_dna + 1) * (D + 1);
@@ -126,24 +150,13 @@ int main(int argc, char **argv)
             ok = so.wrote();
         }
     } else if (guide) {
-        std::vector<uint64_t> offsets(n + 1);
-        std::vector<issl_bulge_hit> hits;
-        size_t total = 0;
-        if (api.issl_genome_search_bulges(g, &pat, &bg, queries.data(), n, static_cast<int>(D), offsets.data(), nullptr, 0, &total))
-            return fail("search failed");
-        if (total) {
-            hits.resize(total);
-            if (api.issl_genome_search_bulges(g, &pat, &bg, queries.data(), n, static_cast<int>(D), offsets.data(), hits.data(), hits.size(), &total))
-                return fail("search failed");
-        }
-        for (size_t j = 0; ok && j < hits.size(); ++j) {
-            const char *name = nullptr;
-            size_t name_len = 0;
-            uint64_t length = 0;
-            if (api.issl_genome_record(g, hits[j].record, &name, &name_len, &length)) return fail("record out of range");
-            st::append_bulge_line(so.text, packed.data() + static_cast<size_t>(hits[j].query) * L, L, bg.guide_start, name, name_len, hits[j]);
-            ok = so.wrote();
-        }
+        auto search = [&](issl_bulge_hit *hits, size_t cap, size_t *total) {
+            return api.issl_genome_search_bulges(g, &pat, &bg, queries.data(), n, static_cast<int>(D), offsets.data(), hits, cap, total);
+        };
+        if (!print_rows<issl_bulge_hit>(g, so, ok, search, [&](const char *name, size_t name_len, const issl_bulge_hit &hit) {
+            st::append_bulge_line(so.text, packed.data() + static_cast<size_t>(hit.query) * L, L, bg.guide_start, name, name_len, hit);
+            }))
+            return 1;
     } else if (profile) {
         std::vector<uint64_t> counts(n * (D + 1));
         if (api.issl_genome_search_profile(g, &pat, queries.data(), n, static_cast<int>(D), counts.data())) return fail("search failed");
@@ -152,23 +165,13 @@ int main(int argc, char **argv)
             ok = so.wrote();
         }
     } else {
-        std::vector<uint64_t> offsets(n + 1);
-        std::vector<issl_search_hit> hits;
-        size_t total = 0;
-        if (api.issl_genome_search(g, &pat, queries.data(), n, static_cast<int>(D), offsets.data(), nullptr, 0, &total)) return fail("search failed");
-        if (total) {
-            hits.resize(total);
-            if (api.issl_genome_search(g, &pat, queries.data(), n, static_cast<int>(D), offsets.data(), hits.data(), hits.size(), &total))
-                return fail("search failed");
-        }
-        for (size_t j = 0; ok && j < hits.size(); ++j) {
-            const char *name = nullptr;
-            size_t name_len = 0;
-            uint64_t length = 0;
-            if (api.issl_genome_record(g, hits[j].record, &name, &name_len, &length)) return fail("record out of range");
-            st::append_hit_line(so.text, packed.data() + static_cast<size_t>(hits[j].query) * L, L, name, name_len, hits[j]);
-            ok = so.wrote();
-        }
+        auto search = [&](issl_search_hit *hits, size_t cap, size_t *total) {
+            return api.issl_genome_search(g, &pat, queries.data(), n, static_cast<int>(D), offsets.data(), hits, cap, total);
+        };
+        if (!print_rows<issl_search_hit>(g, so, ok, search, [&](const char *name, size_t name_len, const issl_search_hit &hit) {
+            st::append_hit_line(so.text, packed.data() + static_cast<size_t>(hit.query) * L, L, name, name_len, hit);
+            }))
+            return 1;
     }
     ok = ok && so.finish();
     if (!ok) { std::fprintf(stderr, "short write on stdout\n"); return 1; }

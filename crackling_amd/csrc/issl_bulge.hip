@@ -1,7 +1,7 @@
 // Genome search with DNA and RNA bulges beside the mismatches (issl_genome_search_bulges*, include/issl_hip.h): where a
-// query binds when up to D bases of the site, or up to R bases of the query, pair with nothing.  The protocol, the text
-// grid, the tile, the pattern test and the survivor queue are those of issl_search.hip; a piece has up to 2^19 queries.
-//
+// query binds when up to D bases of the site, or up to R bases of the query, pair with nothing.  The protocol is that of
+// issl_search_core.hpp, its host side SearchDriver<BulgeSearch> (issl_search_device.hpp); a piece has up to 2^19 queries.
+// This unit's own:
 //   count    k_bulge<kCount>, one launch per bulge b = -R..D (at most seven) with the SearchArgs of that b's pattern P':
 //            the windows have L + b bases.  A lane holds one survivor's packed word t and the same word shifted by b
 //            (a DNA bulge; for an RNA bulge the wave-uniform query is shifted instead: k_bulge<, kRna>); against the query
@@ -11,28 +11,20 @@
 //            kQueryGroup bounds, keeps their minimum and asks once per group whether any lane is within max_dist; only
 //            then the group's queries are taken one by one, and only a query whose own ballot is non-zero walks the break
 //            points -- incrementally, one bit of A in and one bit of B out per step (bulge_min)
-//   emit     the same kernel, k_bulge<kEmit>: a row is one word query | text position | strand | b + R; all b of a piece
-//            share one buffer and one cursor
-//   sort     one radix sort over all b's words of the piece: query-major, then position, strand and bulge as a signed
-//            number -- b + R ascends with b
-//   offsets  k_search_offsets on the query field
+//   emit     a row is one word query | text position | strand | b + R; all b of a piece share one buffer and one cursor,
+//            so one sort orders a query's rows by position, strand and bulge as a signed number -- b + R ascends with b
 //   finish   k_bulge_finish: one thread per row reads the window as text again and recomputes the minimum, its break
 //            point, mism and site with the functions the hot loop's decision came from (bulge_row)
-// The profile is k_bulge<kProfile>: counts[query][b + R][min dist], one atomic per wave, query and distance.
+//   profile  counts[query][b + R][min dist]
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/issl_hip.h"
 #include "issl_genome_handle.hpp"
 #include "issl_host.hpp"
 #include "issl_match.hpp"
-#include "issl_radix.hpp"
-#include "issl_search_device.hpp"
+#include "issl_search_core.hpp"
 #include "issl_search_text.hpp"
 
 namespace issl {
@@ -45,7 +37,6 @@ using search_text::mismatches;
 using search_text::reverse_complement;
 using search_text::window_word;
 constexpr uint32_t kSlotBits = 3;                  // b + R: 0..6
-constexpr size_t kBulgePieceQueries = size_t(1) << 19; // 19 bits of query + 41 of position + 1 of strand + 3 of bulge = one word
 
 static_assert(sizeof(issl_search_bulges) == 16 && sizeof(issl_bulge_hit) == 32, "the layouts of include/issl_hip.h");
 
@@ -102,15 +93,10 @@ __global__ __launch_bounds__(256) void k_bulge(const uint8_t *__restrict__ s, ui
     }
     __syncthreads();
     const uint32_t n_q = q_count;
-
-    // -- every survivor against every query, as k_search walks them: a lane holds one survivor, a wave a quarter of the
-    // queries
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t q_lo = static_cast<uint32_t>(static_cast<uint64_t>(n) * wave / 4);
-    const uint32_t q_hi = static_cast<uint32_t>(static_cast<uint64_t>(n) * (wave + 1) / 4);
+    const QueryRange mine_q = wave_queries(n);
     const uint32_t limit = a.max_dist;
-    unsigned long long found = 0;             // kCount: the rows of this lane's survivors
-    for (uint32_t j0 = 0; j0 < n_q && q_lo < q_hi; j0 += 64) {
+    unsigned long long found = 0; // kCount: the rows of this lane's survivors
+    for (uint32_t j0 = 0; j0 < n_q && mine_q.lo < mine_q.hi; j0 += 64) {
         const uint32_t j = j0 + lane;
         const bool valid = j < n_q;
         uint32_t tag = 0;
@@ -143,46 +129,25 @@ __global__ __launch_bounds__(256) void k_bulge(const uint8_t *__restrict__ s, ui
             }
             const uint64_t who = __ballot(hit);
             if (!who) return;
-            if (kMode == kEmit) {
-                const uint32_t before = lanes_before(who);
-                const int first = __ffsll(static_cast<unsigned long long>(who)) - 1;
-                unsigned long long at = 0;
-                if (static_cast<int>(lane) == first) at = atomicAdd(ctr + 1, static_cast<unsigned long long>(__popcll(who)));
-                at = __shfl(at, first, 64) + before;
-                if (hit && at < cap)
-                    words[at] = (static_cast<uint64_t>(qi) << (pos_bits + 1 + kSlotBits)) | ((base + (tag >> 1)) << (1 + kSlotBits)) |
-                                (static_cast<uint64_t>(tag & 1u) << kSlotBits) | ba.slot;
-            } else {
-                uint64_t left = who;
-                while (left) { // one atomic per distance that occurs among the wave's rows
-                    const int first = __ffsll(static_cast<unsigned long long>(left)) - 1;
-                    const uint32_t d = __shfl(dist, first, 64);
-                    const uint64_t same = __ballot(hit && dist == d);
-                    if (static_cast<int>(lane) == first)
-                        atomicAdd(&counts[(static_cast<uint64_t>(qi) * ba.slots + ba.slot) * (a.max_dist + 1) + d],
-                                  static_cast<unsigned long long>(__popcll(same)));
-                    left &= ~same;
-                }
-            }
+            if (kMode == kEmit) emit_hits<kSlotBits>(who, hit, lane, ctr, words, cap, qi, pos_bits, base, tag, ba.slot);
+            else profile_hits(who, hit, dist, lane, counts, static_cast<uint64_t>(qi) * ba.slots + ba.slot, a.max_dist + 1);
         };
-        // kQueryGroup queries come in with one wait, the group behind them is on its way (k_search's fetch); the group's
-        // bounds share one comparison and one branch
-        uint32_t qi = q_lo;
-        if (q_hi - q_lo >= kQueryGroup) {
+        // the group's bounds share one comparison and one branch
+        uint32_t qi = mine_q.lo;
+        if (mine_q.hi - mine_q.lo >= kQueryGroup) {
             QueryGroup next = *reinterpret_cast<const QueryGroup *>(q + qi);
-            for (; qi + kQueryGroup <= q_hi; qi += kQueryGroup) {
+            for (; qi + kQueryGroup <= mine_q.hi; qi += kQueryGroup) {
                 const QueryGroup group = next;
-                if (qi + 2 * kQueryGroup <= q_hi) next = *reinterpret_cast<const QueryGroup *>(q + qi + kQueryGroup);
+                if (qi + 2 * kQueryGroup <= mine_q.hi) next = *reinterpret_cast<const QueryGroup *>(q + qi + kQueryGroup);
                 uint32_t least = ~0u;
 #pragma unroll
-                for (uint32_t u = 0; u < kQueryGroup; ++u)
-                    least = min(least, bound(group.q[u]));
+                for (uint32_t u = 0; u < kQueryGroup; ++u) least = min(least, bound(group.q[u]));
                 if (!(__ballot(least <= limit) & live)) continue;
 #pragma unroll
                 for (uint32_t u = 0; u < kQueryGroup; ++u) walk(group.q[u], qi + u);
             }
         }
-        for (; qi < q_hi; ++qi) walk(q[qi], qi);
+        for (; qi < mine_q.hi; ++qi) walk(q[qi], qi);
         if (kMode == kCount && valid) found += mine;
     }
     if (kMode == kCount) {
@@ -252,153 +217,42 @@ template <class F> void for_each_launch(const issl_genome *g, const BulgeCall &c
         if (g->len >= c.a[k].length) f(c.a[k], c.b[k]);
 }
 
-bool nothing_to_search(const issl_genome *g, const BulgeCall &c, size_t n)
-{
-    bool any = false;
-    for_each_launch(g, c, [&](const SearchArgs &, const BulgeArgs &) { any = true; });
-    return n == 0 || !any;
-}
+// The unit as SearchDriver takes it (issl_search_device.hpp): the launches of b where the plain search has one, three bits
+// of b + R below the strand.
+struct BulgeSearch {
+    using Row = issl_bulge_hit;
+    using Call = BulgeCall;
+    static constexpr size_t kPieceQueries = size_t(1) << 19; // 19 bits of query + 41 of position + 1 of strand + 3 of bulge = one word
+    static constexpr uint32_t kLowBits = kSlotBits;
+    static constexpr const char *kTag = "[issl bulges]", *kRows = "rows";
+    static std::string counted(const Call &c) { return ", " + std::to_string(c.n_launches) + " bulges"; }
+    static bool nothing(const issl_genome *g, const Call &c, size_t n)
+    {
+        bool any = false;
+        for_each_launch(g, c, [&](const SearchArgs &, const BulgeArgs &) { any = true; });
+        return n == 0 || !any;
+    }
+    static size_t bins(const Call &c) { return static_cast<size_t>(c.bg.max_rna + c.bg.max_dna + 1) * (c.max_dist + 1); }
 
-struct BulgePiece {
-    Arena hit;
-    uint64_t n_words = 0;
-    const uint64_t *words = nullptr; // sorted: query | text position | strand | b + R
-};
-
-// Everything of a piece of n <= 2^19 queries but the rows: d_offsets[0..n] = base + the piece's offsets.
-int bulge_piece(const issl_genome *g, const BulgeCall &c, const issl_search_query *d_q, uint32_t n, uint64_t base, uint64_t *d_offsets,
-                hipStream_t stream, BulgePiece &pc)
-{
-    StageTimer clock(g->timing, stream);
-    DevBuf ctrb;
-    HIP_TRY(hipMalloc(&ctrb.p, 64));
-    unsigned long long *ctr = static_cast<unsigned long long *>(ctrb.p);
-    HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
-    const uint8_t *d_seq = static_cast<const uint8_t *>(g->seq.p);
-    const uint32_t blocks = text_blocks(g);
-    for_each_launch(g, c, [&](const SearchArgs &a, const BulgeArgs &b) {
-        launch_bulge<kCount>(b.r != 0, blocks, stream, d_seq, g->len, a, b, d_q, n, g->pos_bits, ctr,
-                           static_cast<uint64_t *>(nullptr), 0ull, static_cast<unsigned long long *>(nullptr));
-    });
-    HIP_TRY(hipGetLastError());
-    unsigned long long seen[4] = {};
-    HIP_TRY(hipMemcpyAsync(seen, ctr, sizeof seen, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    clock.note("count");
-    pc.n_words = seen[0];
-    if (pc.n_words > 0xFFFFFFFFull) return too_many(pc.n_words); // the radix passes place with 32-bit offsets
-    const uint32_t shift = g->pos_bits + 1 + kSlotBits;
-    if (pc.n_words) {
-        Arena &ha = pc.hit;
-        const size_t o_ha = ha.reserve(8 * pc.n_words), o_hb = ha.reserve(8 * pc.n_words),
-                     o_hh = ha.reserve(4 * radix_hist_words(radix_sort_blocks(pc.n_words)));
-        HIP_TRY(hipMalloc(&ha.buf.p, ha.size));
-        uint64_t *ha_w = ha.at<uint64_t>(o_ha), *hb_w = ha.at<uint64_t>(o_hb);
+    template <int kMode>
+    static void launch(const issl_genome *g, const Call &c, const issl_search_query *d_q, uint32_t n, unsigned long long *ctr, uint64_t *words,
+                       uint64_t cap, unsigned long long *counts, hipStream_t stream)
+    {
         for_each_launch(g, c, [&](const SearchArgs &a, const BulgeArgs &b) {
-            launch_bulge<kEmit>(b.r != 0, blocks, stream, d_seq, g->len, a, b, d_q, n, g->pos_bits, ctr, ha_w,
-                               pc.n_words, static_cast<unsigned long long *>(nullptr));
+            launch_bulge<kMode>(b.r != 0, text_blocks(g), stream, static_cast<const uint8_t *>(g->seq.p), g->len, a, b, d_q, n, g->pos_bits, ctr,
+                                words, cap, counts);
         });
-        clock.note("emit");
-        pc.words = radix_sort_async(ha_w, hb_w, pc.n_words, 0, shift + bits_for(n), ha.at<uint32_t>(o_hh), stream);
-        clock.note("sort");
     }
-    hipLaunchKernelGGL(k_search_offsets, dim3(n / 256 + 1), dim3(256), 0, stream, pc.words, static_cast<uint32_t>(pc.n_words), shift, n,
-                       base, d_offsets);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    clock.note("offsets");
-    if (g->timing)
-        std::fprintf(stderr, "[issl bulges] %u queries, %u bulges:%s | windows %llu admitted %llu rows %llu\n", n, c.n_launches,
-                     clock.line.c_str(), seen[3], seen[2], seen[0]);
-    return ISSL_OK;
-}
 
-// The piece's rows to d_rows[0 .. pc.n_words).  Returns when they are written.
-int bulge_finish(const issl_genome *g, const BulgeCall &c, const BulgePiece &pc, const issl_search_query *d_q, uint32_t q_base,
-                 issl_bulge_hit *d_rows, hipStream_t stream)
-{
-    if (pc.n_words == 0) return ISSL_OK;
-    StageTimer clock(g->timing, stream);
-    const uint32_t total = static_cast<uint32_t>(pc.n_words);
-    hipLaunchKernelGGL(k_bulge_finish, dim3((total + 255) / 256), dim3(256), 0, stream, pc.words, total,
-                       static_cast<const uint8_t *>(g->seq.p), c.length, c.bg, c.max_dist, d_q, q_base,
-                       static_cast<const uint64_t *>(g->starts.p), static_cast<uint32_t>(g->records.size()), g->pos_bits,
-                       reinterpret_cast<uint64_t *>(d_rows));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    clock.note("finish");
-    if (g->timing) std::fprintf(stderr, "[issl bulges]%s\n", clock.line.c_str());
-    return ISSL_OK;
-}
-
-// search_run of issl_search.hip for the bulged rows: queries and offsets in device memory; the rows go to device memory
-// (`hits`) or, rows_to_host, piece by piece through a device buffer of the piece's size into host memory.
-int bulge_run(issl_genome *g, const BulgeCall &c, const issl_search_query *d_q, size_t n, uint64_t *d_offsets, issl_bulge_hit *hits,
-              bool rows_to_host, size_t cap, size_t *n_total, hipStream_t stream)
-{
-    *n_total = 0;
-    if (nothing_to_search(g, c, n)) {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8 * (n + 1), stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return ISSL_OK;
+    static void finish(const issl_genome *g, const Call &c, const uint64_t *words, uint32_t total, const issl_search_query *d_q,
+                       uint32_t q_base, uint64_t *rows, hipStream_t stream)
+    {
+        hipLaunchKernelGGL(k_bulge_finish, dim3((total + 255) / 256), dim3(256), 0, stream, words, total,
+                           static_cast<const uint8_t *>(g->seq.p), c.length, c.bg, c.max_dist, d_q, q_base,
+                           static_cast<const uint64_t *>(g->starts.p), static_cast<uint32_t>(g->records.size()), g->pos_bits, rows);
     }
-    auto rows_of = [&](const BulgePiece &pc, size_t at, uint64_t base) -> int {
-        if (!rows_to_host) return bulge_finish(g, c, pc, d_q + at, static_cast<uint32_t>(at), hits + base, stream);
-        if (pc.n_words == 0) return ISSL_OK;
-        DevBuf d_rows;
-        HIP_TRY(hipMalloc(&d_rows.p, sizeof(issl_bulge_hit) * pc.n_words));
-        if (int rc = bulge_finish(g, c, pc, d_q + at, static_cast<uint32_t>(at), static_cast<issl_bulge_hit *>(d_rows.p), stream)) return rc;
-        HIP_TRY(hipMemcpy(hits + base, d_rows.p, sizeof(issl_bulge_hit) * pc.n_words, hipMemcpyDeviceToHost));
-        return ISSL_OK;
-    };
-    // Counting pass over the pieces; a single piece is finished from what that pass left, several are run once more.
-    std::vector<uint64_t> bases;
-    uint64_t total = 0;
-    for (size_t at = 0; at < n; at += kBulgePieceQueries) {
-        const uint32_t cnt = static_cast<uint32_t>(std::min(kBulgePieceQueries, n - at));
-        BulgePiece pc;
-        bases.push_back(total);
-        if (int rc = bulge_piece(g, c, d_q + at, cnt, total, d_offsets + at, stream, pc)) return rc;
-        total += pc.n_words;
-        if (total > 0xFFFFFFFFull) return too_many(total);
-        if (n <= kBulgePieceQueries && hits && total <= cap)
-            if (int rc = rows_of(pc, at, 0)) return rc;
-    }
-    *n_total = total;
-    if (n <= kBulgePieceQueries || !hits || total > cap) return ISSL_OK;
-    for (size_t at = 0, k = 0; at < n; at += kBulgePieceQueries, ++k) {
-        const uint32_t cnt = static_cast<uint32_t>(std::min(kBulgePieceQueries, n - at));
-        BulgePiece pc;
-        if (int rc = bulge_piece(g, c, d_q + at, cnt, bases[k], d_offsets + at, stream, pc)) return rc;
-        if (int rc = rows_of(pc, at, bases[k])) return rc;
-    }
-    return ISSL_OK;
-}
-
-size_t profile_bins(const BulgeCall &c) { return static_cast<size_t>(c.bg.max_rna + c.bg.max_dna + 1) * (c.max_dist + 1); }
-
-int bulge_profile_run(issl_genome *g, const BulgeCall &c, const issl_search_query *d_q, size_t n, uint64_t *d_counts, hipStream_t stream)
-{
-    if (n == 0) return ISSL_OK;
-    const size_t bins = profile_bins(c);
-    HIP_TRY(hipMemsetAsync(d_counts, 0, 8 * n * bins, stream));
-    if (!nothing_to_search(g, c, n)) {
-        StageTimer clock(g->timing, stream);
-        for (size_t at = 0; at < n; at += kBulgePieceQueries) {
-            const uint32_t cnt = static_cast<uint32_t>(std::min(kBulgePieceQueries, n - at));
-            for_each_launch(g, c, [&](const SearchArgs &a, const BulgeArgs &b) {
-                launch_bulge<kProfile>(b.r != 0, text_blocks(g), stream, static_cast<const uint8_t *>(g->seq.p),
-                                   g->len, a, b, d_q + at, cnt, g->pos_bits, static_cast<unsigned long long *>(nullptr),
-                                   static_cast<uint64_t *>(nullptr), 0ull, reinterpret_cast<unsigned long long *>(d_counts + at * bins));
-            });
-            HIP_TRY(hipGetLastError());
-            clock.note("profile");
-        }
-        if (g->timing) std::fprintf(stderr, "[issl bulges] %zu queries:%s\n", n, clock.line.c_str());
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    return ISSL_OK;
-}
+};
+using Bulged = SearchDriver<BulgeSearch>;
 
 // The checks every entry point makes before any device work.  ISSL_OK: *c holds the launches.
 int check_bulge_call(const issl_search_pattern *pat, const issl_search_bulges *bg, int max_dist, size_t n, BulgeCall *c)
@@ -434,15 +288,7 @@ int issl_genome_search_bulges(issl_genome *g, const issl_search_pattern *pat, co
     return issl::abi_call([&]() -> int {
         issl::BulgeCall c;
         if (int rc = issl::check_bulge_call(pat, bulges, max_dist, n, &c)) return rc;
-        if (int rc = issl::check_host_queries(queries, n, pat->length)) return rc;
-        issl::DevBuf d_q, d_offs;
-        if (int rc = issl::upload_queries(g, queries, n, d_q)) return rc;
-        HIP_TRY(hipMalloc(&d_offs.p, 8 * (n + 1)));
-        if (int rc = issl::bulge_run(g, c, static_cast<const issl_search_query *>(d_q.p), n, static_cast<uint64_t *>(d_offs.p), hits, true, cap,
-                                     n_total, nullptr))
-            return rc;
-        HIP_TRY(hipMemcpy(offsets, d_offs.p, 8 * (n + 1), hipMemcpyDeviceToHost));
-        return ISSL_OK;
+        return issl::Bulged::host_rows(g, c, pat->length, queries, n, offsets, hits, cap, n_total);
     });
 }
 
@@ -455,8 +301,7 @@ int issl_genome_search_bulges_device(issl_genome *g, const issl_search_pattern *
     return issl::abi_call([&]() -> int {
         issl::BulgeCall c;
         if (int rc = issl::check_bulge_call(pat, bulges, max_dist, n, &c)) return rc;
-        HIP_TRY(hipSetDevice(g->device));
-        return issl::bulge_run(g, c, d_queries, n, d_offsets, d_hits, false, cap, n_total, static_cast<hipStream_t>(stream));
+        return issl::Bulged::device_rows(g, c, d_queries, n, d_offsets, d_hits, cap, n_total, stream);
     });
 }
 
@@ -467,16 +312,7 @@ int issl_genome_search_bulges_profile(issl_genome *g, const issl_search_pattern 
     return issl::abi_call([&]() -> int {
         issl::BulgeCall c;
         if (int rc = issl::check_bulge_call(pat, bulges, max_dist, n, &c)) return rc;
-        if (int rc = issl::check_host_queries(queries, n, pat->length)) return rc;
-        if (n == 0) return ISSL_OK;
-        issl::DevBuf d_q, d_counts;
-        if (int rc = issl::upload_queries(g, queries, n, d_q)) return rc;
-        const size_t bytes = 8 * n * issl::profile_bins(c);
-        HIP_TRY(hipMalloc(&d_counts.p, bytes));
-        if (int rc = issl::bulge_profile_run(g, c, static_cast<const issl_search_query *>(d_q.p), n, static_cast<uint64_t *>(d_counts.p), nullptr))
-            return rc;
-        HIP_TRY(hipMemcpy(counts, d_counts.p, bytes, hipMemcpyDeviceToHost));
-        return ISSL_OK;
+        return issl::Bulged::host_profile(g, c, pat->length, queries, n, counts);
     });
 }
 
@@ -487,8 +323,7 @@ int issl_genome_search_bulges_profile_device(issl_genome *g, const issl_search_p
     return issl::abi_call([&]() -> int {
         issl::BulgeCall c;
         if (int rc = issl::check_bulge_call(pat, bulges, max_dist, n, &c)) return rc;
-        HIP_TRY(hipSetDevice(g->device));
-        return issl::bulge_profile_run(g, c, d_queries, n, d_counts, static_cast<hipStream_t>(stream));
+        return issl::Bulged::device_profile(g, c, d_queries, n, d_counts, stream);
     });
 }
 

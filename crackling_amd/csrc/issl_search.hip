@@ -1,42 +1,18 @@
 // Genome search: where a query binds with at most max_dist mismatches, for any PAM pattern and any length up to 32
 // (issl_genome_search*, include/issl_hip.h).  No index: the resident text of a genome handle (issl_genome_handle.hpp) is
-// compared with every query.
-//
-// One piece of up to 2^22 queries, everything on one stream, the protocol of issl_locate.hip:
-//   count    k_search<kCount> on the text grid of k_match_* (4096 positions per 256-thread workgroup).  The tile and its
-//            halo go to LDS as 2-bit codes and one validity bit per base, 16 bases per word; a thread cuts its 16 windows
-//            out of three words, tests the pattern on both strands and keeps a bit per window-strand that passes.  The
-//            survivors of the workgroup are compacted into an LDS queue of 13-bit tags (one wave scan and one LDS atomic
-//            per wave), so that the comparison runs on full waves: a lane holds one survivor's packed word and walks
-//            the queries, whose sig and care are wave-uniform and come through scalar loads, kQueryGroup of them per
-//            load and one group ahead; each of the four waves takes all survivors against a quarter of the queries.
-//            Hits are only counted
-//   emit     the same kernel, k_search<kEmit>: a hit is one word query | text position | strand, room reserved with one
-//            atomic per wave and query that has a hit.  The order in the buffer does not matter
-//   sort     radix sort of the words over the bits in use: query-major, then position, then strand -- which is
-//            (record, pos, strand), records being laid out in ascending order.  No two words are equal, so the sorted
-//            buffer is the same on every run
-//   offsets  k_search_offsets: query k's rows start at the first word of a query >= k (a binary search per query; a
-//            query named twice is compared twice and owns its own rows, so there are no ranks to resolve)
-//   finish   k_search_finish: one thread per row re-reads the window and writes site, mism, dist and the record
-// The profile is k_search<kProfile>: one pass, a hit adds to counts[query][dist] with one atomic per wave, query and
-// distance; no row exists anywhere.
-// The host waits for the number of hit words (sizes the buffers of the sort) and for the end of a piece.
-// pack16, the offsets kernel and the argument checks are issl_search_device.hpp's: issl_bulge.hip takes them too.
+// compared with every query.  The protocol -- count, emit, sort, offsets, finish, and the profile -- is that of
+// issl_search_core.hpp, its host side SearchDriver<PlainSearch> (issl_search_device.hpp); issl_bulge.hip follows it too.
+// This unit's own: k_search's comparison, one distance per survivor and query; a hit word is query | text position |
+// strand with nothing below; k_search_finish writes site, mism, dist and the record of a row.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/issl_hip.h"
 #include "issl_genome_handle.hpp"
 #include "issl_host.hpp"
 #include "issl_match.hpp"
-#include "issl_radix.hpp"
-#include "issl_search_device.hpp"
+#include "issl_search_core.hpp"
 #include "issl_search_text.hpp"
 
 namespace issl {
@@ -48,7 +24,6 @@ using search_text::gather_even_bits;
 using search_text::mismatches;
 using search_text::reverse_complement;
 using search_text::window_word;
-constexpr size_t kPieceQueries = size_t(1) << 22;       // 22 bits of query + 41 of position + 1 of strand = one word
 
 // ctr[0]: hits; ctr[1]: the cursor of k_search<kEmit>; ctr[2]: window-strands the pattern admits; ctr[3]: windows of L
 // bases A C G T (the figures of the timing line, kCount only).
@@ -104,14 +79,10 @@ __global__ __launch_bounds__(256) void k_search(const uint8_t *__restrict__ s, u
     __syncthreads();
     const uint32_t n_q = q_count;
 
-    // -- every survivor against every query: a lane holds one survivor.  Every wave walks all the survivors, 64 at a time,
-    // against its quarter of the queries: the four waves end together whatever the number of survivors is (with a
-    // quarter of the survivors each, 530 of them cost a workgroup three rounds where the other waves had two)
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // (uniform: the queries come through scalar loads)
-    const uint32_t q_lo = static_cast<uint32_t>(static_cast<uint64_t>(n) * wave / 4);
-    const uint32_t q_hi = static_cast<uint32_t>(static_cast<uint64_t>(n) * (wave + 1) / 4);
+    // -- every survivor against every query: a lane holds one survivor, a wave its quarter of the queries
+    const QueryRange mine_q = wave_queries(n);
     unsigned long long found = 0; // kCount: the hits of this lane's survivors
-    for (uint32_t j0 = 0; j0 < n_q && q_lo < q_hi; j0 += 64) {
+    for (uint32_t j0 = 0; j0 < n_q && mine_q.lo < mine_q.hi; j0 += 64) {
         const uint32_t j = j0 + lane;
         const bool valid = j < n_q;
         uint32_t tag = 0;
@@ -134,42 +105,25 @@ __global__ __launch_bounds__(256) void k_search(const uint8_t *__restrict__ s, u
             const uint64_t who = __ballot(dist <= a.max_dist) & live; // (no branch around the lanes without a survivor)
             if (!who) return;
             const bool hit = (who >> lane) & 1u;
-            if (kMode == kEmit) {
-                const uint32_t before = lanes_before(who);
-                const int first = __ffsll(static_cast<unsigned long long>(who)) - 1;
-                unsigned long long at = 0;
-                if (static_cast<int>(lane) == first) at = atomicAdd(ctr + 1, static_cast<unsigned long long>(__popcll(who)));
-                at = __shfl(at, first, 64) + before;
-                if (hit && at < cap)
-                    words[at] = (static_cast<uint64_t>(qi) << (pos_bits + 1)) | ((base + (tag >> 1)) << 1) | (tag & 1u);
-            } else {
-                uint64_t left = who;
-                while (left) { // one atomic per distance that occurs among the wave's hits
-                    const int first = __ffsll(static_cast<unsigned long long>(left)) - 1;
-                    const uint32_t d = __shfl(dist, first, 64);
-                    const uint64_t same = __ballot(hit && dist == d);
-                    if (static_cast<int>(lane) == first)
-                        atomicAdd(&counts[static_cast<uint64_t>(qi) * (a.max_dist + 1) + d], static_cast<unsigned long long>(__popcll(same)));
-                    left &= ~same;
-                }
-            }
+            if (kMode == kEmit) emit_hits<0>(who, hit, lane, ctr, words, cap, qi, pos_bits, base, tag, 0);
+            else profile_hits(who, hit, dist, lane, counts, qi, a.max_dist + 1);
         };
         // kQueryGroup queries come in with one wait: a scalar load per query and a wait behind each left a wave idle for
         // the scalar cache's latency once per 11 vector instructions
         // the group behind the one being compared is on its way.  (Two groups ping-ponging in registers of their own
         // would save the scalar copies, but scalar loads return out of order: the wait for one group is a wait for
         // both, and the compiler put it right behind the younger load.)
-        uint32_t qi = q_lo;
-        if (q_hi - q_lo >= kQueryGroup) {
+        uint32_t qi = mine_q.lo;
+        if (mine_q.hi - mine_q.lo >= kQueryGroup) {
             QueryGroup next = *reinterpret_cast<const QueryGroup *>(q + qi);
-            for (; qi + kQueryGroup <= q_hi; qi += kQueryGroup) {
+            for (; qi + kQueryGroup <= mine_q.hi; qi += kQueryGroup) {
                 const QueryGroup group = next;
-                if (qi + 2 * kQueryGroup <= q_hi) next = *reinterpret_cast<const QueryGroup *>(q + qi + kQueryGroup);
+                if (qi + 2 * kQueryGroup <= mine_q.hi) next = *reinterpret_cast<const QueryGroup *>(q + qi + kQueryGroup);
 #pragma unroll
                 for (uint32_t u = 0; u < kQueryGroup; ++u) compare(group.q[u], qi + u);
             }
         }
-        for (; qi < q_hi; ++qi) compare(q[qi], qi);
+        for (; qi < mine_q.hi; ++qi) compare(q[qi], qi);
         if (kMode == kCount && valid) found += mine;
     }
     if (kMode == kCount) {
@@ -209,141 +163,35 @@ __global__ __launch_bounds__(256) void k_search_finish(const uint64_t *__restric
     row[3] = gather_even_bits(m) | (static_cast<uint64_t>(strand) << 32) | (static_cast<uint64_t>(__popcll(m)) << 40);
 }
 
-// ---- host --------------------------------------------------------------------------------------------------------
+// ---- host: the unit as SearchDriver takes it (issl_search_device.hpp) ----------------------------------------------------
 
-bool nothing_to_search(const issl_genome *g, const SearchArgs &a, size_t n) { return n == 0 || g->len < a.length; }
+struct PlainSearch {
+    using Row = issl_search_hit;
+    using Call = SearchArgs;
+    static constexpr size_t kPieceQueries = size_t(1) << 22; // 22 bits of query + 41 of position + 1 of strand = one word
+    static constexpr uint32_t kLowBits = 0;
+    static constexpr const char *kTag = "[issl search]", *kRows = "hits";
+    static std::string counted(const Call &) { return ""; }
+    static bool nothing(const issl_genome *g, const Call &a, size_t n) { return n == 0 || g->len < a.length; }
+    static size_t bins(const Call &a) { return a.max_dist + 1; }
 
-struct SearchPiece {
-    Arena hit;
-    uint64_t n_words = 0;
-    const uint64_t *words = nullptr; // sorted: query << (pos_bits + 1) | text position << 1 | strand
+    template <int kMode>
+    static void launch(const issl_genome *g, const Call &a, const issl_search_query *d_q, uint32_t n, unsigned long long *ctr, uint64_t *words,
+                       uint64_t cap, unsigned long long *counts, hipStream_t stream)
+    {
+        hipLaunchKernelGGL(k_search<kMode>, dim3(text_blocks(g)), dim3(256), 0, stream, static_cast<const uint8_t *>(g->seq.p), g->len, a, d_q,
+                           n, g->pos_bits, ctr, words, cap, counts);
+    }
+
+    static void finish(const issl_genome *g, const Call &a, const uint64_t *words, uint32_t total, const issl_search_query *d_q,
+                       uint32_t q_base, uint64_t *rows, hipStream_t stream)
+    {
+        hipLaunchKernelGGL(k_search_finish, dim3((total + 255) / 256), dim3(256), 0, stream, words, total,
+                           static_cast<const uint8_t *>(g->seq.p), a, d_q, q_base, static_cast<const uint64_t *>(g->starts.p),
+                           static_cast<uint32_t>(g->records.size()), g->pos_bits, rows);
+    }
 };
-
-// Everything of a piece of n <= 2^22 queries but the rows: d_offsets[0..n] = base + the piece's offsets.
-int search_piece(const issl_genome *g, const SearchArgs &a, const issl_search_query *d_q, uint32_t n, uint64_t base,
-                 uint64_t *d_offsets, hipStream_t stream, SearchPiece &pc)
-{
-    StageTimer clock(g->timing, stream);
-    DevBuf ctrb;
-    HIP_TRY(hipMalloc(&ctrb.p, 64));
-    unsigned long long *ctr = static_cast<unsigned long long *>(ctrb.p);
-    HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
-    const uint8_t *d_seq = static_cast<const uint8_t *>(g->seq.p);
-    const uint32_t blocks = text_blocks(g);
-    hipLaunchKernelGGL(k_search<kCount>, dim3(blocks), dim3(256), 0, stream, d_seq, g->len, a, d_q, n, g->pos_bits, ctr,
-                       static_cast<uint64_t *>(nullptr), 0ull, static_cast<unsigned long long *>(nullptr));
-    HIP_TRY(hipGetLastError());
-    unsigned long long seen[4] = {};
-    HIP_TRY(hipMemcpyAsync(seen, ctr, sizeof seen, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    clock.note("count");
-    pc.n_words = seen[0];
-    if (pc.n_words > 0xFFFFFFFFull) return too_many(pc.n_words); // the radix passes place with 32-bit offsets
-    const uint32_t shift = g->pos_bits + 1;
-    if (pc.n_words) {
-        Arena &ha = pc.hit;
-        const size_t o_ha = ha.reserve(8 * pc.n_words), o_hb = ha.reserve(8 * pc.n_words),
-                     o_hh = ha.reserve(4 * radix_hist_words(radix_sort_blocks(pc.n_words)));
-        HIP_TRY(hipMalloc(&ha.buf.p, ha.size));
-        uint64_t *ha_w = ha.at<uint64_t>(o_ha), *hb_w = ha.at<uint64_t>(o_hb);
-        hipLaunchKernelGGL(k_search<kEmit>, dim3(blocks), dim3(256), 0, stream, d_seq, g->len, a, d_q, n, g->pos_bits, ctr, ha_w,
-                           pc.n_words, static_cast<unsigned long long *>(nullptr));
-        clock.note("emit");
-        pc.words = radix_sort_async(ha_w, hb_w, pc.n_words, 0, shift + bits_for(n), ha.at<uint32_t>(o_hh), stream);
-        clock.note("sort");
-    }
-    hipLaunchKernelGGL(k_search_offsets, dim3(n / 256 + 1), dim3(256), 0, stream, pc.words, static_cast<uint32_t>(pc.n_words), shift, n,
-                       base, d_offsets);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    clock.note("offsets");
-    if (g->timing)
-        std::fprintf(stderr, "[issl search] %u queries:%s | windows %llu admitted %llu hits %llu\n", n, clock.line.c_str(), seen[3],
-                     seen[2], seen[0]);
-    return ISSL_OK;
-}
-
-// The piece's rows to d_rows[0 .. pc.n_words).  Returns when they are written.
-int search_finish(const issl_genome *g, const SearchArgs &a, const SearchPiece &pc, const issl_search_query *d_q, uint32_t q_base,
-                  issl_search_hit *d_rows, hipStream_t stream)
-{
-    if (pc.n_words == 0) return ISSL_OK;
-    StageTimer clock(g->timing, stream);
-    const uint32_t total = static_cast<uint32_t>(pc.n_words);
-    hipLaunchKernelGGL(k_search_finish, dim3((total + 255) / 256), dim3(256), 0, stream, pc.words, total,
-                       static_cast<const uint8_t *>(g->seq.p), a, d_q, q_base, static_cast<const uint64_t *>(g->starts.p),
-                       static_cast<uint32_t>(g->records.size()), g->pos_bits, reinterpret_cast<uint64_t *>(d_rows));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    clock.note("finish");
-    if (g->timing) std::fprintf(stderr, "[issl search]%s\n", clock.line.c_str());
-    return ISSL_OK;
-}
-
-// Queries and offsets in device memory; the rows go to device memory (`hits`) or, rows_to_host, piece by piece through a
-// device buffer of the piece's size into host memory.
-int search_run(issl_genome *g, const SearchArgs &a, const issl_search_query *d_q, size_t n, uint64_t *d_offsets, issl_search_hit *hits,
-               bool rows_to_host, size_t cap, size_t *n_total, hipStream_t stream)
-{
-    *n_total = 0;
-    if (nothing_to_search(g, a, n)) {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8 * (n + 1), stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return ISSL_OK;
-    }
-    auto rows_of = [&](const SearchPiece &pc, size_t at, uint64_t base) -> int {
-        if (!rows_to_host) return search_finish(g, a, pc, d_q + at, static_cast<uint32_t>(at), hits + base, stream);
-        if (pc.n_words == 0) return ISSL_OK;
-        DevBuf d_rows;
-        HIP_TRY(hipMalloc(&d_rows.p, sizeof(issl_search_hit) * pc.n_words));
-        if (int rc = search_finish(g, a, pc, d_q + at, static_cast<uint32_t>(at), static_cast<issl_search_hit *>(d_rows.p), stream)) return rc;
-        HIP_TRY(hipMemcpy(hits + base, d_rows.p, sizeof(issl_search_hit) * pc.n_words, hipMemcpyDeviceToHost));
-        return ISSL_OK;
-    };
-    // Counting pass over the pieces; a single piece is finished from what that pass left, several are run once more.
-    std::vector<uint64_t> bases;
-    uint64_t total = 0;
-    for (size_t at = 0; at < n; at += kPieceQueries) {
-        const uint32_t cnt = static_cast<uint32_t>(std::min(kPieceQueries, n - at));
-        SearchPiece pc;
-        bases.push_back(total);
-        if (int rc = search_piece(g, a, d_q + at, cnt, total, d_offsets + at, stream, pc)) return rc;
-        total += pc.n_words;
-        if (total > 0xFFFFFFFFull) return too_many(total);
-        if (n <= kPieceQueries && hits && total <= cap)
-            if (int rc = rows_of(pc, at, 0)) return rc;
-    }
-    *n_total = total;
-    if (n <= kPieceQueries || !hits || total > cap) return ISSL_OK;
-    for (size_t at = 0, k = 0; at < n; at += kPieceQueries, ++k) {
-        const uint32_t cnt = static_cast<uint32_t>(std::min(kPieceQueries, n - at));
-        SearchPiece pc;
-        if (int rc = search_piece(g, a, d_q + at, cnt, bases[k], d_offsets + at, stream, pc)) return rc;
-        if (int rc = rows_of(pc, at, bases[k])) return rc;
-    }
-    return ISSL_OK;
-}
-
-int profile_run(issl_genome *g, const SearchArgs &a, const issl_search_query *d_q, size_t n, uint64_t *d_counts, hipStream_t stream)
-{
-    if (n == 0) return ISSL_OK;
-    const size_t bins = a.max_dist + 1;
-    HIP_TRY(hipMemsetAsync(d_counts, 0, 8 * n * bins, stream));
-    if (!nothing_to_search(g, a, n)) {
-        StageTimer clock(g->timing, stream);
-        for (size_t at = 0; at < n; at += kPieceQueries) {
-            const uint32_t cnt = static_cast<uint32_t>(std::min(kPieceQueries, n - at));
-            hipLaunchKernelGGL(k_search<kProfile>, dim3(text_blocks(g)), dim3(256), 0, stream, static_cast<const uint8_t *>(g->seq.p),
-                               g->len, a, d_q + at, cnt, g->pos_bits, static_cast<unsigned long long *>(nullptr),
-                               static_cast<uint64_t *>(nullptr), 0ull, reinterpret_cast<unsigned long long *>(d_counts + at * bins));
-            HIP_TRY(hipGetLastError());
-            clock.note("profile");
-        }
-        if (g->timing) std::fprintf(stderr, "[issl search] %zu queries:%s\n", n, clock.line.c_str());
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    return ISSL_OK;
-}
+using Plain = SearchDriver<PlainSearch>;
 
 } // namespace
 } // namespace issl
@@ -368,15 +216,7 @@ int issl_genome_search(issl_genome *g, const issl_search_pattern *pat, const iss
     return issl::abi_call([&]() -> int {
         issl::SearchArgs a;
         if (int rc = issl::check_call(pat, max_dist, n, &a)) return rc;
-        if (int rc = issl::check_host_queries(queries, n, pat->length)) return rc;
-        issl::DevBuf d_q, d_offs;
-        if (int rc = issl::upload_queries(g, queries, n, d_q)) return rc;
-        HIP_TRY(hipMalloc(&d_offs.p, 8 * (n + 1)));
-        if (int rc = issl::search_run(g, a, static_cast<const issl_search_query *>(d_q.p), n, static_cast<uint64_t *>(d_offs.p), hits, true,
-                                      cap, n_total, nullptr))
-            return rc;
-        HIP_TRY(hipMemcpy(offsets, d_offs.p, 8 * (n + 1), hipMemcpyDeviceToHost));
-        return ISSL_OK;
+        return issl::Plain::host_rows(g, a, pat->length, queries, n, offsets, hits, cap, n_total);
     });
 }
 
@@ -387,8 +227,7 @@ int issl_genome_search_device(issl_genome *g, const issl_search_pattern *pat, co
     return issl::abi_call([&]() -> int {
         issl::SearchArgs a;
         if (int rc = issl::check_call(pat, max_dist, n, &a)) return rc;
-        HIP_TRY(hipSetDevice(g->device));
-        return issl::search_run(g, a, d_queries, n, d_offsets, d_hits, false, cap, n_total, static_cast<hipStream_t>(stream));
+        return issl::Plain::device_rows(g, a, d_queries, n, d_offsets, d_hits, cap, n_total, stream);
     });
 }
 
@@ -399,16 +238,7 @@ int issl_genome_search_profile(issl_genome *g, const issl_search_pattern *pat, c
     return issl::abi_call([&]() -> int {
         issl::SearchArgs a;
         if (int rc = issl::check_call(pat, max_dist, n, &a)) return rc;
-        if (int rc = issl::check_host_queries(queries, n, pat->length)) return rc;
-        if (n == 0) return ISSL_OK;
-        issl::DevBuf d_q, d_counts;
-        if (int rc = issl::upload_queries(g, queries, n, d_q)) return rc;
-        const size_t bytes = 8 * n * (static_cast<size_t>(max_dist) + 1);
-        HIP_TRY(hipMalloc(&d_counts.p, bytes));
-        if (int rc = issl::profile_run(g, a, static_cast<const issl_search_query *>(d_q.p), n, static_cast<uint64_t *>(d_counts.p), nullptr))
-            return rc;
-        HIP_TRY(hipMemcpy(counts, d_counts.p, bytes, hipMemcpyDeviceToHost));
-        return ISSL_OK;
+        return issl::Plain::host_profile(g, a, pat->length, queries, n, counts);
     });
 }
 
@@ -419,8 +249,7 @@ int issl_genome_search_profile_device(issl_genome *g, const issl_search_pattern 
     return issl::abi_call([&]() -> int {
         issl::SearchArgs a;
         if (int rc = issl::check_call(pat, max_dist, n, &a)) return rc;
-        HIP_TRY(hipSetDevice(g->device));
-        return issl::profile_run(g, a, d_queries, n, d_counts, static_cast<hipStream_t>(stream));
+        return issl::Plain::device_profile(g, a, d_queries, n, d_counts, stream);
     });
 }
 

@@ -577,6 +577,43 @@ class Genome:
                                             C.c_void_p(stream) if stream else None))
         return n.value
 
+    # The four call shapes of the search entry points; `extra` is what a unit passes between the pattern and the queries
+    # (nothing, or the bulge limits).
+    def _search_rows(self, fn, dtype, pattern, extra, queries, max_dist):
+        pat, q = _search_args(pattern, queries)
+        offsets = np.zeros(len(q) + 1, dtype=np.uint64)
+        n = C.c_size_t()
+        args = (self._h, C.byref(pat), *extra, q.ctypes.data if len(q) else None, len(q), int(max_dist), offsets.ctypes.data)
+        check(fn(*args, None, 0, C.byref(n)))  # the counting call, then the filling call
+        hits = np.zeros(n.value, dtype=dtype)
+        if n.value:
+            check(fn(*args, hits.ctypes.data, n.value, C.byref(n)))
+        return offsets, hits
+
+    def _search_counts(self, fn, pattern, extra, queries, max_dist, shape):
+        pat, q = _search_args(pattern, queries)
+        counts = np.zeros((len(q),) + shape, dtype=np.uint64)
+        check(fn(self._h, C.byref(pat), *extra, q.ctypes.data if len(q) else None, len(q), int(max_dist),
+                 counts.ctypes.data if len(q) else None))
+        return counts
+
+    def _search_rows_device(self, fn, dtype, pattern, extra, d_queries, max_dist, d_offsets, d_hits, stream):
+        pat = _search_pattern(pattern)
+        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
+        n = C.c_size_t()
+        cap = d_hits.numel() * d_hits.element_size() // dtype.itemsize if d_hits is not None else 0
+        check(fn(self._h, C.byref(pat), *extra, d_queries.data_ptr() if nq else None, nq, int(max_dist), d_offsets.data_ptr(),
+                 d_hits.data_ptr() if cap else None, cap, C.byref(n), C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def _search_counts_device(self, fn, pattern, extra, d_queries, max_dist, d_counts, bins, words, stream):
+        pat = _search_pattern(pattern)
+        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
+        if d_counts.numel() * d_counts.element_size() < 8 * nq * bins:
+            raise ValueError("d_counts holds fewer than " + words + " words")
+        check(fn(self._h, C.byref(pat), *extra, d_queries.data_ptr() if nq else None, nq, int(max_dist),
+                 d_counts.data_ptr() if nq else None, C.c_void_p(stream) if stream else None))
+
     def search(self, pattern, queries, max_dist=4):
         """Index-free search (issl_genome_search of include/issl_hip.h).  pattern: 1 to 32 IUPAC codes, or the struct of
         search_prepare(); queries: a list of str / bytes of the pattern's length over ACGTN (N: not compared), or the
@@ -584,45 +621,23 @@ class Genome:
         structured array (SEARCH_HIT_DTYPE) sorted by (record, pos, strand).  `pos` is the window's 0-based start on the
         forward strand for both strands; `site` is what the query was compared with (strand 1: the reverse complement of
         the window), `mism` its mismatching positions."""
-        pat, q = _search_args(pattern, queries)
-        offsets = np.zeros(len(q) + 1, dtype=np.uint64)
-        n = C.c_size_t()
-        args = (self._h, C.byref(pat), q.ctypes.data if len(q) else None, len(q), int(max_dist), offsets.ctypes.data)
-        check(lib.issl_genome_search(*args, None, 0, C.byref(n)))
-        hits = np.zeros(n.value, dtype=SEARCH_HIT_DTYPE)
-        if n.value:
-            check(lib.issl_genome_search(*args, hits.ctypes.data, n.value, C.byref(n)))
-        return offsets, hits
+        return self._search_rows(lib.issl_genome_search, SEARCH_HIT_DTYPE, pattern, (), queries, max_dist)
 
     def search_profile(self, pattern, queries, max_dist=4):
         """-> uint64 array [n, max_dist + 1]: the hits of query k at distance d, counted on the device."""
-        pat, q = _search_args(pattern, queries)
-        counts = np.zeros((len(q), int(max_dist) + 1), dtype=np.uint64)
-        check(lib.issl_genome_search_profile(self._h, C.byref(pat), q.ctypes.data if len(q) else None, len(q), int(max_dist),
-                                             counts.ctypes.data if len(q) else None))
-        return counts
+        return self._search_counts(lib.issl_genome_search_profile, pattern, (), queries, max_dist, (int(max_dist) + 1,))
 
     def search_device(self, pattern, d_queries, d_offsets, d_hits, max_dist=4, stream=None):
         """pattern: as for search(); d_queries: CUDA tensor of 16 bytes per query (SEARCH_QUERY_DTYPE, e.g. int64 [n, 2]);
         d_offsets: int64 CUDA tensor of n + 1 words; d_hits: uint8 CUDA tensor (32 bytes per hit, SEARCH_HIT_DTYPE) or None
         for the counting call.  -> the number of hits; nothing is written when they do not fit d_hits."""
-        pat = _search_pattern(pattern)
-        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
-        n = C.c_size_t()
-        cap = d_hits.numel() * d_hits.element_size() // SEARCH_HIT_DTYPE.itemsize if d_hits is not None else 0
-        check(lib.issl_genome_search_device(self._h, C.byref(pat), d_queries.data_ptr() if nq else None, nq, int(max_dist),
-                                            d_offsets.data_ptr(), d_hits.data_ptr() if cap else None, cap, C.byref(n),
-                                            C.c_void_p(stream) if stream else None))
-        return n.value
+        return self._search_rows_device(lib.issl_genome_search_device, SEARCH_HIT_DTYPE, pattern, (), d_queries, max_dist, d_offsets,
+                                        d_hits, stream)
 
     def search_profile_device(self, pattern, d_queries, d_counts, max_dist=4, stream=None):
         """d_counts: int64 CUDA tensor of n * (max_dist + 1) words.  Returns when they are written."""
-        pat = _search_pattern(pattern)
-        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
-        if d_counts.numel() * d_counts.element_size() < 8 * nq * (int(max_dist) + 1):
-            raise ValueError("d_counts holds fewer than n * (max_dist + 1) words")
-        check(lib.issl_genome_search_profile_device(self._h, C.byref(pat), d_queries.data_ptr() if nq else None, nq, int(max_dist),
-                                                    d_counts.data_ptr() if nq else None, C.c_void_p(stream) if stream else None))
+        self._search_counts_device(lib.issl_genome_search_profile_device, pattern, (), d_queries, max_dist, d_counts, int(max_dist) + 1,
+                                   "n * (max_dist + 1)", stream)
 
     def search_bulges(self, pattern, queries, span, max_dist=4, dna_bulge=1, rna_bulge=1):
         """Search with bulges beside the mismatches (issl_genome_search_bulges of include/issl_hip.h).  pattern and queries:
@@ -633,51 +648,30 @@ class Genome:
         least distance over the break points; `bulge` is signed (> 0: DNA, < 0: RNA), `at` the break point inside the span,
         `site` the window of L + bulge bases, `mism` in query coordinates.  Nothing is filtered: a locus that matches
         without a bulge is listed under the other bulges' shifted windows too."""
-        pat, q = _search_args(pattern, queries)
         bg = _search_bulges(span, dna_bulge, rna_bulge)
-        offsets = np.zeros(len(q) + 1, dtype=np.uint64)
-        n = C.c_size_t()
-        args = (self._h, C.byref(pat), C.byref(bg), q.ctypes.data if len(q) else None, len(q), int(max_dist), offsets.ctypes.data)
-        check(lib.issl_genome_search_bulges(*args, None, 0, C.byref(n)))
-        hits = np.zeros(n.value, dtype=BULGE_HIT_DTYPE)
-        if n.value:
-            check(lib.issl_genome_search_bulges(*args, hits.ctypes.data, n.value, C.byref(n)))
-        return offsets, hits
+        return self._search_rows(lib.issl_genome_search_bulges, BULGE_HIT_DTYPE, pattern, (C.byref(bg),), queries, max_dist)
 
     def search_bulges_profile(self, pattern, queries, span, max_dist=4, dna_bulge=1, rna_bulge=1):
         """-> uint64 array [n, rna_bulge + dna_bulge + 1, max_dist + 1]: the rows of query k with bulge b (at index
         b + rna_bulge) at minimum distance d, counted on the device."""
-        pat, q = _search_args(pattern, queries)
         bg = _search_bulges(span, dna_bulge, rna_bulge)
-        counts = np.zeros((len(q), int(rna_bulge) + int(dna_bulge) + 1, int(max_dist) + 1), dtype=np.uint64)
-        check(lib.issl_genome_search_bulges_profile(self._h, C.byref(pat), C.byref(bg), q.ctypes.data if len(q) else None, len(q),
-                                                    int(max_dist), counts.ctypes.data if len(q) else None))
-        return counts
+        return self._search_counts(lib.issl_genome_search_bulges_profile, pattern, (C.byref(bg),), queries, max_dist,
+                                   (int(rna_bulge) + int(dna_bulge) + 1, int(max_dist) + 1))
 
     def search_bulges_device(self, pattern, d_queries, d_offsets, d_hits, span, max_dist=4, dna_bulge=1, rna_bulge=1, stream=None):
         """search_device() with bulges: d_hits is a uint8 CUDA tensor (32 bytes per row, BULGE_HIT_DTYPE) or None for the
         counting call.  -> the number of rows; nothing is written when they do not fit d_hits."""
-        pat = _search_pattern(pattern)
         bg = _search_bulges(span, dna_bulge, rna_bulge)
-        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
-        n = C.c_size_t()
-        cap = d_hits.numel() * d_hits.element_size() // BULGE_HIT_DTYPE.itemsize if d_hits is not None else 0
-        check(lib.issl_genome_search_bulges_device(self._h, C.byref(pat), C.byref(bg), d_queries.data_ptr() if nq else None, nq,
-                                                   int(max_dist), d_offsets.data_ptr(), d_hits.data_ptr() if cap else None, cap,
-                                                   C.byref(n), C.c_void_p(stream) if stream else None))
-        return n.value
+        return self._search_rows_device(lib.issl_genome_search_bulges_device, BULGE_HIT_DTYPE, pattern, (C.byref(bg),), d_queries, max_dist,
+                                        d_offsets, d_hits, stream)
 
     def search_bulges_profile_device(self, pattern, d_queries, d_counts, span, max_dist=4, dna_bulge=1, rna_bulge=1, stream=None):
         """d_counts: int64 CUDA tensor of n * (rna_bulge + dna_bulge + 1) * (max_dist + 1) words.  Returns when they are
         written."""
-        pat = _search_pattern(pattern)
         bg = _search_bulges(span, dna_bulge, rna_bulge)
-        nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
-        if d_counts.numel() * d_counts.element_size() < 8 * nq * (int(rna_bulge) + int(dna_bulge) + 1) * (int(max_dist) + 1):
-            raise ValueError("d_counts holds fewer than n * (rna_bulge + dna_bulge + 1) * (max_dist + 1) words")
-        check(lib.issl_genome_search_bulges_profile_device(self._h, C.byref(pat), C.byref(bg), d_queries.data_ptr() if nq else None, nq,
-                                                           int(max_dist), d_counts.data_ptr() if nq else None,
-                                                           C.c_void_p(stream) if stream else None))
+        self._search_counts_device(lib.issl_genome_search_bulges_profile_device, pattern, (C.byref(bg),), d_queries, max_dist, d_counts,
+                                   (int(rna_bulge) + int(dna_bulge) + 1) * (int(max_dist) + 1),
+                                   "n * (rna_bulge + dna_bulge + 1) * (max_dist + 1)", stream)
 
     def occurrences(self, sites, page_length=0, page_starts=None):
         """The Bowtie step (Crackling.py:600-725) as exact counts.  sites: 20-mer strings or a uint64 array of packed

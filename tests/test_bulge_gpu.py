@@ -310,3 +310,66 @@ def test_query_counts(query_case, n):
                 p["query"] = k
             assert np.concatenate(parts).tobytes() == rows.tobytes() and {-1, 0, 1} == set(rows["bulge"].tolist())
             assert off.tolist() == np.concatenate([[0], np.cumsum([len(p) for p in parts])]).tolist()
+
+
+# ---- more queries than a piece holds ---------------------------------------------------------------------------------------
+
+PIECE_BULGES = 1 << 19  # BulgeSearch::kPieceQueries: 19 bits of query in a hit word
+
+
+def two_piece_case():
+    """2^19 + 1 queries over a pool of 1025 (query k is pool[k % 1025]) against one record of 400 random bases, NGG, span
+    (0, 20), max_dist 1, D = R = 1.  Three pool queries are read off forward sites of the record: pool[513], the single query
+    of the second piece (2^19 mod 1025 = 513), copies a site; pool[7] is a site of 21 bases less one base (a DNA bulge),
+    pool[11] a site of 19 bases with one base put in (an RNA bulge).  -> (blob, pool, which, offsets, rows), the expected
+    bytes being the pool's brute force, tiled.  No device needed."""
+    rng = np.random.default_rng(5)
+    text = random_text(rng, 400)
+    records = [(b"rec0 some text", text.encode())]
+    _, _, _, t = su.candidates(records, NGG)
+    assert 16 <= len(t) <= 64  # at most one workgroup and one wave of survivors
+    sites = [p for p in range(1, 400 - 23) if text[p + 21:p + 23] == "GG"]
+    a, b, c = (int(p) for p in rng.choice(sites, size=3, replace=False))
+    pool = [random_text(rng, 20) + "NNN" for _ in range(1025)]
+    pool[513] = text[a:a + 20] + "NNN"
+    pool[7] = text[b - 1:b + 8] + text[b + 9:b + 20] + "NNN"
+    pool[11] = text[c + 1:c + 10] + "ACGT"[int(rng.integers(0, 4))] + text[c + 10:c + 20] + "NNN"
+    p_off, p_rows, _ = bu.brute_force(records, NGG, pool, (0, 20), 1, 1, 1)
+    n = PIECE_BULGES + 1
+    which = np.arange(n) % 1025
+    counts = np.diff(p_off.astype(np.int64))[which]
+    want_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    has = np.flatnonzero(counts)
+    want_rows = np.concatenate([p_rows[int(p_off[which[k]]):int(p_off[which[k] + 1])] for k in has])
+    want_rows["query"] = np.repeat(has, counts[has])
+    return fasta_of([text]), pool, which, want_off, want_rows
+
+
+def test_more_queries_than_a_piece_holds():
+    """The two-piece path of the bulged search: the rows of the second piece are written behind the first piece's, to host
+    memory and to device memory, and not at all when they do not fit."""
+    import torch
+    blob, pool, which, want_off, want_rows = two_piece_case()
+    n, total = len(which), len(want_rows)
+    first = want_rows[:int(want_off[PIECE_BULGES])]
+    assert want_off[n] - want_off[PIECE_BULGES] >= 1 and which[PIECE_BULGES] == 513  # the second piece has rows
+    assert (first["bulge"] == -1).any() and (first["bulge"] == 1).any()
+    pat, pq = ca.search_prepare(NGG, pool)
+    q = np.ascontiguousarray(pq[which])
+    bg = _lib.SearchBulges(0, 20, 1, 1)
+    with ca.Genome.open([blob]) as g:
+        off, rows = g.search_bulges(pat, q, (0, 20), 1, 1, 1)
+        assert off.tobytes() == want_off.tobytes() and rows.tobytes() == want_rows.tobytes()
+        d_q = torch.from_numpy(q.view(np.int64).reshape(-1, 2).copy()).cuda()
+        d_off = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda")
+        d_hits = torch.full((total * 32,), 0xA5, dtype=torch.uint8, device="cuda")  # exactly n_total rows
+        assert g.search_bulges_device(pat, d_q, d_off, d_hits, (0, 20), 1, 1, 1) == total
+        assert d_off.cpu().numpy().view(np.uint64).tobytes() == want_off.tobytes()
+        assert d_hits.cpu().numpy().tobytes() == want_rows.tobytes()
+        poison = np.full(total * 32, 0xA5, dtype=np.uint8)
+        off = np.full(n + 1, 0xFFFFFFFF, dtype=np.uint64)
+        n_total = C.c_size_t()
+        assert _lib.lib.issl_genome_search_bulges(g._h, C.byref(pat), C.byref(bg), q.ctypes.data, n, 1, off.ctypes.data, poison.ctypes.data,
+                                                  total - 1, C.byref(n_total)) == 0
+        assert n_total.value == total and off.tobytes() == want_off.tobytes()
+        assert (poison == 0xA5).all()  # cap one below n_total: nothing is written
