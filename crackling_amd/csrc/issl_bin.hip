@@ -287,6 +287,7 @@ __global__ __launch_bounds__(256) void k_plan(ImageView v, uint32_t *__restrict_
         plan->candidates = tot_cand;
         plan->reference_candidates = tot_cand;
         plan->fine = 0;
+        plan->scan_tail = 0;
         plan->tiles = tot_tiles;
         // one equal-cost range per scan workgroup; inside a workgroup the waves share the tiles dynamically
         plan->n_ranges = (overflow || tot_tiles == 0) ? 0u : ranges_for(tot_tiles, scan_blocks);
@@ -536,6 +537,7 @@ __global__ __launch_bounds__(256) void k_fine_plan(FineSum *__restrict__ fsum, u
             counters->raw_chunks = (plan->n_ranges ? plan->n_ranges : 1u) * 16u;
             plan->fine = prune_mode;
             plan->fine_slots = static_cast<uint32_t>(t_slots);
+            plan->scan_tail = t_cand >= kScanTailCands * 16ull * plan->n_ranges ? 1u : 0u; // (16 waves per range)
         }
     }
 }

@@ -187,6 +187,7 @@ static bool workspace_option(const issl_index *idx, const char *key, long long *
         {"ws_cap_chunks", static_cast<long long>(w.cap_chunks)},
         {"ws_cap_fitems", static_cast<long long>(w.cap_fitems)},
         {"ws_lean", idx->lane.lean ? 1 : 0},
+        {"ws_scan_verified", static_cast<long long>(idx->lane.scan_verified)},
     };
     for (const auto &k : keys)
         if (std::strcmp(k.key, key) == 0) {

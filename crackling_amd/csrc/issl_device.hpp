@@ -162,6 +162,10 @@ struct Tuning {
     int scan_events;        // ISSL_SCAN_EVENTS   HIP event pair around the scan: 1 every batch, 2 (default) the first batch after a finish, 0 never
     bool stage_timing;      // ISSL_STAGE_TIMING  asynchronous batches record an event at every stage boundary
     bool upload_timing;     // ISSL_UPLOAD_TIMING one stderr line per upload stage
+    int scan_verify;        // ISSL_SCAN_VERIFY   (environment only) unset = -1: a scan wave verifies the chunks of records it has filled between two
+                            //                    of its units, and, once it has filled one, its last chunk when its range is done (scan_tail in
+                            //                    issl_kernels.hip); 1: every wave's last chunk too (tests: the tail on batches of a few records); 0:
+                            //                    every record is k_verify's (A/B)
     size_t raw_chunks;      // ISSL_RAW_CHUNKS    initial raw-record buffer in chunks (0: sized from the launch)
     int inline_sigs;        // ISSL_INLINE_SIGS   -1 automatic, 0 never, 1 always
     int sorted_layout;      // ISSL_SORTED_LAYOUT -1 automatic (whenever the lists allow it and an image fits), 0 never, 1 always
@@ -263,6 +267,10 @@ constexpr uint32_t kStampsWords = kStampsBig1024 + kStampsPerReplay;
 constexpr uint32_t kSpanRing = 64;              // batches per lane whose scan spans are kept until the next finish
 constexpr uint32_t kChunkRecs = 128;            // raw-record chunk: 1 KiB, slot 0 is the fill count
 constexpr uint64_t kDeadKey = ~0ull;            // raw slot that did not survive the exact check
+constexpr uint32_t kChunkVerified = 1u << 31;   // raw_used[chunk]: the scan wave that filled the chunk has verified it (k_scan's tail); k_verify skips it
+constexpr uint64_t kScanTailCands = 2ull * 127ull * 2048ull; // PlanInfo::scan_tail: planned comparisons per scan wave from which the waves verify (two chunks of records at one per 2048)
+constexpr uint32_t kScanVerifyRuns = 8;         // runs of chunks a scan wave remembers for its tail: its own chunk and seven reservations (1, 2, 4, 8, 16, 16,
+                                                // 16: 64 chunks = 8128 records; the flagship batch fills about 7 chunks per wave); later ones are k_verify's
 // Key of a scored off-target: guide << 37 | first matching slice << 32 | site id (sorted layouts) or position in the
 // bucket's list -- the reference's scoring order inside a guide (isslScoreOfftargets.cpp:330,344) is the numeric order
 // of the low 37 bits.  Five bits of slice: up to 20 slices (slice width 2).
@@ -319,7 +327,13 @@ struct PlanInfo {
     uint64_t reference_candidates; // sum over guides of their five bucket lengths = what the reference compares
     uint64_t tiles;       // (tile, item) pairs the scan works through
     uint32_t fine_slots;  // pruned plan: guide slots in use (a multiple of 8)
-    uint32_t pad;
+    uint32_t scan_tail;   // 1: the scan's waves verify the records they note (scan_tail, issl_kernels.hip).  Decided with the plan
+                          // (k_fine_plan; 0 from k_plan and k_bin_small): only a batch that plans kScanTailCands comparisons per
+                          // scan wave or more -- on an even index at max_dist 4 one comparison in ~2000 notes a record, so a
+                          // wave of such a batch fills chunks.  Below that a wave notes a handful of records, the tail would
+                          // never run between two units, and what a launch pays for having one (the per-wave list, the end
+                          // stamp behind the tails, k_verify's header read ahead of its records) is paid for nothing:
+                          // 64 guides x 300 M sites 0.0642 -> 0.0661 ms per step with the tail armed on every batch
 };
 
 // Updated by the scan with atomics.
@@ -331,6 +345,7 @@ struct Counters {
     uint32_t raw_chunks;  // chunks of the raw record buffer handed out
     uint32_t raw_overflow; // set when the raw buffer was too small
     uint32_t overflowed;  // hit slots: guides with more than kReplayLds hits (k_verify); 0 = nothing to group, no many-hit replay
+    uint32_t scan_verified; // records the scan's own waves verified (k_scan's tail); the others are k_verify's
     uint32_t replay_next[3]; // tickets of the many-hit replays (k_replay_mid, k_replay_big<256>, k_replay_big<1024>): the next entry
                              // of the shared guide list a workgroup of that kernel takes
 };
@@ -443,6 +458,11 @@ struct Workspace {
     SlotRec *slots = nullptr;       // [cap_slot_guides * slot_width]
     uint32_t slot_hits = 0;         // of the batch being enqueued: 0 or slot_width
     uint32_t slot_width = kSlotHits; // slots per guide the array was allocated with (kSlotHits / kSlotHitsWide)
+    uint32_t scan_verify = 0;       // of the batch being enqueued: 0 = its scan and its k_verify are the builds WITHOUT the verify tail (k_scan<THR,
+                                    // false>, k_verify<false>: the code a batch ran before there was a tail -- a launch that merely
+                                    // could arm one is 1.4 us of a 64-guide batch's 64 slower); 1 = the builds with it, armed by the
+                                    // batch's plan (PlanInfo::scan_tail); 2 = armed always (ISSL_SCAN_VERIFY=1).  The host decides 0 / 1
+                                    // from what it knows before the plan exists (tail_worth_arming, issl_pipeline.cpp)
     uint32_t lean_tail = 0;         // of the batch being enqueued: 1 = the grouping pass and the three many-hit replays are NOT
                                     // launched for it (five dependent launches that find nothing to do on an index where no
                                     // guide outgrows its hit slots -- 25 us of every batch, a fifth of a 64-guide one).  A
@@ -471,6 +491,28 @@ struct ScoreParams {
     double maximum_sum; // (10000 - 100*thr)/thr, isslScoreOfftargets.cpp:326
 };
 
+// What the exact test of one raw record needs of the image, the workspace and the batch (verify_record, issl_kernels.hpp):
+// a kernel argument of k_verify and of k_scan, whose waves verify the chunks of records they have filled between two of
+// their units (scan_tail, issl_kernels.hip).
+struct VerifyCtx {
+    ImageView v;
+    const uint64_t *guides;
+    uint64_t *raw;
+    uint32_t *raw_used;
+    const uint32_t *gidx, *gbucket; // bucket-level plan: guide and bucket of a guide slot
+    uint32_t *gcount;
+    SlotRec *slots;
+    uint32_t *rank;
+    double *pay;
+    Counters *counters;
+    uint32_t n;          // guides of the batch
+    uint32_t slot_hits, lean_tail;
+    int max_dist;
+    uint32_t calc_mit, calc_cfd;
+    uint32_t scan_verify; // Workspace::scan_verify
+};
+VerifyCtx make_verify_ctx(const ImageView &v, const Workspace &ws, const Tuning &tn, const uint64_t *d_guides, uint32_t n, const ScoreParams &p);
+
 // Launchers, one stage file each (issl_bin.hip: pack_scan_* and bin_guides; issl_kernels.hip: scan; issl_verify.hip,
 // issl_group.hip, issl_replay.hip; issl_report.hip: profile and report_*).  All asynchronous on `stream`.
 // error_flag bits: 1 = an entry's id lies beyond the site table, 4 = a list holds a site in a bucket its signature does
@@ -488,8 +530,8 @@ uint32_t prune_mode_for(const ImageView &v, const Tuning &tn, uint32_t n_guides,
 void launch_bin_guides(const ImageView &v, const Workspace &ws, const Tuning &tn, const uint64_t *d_guides, uint32_t n,
                        uint32_t prune_mode, void *stream);
 void launch_scan(const ImageView &v, const Workspace &ws, const Tuning &tn, const uint64_t *d_guides, uint32_t n,
-                 int max_dist, uint32_t prune_mode, void *stream);
-void launch_verify(const ImageView &v, const Workspace &ws, const uint64_t *d_guides, uint32_t n, const ScoreParams &p, void *stream);
+                 const ScoreParams &p, uint32_t prune_mode, void *stream);
+void launch_verify(const ImageView &v, const Workspace &ws, const Tuning &tn, const uint64_t *d_guides, uint32_t n, const ScoreParams &p, void *stream);
 void launch_group_hits(const Workspace &ws, uint32_t n, void *stream);
 void launch_replay(const ImageView &v, const Workspace &ws, const uint64_t *d_guides, uint32_t n,
                    const ScoreParams &p, double *d_mit, double *d_cfd, uint32_t *d_kept, issl_hit *d_hitrec,

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kChunkRecs) void k_group_scatter(const uint64_t *__
         const uint64_t key = recs[t < kChunkRecs ? t : 0u];
         const uint32_t my_rank = rank[slot];
         const double2 my_pay = pay[slot];
-        const uint32_t used = raw_used[chunk];
+        const uint32_t used = raw_used[chunk] & ~kChunkVerified; // (a chunk its scan wave verified: the same keys, ranks and terms as k_verify leaves)
         if (t >= used || t >= kChunkRecs || key == kDeadKey) continue;
         const uint32_t guide = static_cast<uint32_t>(key >> kKeyGuideShift);
         const uint32_t to = goff[guide] + my_rank; // rank: k_verify's

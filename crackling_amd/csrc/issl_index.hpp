@@ -35,6 +35,7 @@ struct Lane {
     hipStream_t last_tail = nullptr; // the stream that batch's last kernels went to
     int last_max_dist = 0;
     uint32_t last_prune = 0;
+    uint32_t scan_verified = 0; // Counters::scan_verified of the lane's last finished batch
     bool lean = false;          // the lane's finished batches had no guide beyond its hit slots: the next ones are enqueued
                                 // without the grouping pass and the many-hit replays (Workspace::lean_tail)
 };
@@ -72,6 +73,9 @@ struct issl_index {
     // proven_chunks chunks at a max_dist of at least proven_dist: pieces within that skip the per-guide estimate (0.9 ms per 500 k guides)
     size_t proven_guides = 0, proven_chunks = 0;
     int proven_dist = -1;
+    // what the pruned plan of the last finished batch planned per guide, and for which prune mode (tail_worth_arming)
+    double plan_cands_per_guide = 0.0;
+    uint32_t plan_cands_prune = 0;
 };
 
 namespace issl {

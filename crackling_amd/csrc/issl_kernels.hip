@@ -9,6 +9,8 @@
 //   verify     every record: exact test on the whole signatures, first-matching-slice rule (replaces
 //              the seen-bitmap, A7), key (guide, slice, site id or list position), MIT / CFD terms;
 //              the first 512 hits of a guide go straight to its hit slots (Workspace)                 (A7-A9)
+//              -- by the scan wave that noted the record, between two of its units (scan_tail: pruned
+//              plan, sorted layout), else by k_verify
 //   group_*    counting sort by guide of the keys and terms that lie beyond their guide's slots
 //              (nothing on an index where no guide has more than 512 hits)
 //   replay     per guide: its hits in key order = the reference's scan order, terms added sequentially
@@ -44,8 +46,9 @@ struct alignas(4 * kGuideGroup) GuideGroup {
 // 8-byte record (guide slot, tile, offset in tile), with plain stores into a chunk of the raw buffer
 // that the wave owns -- no dependent load, no returning atomic on the hot path (one hit per ~50k
 // comparisons is frequent enough that a latency chain per hit would dominate the kernel).
-// k_verify then checks every record exactly, applies the first-matching-slice rule and turns the
-// survivors into keys.  Chunk = kChunkRecs slots of 8 bytes, slot 0 unused; raw_used[chunk] = slots in use (slot 0 included).
+// Every record is then checked exactly, the first-matching-slice rule applied and the survivors turned
+// into keys (verify_record, issl_kernels.hpp) -- off the hot path: by the wave itself between two units
+// (scan_tail), by k_verify where no tail runs.  Chunk = kChunkRecs slots of 8 bytes, slot 0 unused; raw_used[chunk] = slots in use (slot 0 included).
 __device__ __forceinline__ uint64_t raw_record(uint32_t gslot, uint32_t tile, uint32_t offset)
 {
     return (static_cast<uint64_t>(gslot) << 37) | (static_cast<uint64_t>(tile) << 11) | offset;
@@ -58,7 +61,27 @@ struct RawWriter {
     uint32_t reserve;  // chunks the next reservation takes: 1, 2, 4 ... 16 -- a wave in a hit-dense bucket fills a chunk
                        // every few guides, and every reservation is a returning atomic that the wave waits for with all
                        // its record stores; a wave with few hits never reserves a chunk it does not use
+    uint32_t tail;     // the wave's verify tail (scan_tail).  kTailOn: one follows; kTailPending: a chunk has been retired since
+                       // it last ran; kTailRangeDone: the wave's range has no unit left; kTailLast: the chunk the wave is
+                       // writing when its range is done is the tail's too -- always where the tail is forced, else once
+                       // the wave has retired a chunk.  (A wave of a small batch notes a few records; verifying them
+                       // is a chain of six dependent accesses behind its last unit, with nothing on the CU to hide it:
+                       // 64 guides 0.058 -> 0.076 ms, 10 k guides x 50 M sites 0.29 -> 0.42 ms per step with every wave's
+                       // last chunk taken.  k_verify does those chunks at full occupancy, as before.)
 };
+constexpr uint32_t kTailOn = 4u, kTailPending = 1u, kTailRangeDone = 2u, kTailLast = 8u;
+// The wave's list in LDS for its verify tail: [0] = runs listed, then the first chunk of each -- run 0 is the wave's own
+// chunk, run k >= 1 its k-th reservation, min(1 << (k - 1), 16) chunks.  A list that is full stays as it is: what the wave
+// reserves from then on is k_verify's.  Behind the list: the tail's cursor (run, chunk of the run) and its count of
+// records.  (Found from the thread's number where it is wanted, all cold places: a pointer carried through the scan's
+// loop is a register the passes do not have.)
+constexpr uint32_t kRunCursor = 1u + kScanVerifyRuns, kRunWords = kRunCursor + 3u;
+__device__ __forceinline__ uint32_t *wave_runs()
+{
+    __shared__ uint32_t runs[16][kRunWords];
+    return runs[threadIdx.x >> 6];
+}
+__device__ __forceinline__ uint32_t run_chunks(uint32_t k) { return k == 0u ? 1u : k > 4u ? 16u : 1u << (k - 1u); }
 
 __device__ __forceinline__ void raw_retire(const RawWriter &w, uint32_t lane, const uint64_t *raw, uint32_t *raw_used)
 {
@@ -69,6 +92,7 @@ __device__ __forceinline__ void raw_acquire(RawWriter &w, uint64_t *raw, uint32_
                                             uint32_t lane)
 {
     w.fill = 1;
+    if ((w.tail & kTailOn) != 0u) w.tail |= kTailPending | kTailLast;
     if (w.left != 0u) { // the next chunk of the reservation: its header was cleared with all the others (k_guide_hist)
         w.chunk += kChunkRecs;
         w.left -= 1u;
@@ -87,6 +111,14 @@ __device__ __forceinline__ void raw_acquire(RawWriter &w, uint64_t *raw, uint32_
     w.chunk = raw + static_cast<uint64_t>(idx) * kChunkRecs;
     w.left = take - 1u;
     if (take < 16u) w.reserve = take * 2u;
+    if ((w.tail & kTailOn) != 0u && lane == 0) {
+        uint32_t *runs = wave_runs();
+        const uint32_t listed = runs[0];
+        if (listed < kScanVerifyRuns) {
+            runs[1u + listed] = idx;
+            runs[0] = listed + 1u;
+        }
+    }
 }
 
 // ---- bit-sliced distance test -------------------------------------------------------------------
@@ -419,6 +451,54 @@ __device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, con
     } while (__builtin_expect(who != 0ull, 0));
 }
 
+// The verify tail of a scan wave.  Between two units its planes and guide words are dead, and the SIMD's other waves go
+// on comparing: there, and once more when its range has no unit left, it applies verify_record's rules (issl_kernels.hpp)
+// to the records it noted itself, in the chunks only it owns and has retired (wave_runs), instead of leaving them to
+// k_verify, which does nothing but wait for HBM while the vector ALUs idle.  (At the end of the range alone the tails of
+// all waves fall into the same moment -- the ranges cost the same -- and the chip then does what k_verify does, for as
+// long: measured, profiles/ab_scan_verify_bench.log.)  A whole chunk per round, two records per lane, both asked for at
+// once; the chains behind them run one after the other (two VerifyRec at a time do not fit the scan's 64 registers
+// without scratch).  The wave reads back what it stored: it waits for its stores, and the loads are device-scope ones,
+// which cannot be served from a line the CU's L1 holds from before the store.  A chunk it has been through is marked in
+// raw_used (kChunkVerified): k_verify leaves it alone.  The walk stops at the first chunk without a fill count: the one
+// the wave is writing (raw_retire has not come to it), cleared by the binning like every header.  Only behind the pruned
+// plan on a sorted layout (VerifyCtx::scan_verify, plan->fine): there a record needs nothing but itself, the stream and
+// the batch's guides.
+__device__ __forceinline__ void scan_tail(uint32_t prune_mode, uint32_t lane, const uint64_t *raw, const uint32_t *raw_used)
+{
+    // the verify context is k_scan's FIRST argument: it stands at the start of the kernel-argument segment, and is read from
+    // there HERE (the address passes through an empty asm statement: nothing the tail needs is loaded ahead of the scan's loop).
+    // Should the context ever stand elsewhere -- a parameter put in front of it, a code object that lays its arguments out
+    // differently -- what is read here is not the context: its record buffer and fill counts are then not the kernel's own
+    // `raw` and `raw_used`, and the tail leaves everything to k_verify (tests/test_scan_verify.py sees ws_scan_verified 0).
+    uint64_t kernarg = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr());
+    asm volatile("" : "+s"(kernarg));
+    KernargCtx &vc = *(KernargCtx *)kernarg;
+    if (vc.raw != raw || vc.raw_used != raw_used) return;
+    uint32_t *runs = wave_runs();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the wave's record stores and its fill counts (raw_retire)
+    asm volatile("" : "+v"(lane)); // (what the tail makes of the lane number is made here, not ahead of the scan's loop, where it would hold registers through the passes)
+    const uint32_t listed = __builtin_amdgcn_readfirstlane(runs[0]);
+    uint32_t k = __builtin_amdgcn_readfirstlane(runs[kRunCursor]), j = __builtin_amdgcn_readfirstlane(runs[kRunCursor + 1u]);
+    uint32_t verified = 0;
+    while (k < listed) {
+        const uint32_t chunk = __builtin_amdgcn_readfirstlane(runs[1u + k]) + j;
+        const uint32_t used = __builtin_amdgcn_readfirstlane(__hip_atomic_load(vc.raw_used + chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (used <= 1u) break;
+        const uint64_t *recs = vc.raw + static_cast<uint64_t>(chunk) * kChunkRecs;
+        const uint32_t t0 = lane + 1u, t1 = lane + 65u;
+        const bool use0 = t0 < used, use1 = t1 < used && t1 < kChunkRecs;
+        const uint64_t rec0 = use0 ? __hip_atomic_load(recs + t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+        const uint64_t rec1 = use1 ? __hip_atomic_load(recs + t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+        verify_record<true>(vc, prune_mode, rec0, use0, chunk, t0, lane);
+        verify_record<true>(vc, prune_mode, rec1, use1, chunk, t1, lane);
+        if (lane == 0) vc.raw_used[chunk] = used | kChunkVerified;
+        verified += (used < kChunkRecs ? used : kChunkRecs) - 1u;
+        if (++j == run_chunks(k)) { j = 0u; ++k; }
+    }
+    if (lane == 0) { runs[kRunCursor] = k; runs[kRunCursor + 1u] = j; runs[kRunCursor + 2u] += verified; }
+}
+
 // Scan kernel.  A workgroup of 16 waves (two per CU = 8 waves per SIMD) owns one equal-cost range of the work
 // and its waves share the tiles of that range through a ticket counter in LDS: the hardware favours the older
 // waves of a SIMD, so waves with equal static shares finish anywhere between 30 % and 100 % of the kernel time
@@ -435,7 +515,7 @@ __device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, con
 // The work of one scan workgroup.  FINE: the plan of the pruned scan (single-tile items numbered like the units).  A
 // function template instantiated once per plan inside k_scan, so that each copy reads its item list and guide words
 // through the kernel's own `__restrict__` arguments (a pointer chosen at run time loses the scalar loads).
-template <int THR, bool FINE>
+template <int THR, bool FINE, bool TAIL>
 __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_stream, const ScanItem *__restrict__ items,
                                            const PlanInfo *__restrict__ plan, const RangeStart *__restrict__ range_start,
                                            const std::conditional_t<FINE, FineSlot, uint32_t> *__restrict__ gword_stream, uint4 *wave_masks,
@@ -443,7 +523,8 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                                            Counters *counters, uint32_t thr, unsigned long long *stamps,
                                            uint64_t *__restrict__ scan_count, uint32_t *next_unit_p, uint32_t *waves_done_p,
                                            unsigned long long *wg_compared_p, unsigned long long t_start,
-                                           unsigned long long *span, uint32_t n_tiles, uint32_t slice_bits)
+                                           unsigned long long *span, uint32_t n_tiles, uint32_t slice_bits,
+                                           const VerifyCtx &vc, uint32_t *tails_done_p)
 {
     uint32_t &next_unit = *next_unit_p;
     uint32_t &waves_done = *waves_done_p;
@@ -460,6 +541,15 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
     w.fill = 1;
     w.left = 0;
     w.reserve = 1;
+    // the verify tail (scan_tail): the pruned plan alone, and no wave that starts in the spare chunk
+    // (the batch's plan says whether its waves fill chunks at all, PlanInfo::scan_tail; scan_verify 2 = the test setting: always)
+    const bool tail_launch = TAIL && FINE && (vc.scan_verify > 1u || (vc.scan_verify != 0u && plan->scan_tail != 0u)); // (TAIL = false: the build without a tail, Workspace::scan_verify 0)
+    const bool tail = tail_launch && !no_own_chunk;
+    w.tail = tail ? kTailOn | (vc.scan_verify > 1u ? kTailLast : 0u) : 0u;
+    if (tail && lane == 0) {
+        uint32_t *runs = wave_runs();
+        runs[0] = 1u; runs[1] = wave_id; runs[kRunCursor] = 0u; runs[kRunCursor + 1u] = 0u; runs[kRunCursor + 2u] = 0u;
+    }
     bool own_chunk = false;
     unsigned long long compared = 0ull; // (real candidate, real guide) pairs this wave has compared; wave-uniform
 
@@ -476,10 +566,33 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
 
     const uint32_t order_step = slice_bits == 8u ? 6u : 0u; // pruned scan: bits per slice in kFineOrders
     while (true) {
+        if constexpr (FINE && TAIL) {
+            // between two units: the chunks retired since; behind the last one: also the chunk the wave was writing
+            if ((w.tail & kTailPending) != 0u) {
+                scan_tail(plan->fine, lane, raw, raw_used);
+                w.tail &= ~kTailPending;
+            }
+        }
+        if ((w.tail & kTailRangeDone) != 0u) break;
         uint32_t u = 0;
         if (lane == 0) u = atomicAdd(&next_unit, 1u);
         u = __builtin_amdgcn_readfirstlane(u);
-        if (u >= n_units) break;
+        if (u >= n_units) {
+            if (own_chunk) {
+                raw_retire(w, lane, raw, raw_used);
+                if (no_own_chunk && lane == 0) counters->raw_overflow = 1u;
+            }
+            // comparisons of the workgroup: summed in LDS, stored (not added: no reset needed) by its last wave
+            if (lane == 0) {
+                atomicAdd(&wg_compared, compared);
+                if (atomicAdd(&waves_done, 1u) == (blockDim.x >> 6) - 1u) {
+                    scan_count[blockIdx.x] = atomicAdd(&wg_compared, 0ull);
+                    if (!tail_launch) atomicMax(span + 1, static_cast<unsigned long long>(__builtin_amdgcn_s_memrealtime())); // (no tails: the launch ends here)
+                }
+            }
+            w.tail |= kTailRangeDone | ((own_chunk && (w.tail & kTailLast) != 0u) ? kTailPending : 0u);
+            continue;
+        }
         ++units_done;
         const uint32_t gt = tile_begin + u;            // tile number in item order
         if (fine) { it = gt; cur = items[gt]; }        // single-tile items: numbered like the units, no search
@@ -676,18 +789,12 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
             }
         }
     }
-    if (own_chunk) {
-        raw_retire(w, lane, raw, raw_used);
-        if (no_own_chunk && lane == 0) counters->raw_overflow = 1u;
+    if constexpr (FINE && TAIL) {
+        if ((w.tail & kTailOn) != 0u && lane == 0 && wave_runs()[kRunCursor + 2u] != 0u) atomicAdd(&vc.counters->scan_verified, wave_runs()[kRunCursor + 2u]);
     }
-    // comparisons of the workgroup: summed in LDS, stored (not added: no reset needed) by its last wave
-    if (lane == 0) {
-        atomicAdd(&wg_compared, compared);
-        if (atomicAdd(&waves_done, 1u) == (blockDim.x >> 6) - 1u) {
-            scan_count[blockIdx.x] = atomicAdd(&wg_compared, 0ull);
-            atomicMax(span + 1, static_cast<unsigned long long>(__builtin_amdgcn_s_memrealtime()));
-        }
-    }
+    // the launch's own end: behind the tails, by the workgroup's last wave
+    if (tail_launch && lane == 0 && atomicAdd(tails_done_p, 1u) == (blockDim.x >> 6) - 1u)
+        atomicMax(span + 1, static_cast<unsigned long long>(__builtin_amdgcn_s_memrealtime()));
     if (stamps && lane == 0) {
         stamps[4 * wave_id] = t_start;
         stamps[4 * wave_id + 1] = __builtin_amdgcn_s_memrealtime();
@@ -697,8 +804,11 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
     }
 }
 
-template <int THR>
-__global__ __launch_bounds__(1024, 8) void k_scan(const uint32_t *__restrict__ scan_stream,
+// INVARIANT: `vc` is the FIRST parameter.  scan_tail reads it at offset 0 of the kernel-argument segment (and checks what it
+// finds there against `raw` and `raw_used`).
+template <int THR, bool TAIL>
+__global__ __launch_bounds__(1024, 8) void k_scan(VerifyCtx vc,
+                                                  const uint32_t *__restrict__ scan_stream,
                                                   const ScanItem *__restrict__ items_full,
                                                   const ScanItem *__restrict__ items_fine,
                                                   const PlanInfo *__restrict__ plan,
@@ -711,12 +821,13 @@ __global__ __launch_bounds__(1024, 8) void k_scan(const uint32_t *__restrict__ s
 {
     __shared__ uint32_t next_unit;
     __shared__ uint32_t waves_done;
+    __shared__ uint32_t tails_done;
     __shared__ unsigned long long wg_compared;
     __shared__ uint4 tail_masks[16][64]; // per wave: the guide masks of 8 passes of a short unit (short_unit_masks)
     // stamps (diagnostics, normally null): per wave {start, end} in 100 MHz ticks, {XCC_ID, HW_ID} and the number of
     // tiles it took; nothing else reads them
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0) { next_unit = 0; waves_done = 0; wg_compared = 0ull; }
+    if (threadIdx.x == 0) { next_unit = 0; waves_done = 0; wg_compared = 0ull; if (TAIL) tails_done = 0; }
     __syncthreads();
     if (blockIdx.x >= plan->n_ranges) {
         if (threadIdx.x == 0) scan_count[blockIdx.x] = 0ull;
@@ -725,42 +836,48 @@ __global__ __launch_bounds__(1024, 8) void k_scan(const uint32_t *__restrict__ s
     if (threadIdx.x == 0) atomicMin(span, t_start); // the launch's own span: first workgroup in, last one out
     // the plan of this batch: bucket-level items, or the successor-byte groups of the pruned scan (k_fine_plan)
     if (plan->fine != 0u)
-        scan_range<THR, true>(scan_stream, items_fine, plan, range_start, gword_fine, tail_masks[threadIdx.x >> 6], raw, raw_used, max_chunks, counters, thr, stamps,
-                              scan_count, &next_unit, &waves_done, &wg_compared, t_start, span, n_tiles, slice_bits);
+        scan_range<THR, true, TAIL>(scan_stream, items_fine, plan, range_start, gword_fine, tail_masks[threadIdx.x >> 6], raw, raw_used, max_chunks, counters, thr, stamps,
+                              scan_count, &next_unit, &waves_done, &wg_compared, t_start, span, n_tiles, slice_bits, vc, &tails_done);
     else
-        scan_range<THR, false>(scan_stream, items_full, plan, range_start, gword_full, tail_masks[threadIdx.x >> 6], raw, raw_used, max_chunks, counters, thr, stamps,
-                               scan_count, &next_unit, &waves_done, &wg_compared, t_start, span, n_tiles, slice_bits);
+        scan_range<THR, false, TAIL>(scan_stream, items_full, plan, range_start, gword_full, tail_masks[threadIdx.x >> 6], raw, raw_used, max_chunks, counters, thr, stamps,
+                               scan_count, &next_unit, &waves_done, &wg_compared, t_start, span, n_tiles, slice_bits, vc, &tails_done);
 }
 
 template <int THR>
 static void launch_scan_thr(const ImageView &v, const Workspace &ws, const Tuning &tn, uint32_t thr, uint32_t prune_mode,
-                            hipStream_t stream)
+                            const VerifyCtx &vc, hipStream_t stream)
 {
     // pruned scan: the items and guide words grouped by (bucket, successor byte); the plan says which list counts
-    hipLaunchKernelGGL(k_scan<THR>, dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, v.scan, ws.items,
-                       prune_mode ? ws.fitems : ws.items, ws.plan, ws.range_start, ws.gword, ws.fword,
-                       ws.raw, ws.raw_used, static_cast<uint32_t>(ws.cap_chunks), ws.counters, thr, ws.stamps, ws.scan_count,
-                       ws.scan_span + 2u * ws.span_slot, v.n_tiles, v.slice_width);
+    if (vc.scan_verify != 0u)
+        hipLaunchKernelGGL((k_scan<THR, true>), dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, vc, v.scan, ws.items,
+                           prune_mode ? ws.fitems : ws.items, ws.plan, ws.range_start, ws.gword, ws.fword,
+                           ws.raw, ws.raw_used, static_cast<uint32_t>(ws.cap_chunks), ws.counters, thr, ws.stamps, ws.scan_count,
+                           ws.scan_span + 2u * ws.span_slot, v.n_tiles, v.slice_width);
+    else
+        hipLaunchKernelGGL((k_scan<THR, false>), dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, vc, v.scan, ws.items,
+                           prune_mode ? ws.fitems : ws.items, ws.plan, ws.range_start, ws.gword, ws.fword,
+                           ws.raw, ws.raw_used, static_cast<uint32_t>(ws.cap_chunks), ws.counters, thr, ws.stamps, ws.scan_count,
+                           ws.scan_span + 2u * ws.span_slot, v.n_tiles, v.slice_width);
 }
 
 void launch_scan(const ImageView &v, const Workspace &ws, const Tuning &tn, const uint64_t *d_guides, uint32_t n,
-                 int max_dist, uint32_t prune_mode, void *stream_)
+                 const ScoreParams &p, uint32_t prune_mode, void *stream_)
 {
-    (void)n;
-    (void)d_guides;
+    const int max_dist = p.max_dist;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (max_dist < 0) { // isslScoreOfftargets.cpp:382: no distance satisfies 0 <= dist <= maxDist -- nothing is compared
         (void)hipMemsetAsync(ws.scan_count, 0, 8ull * tn.scan_blocks, stream);
         return;
     }
     const uint32_t thr = max_dist > 31 ? 31u : static_cast<uint32_t>(max_dist);
+    const VerifyCtx vc = make_verify_ctx(v, ws, tn, d_guides, n, p); // the waves' verify tail (scan_tail)
     // the runtime-threshold build serves max_dist > 4 (and, forced by the scan_generic knob, the tests of that build)
-    if (tn.scan_generic || thr > 4) launch_scan_thr<-1>(v, ws, tn, thr, prune_mode, stream);
-    else if (thr == 0) launch_scan_thr<0>(v, ws, tn, thr, prune_mode, stream);
-    else if (thr == 1) launch_scan_thr<1>(v, ws, tn, thr, prune_mode, stream);
-    else if (thr == 2) launch_scan_thr<2>(v, ws, tn, thr, prune_mode, stream);
-    else if (thr == 3) launch_scan_thr<3>(v, ws, tn, thr, prune_mode, stream);
-    else launch_scan_thr<4>(v, ws, tn, thr, prune_mode, stream);
+    if (tn.scan_generic || thr > 4) launch_scan_thr<-1>(v, ws, tn, thr, prune_mode, vc, stream);
+    else if (thr == 0) launch_scan_thr<0>(v, ws, tn, thr, prune_mode, vc, stream);
+    else if (thr == 1) launch_scan_thr<1>(v, ws, tn, thr, prune_mode, vc, stream);
+    else if (thr == 2) launch_scan_thr<2>(v, ws, tn, thr, prune_mode, vc, stream);
+    else if (thr == 3) launch_scan_thr<3>(v, ws, tn, thr, prune_mode, vc, stream);
+    else launch_scan_thr<4>(v, ws, tn, thr, prune_mode, vc, stream);
 }
 
 } // namespace issl

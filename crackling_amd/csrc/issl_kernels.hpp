@@ -197,7 +197,9 @@ __device__ __forceinline__ uint32_t grouped_hits(uint32_t count, uint32_t slot_h
 // precalculatedScores[mask] with operator[] semantics: a missing mask contributes 0.0 (:394).
 // Reference-built tables hold masks with flags on even bits below bit 40 only; for those the image carries a
 // dense 2^20-entry table indexed by the 20 flags (one load instead of a 13-step search).
-__device__ inline double mit_lookup(const ImageView &v, uint64_t mask)
+// (View: ImageView, or the one in k_scan's kernel arguments -- VerifyCtx, KernargCtx.)
+template <class View>
+__device__ inline double mit_lookup(const View &v, uint64_t mask)
 {
     if (v.mit_dense) {
         if (mask >> 40) return 0.0;
@@ -218,7 +220,8 @@ __device__ inline double mit_lookup(const ImageView &v, uint64_t mask)
 // MIT and CFD terms of one scored off-target (isslScoreOfftargets.cpp:392-460) from the two signatures and the
 // occurrence count.  The CFD product multiplies the penalties of the mismatching positions in position order, as the
 // reference's loop over all 20 positions does (:399-460); the walk over the set flags visits the same positions.
-__device__ inline void score_terms(const ImageView &v, uint64_t gsig, uint64_t ot, uint32_t occ, bool calc_mit, bool calc_cfd,
+template <class View>
+__device__ inline void score_terms(const View &v, uint64_t gsig, uint64_t ot, uint32_t occ, bool calc_mit, bool calc_cfd,
                                    double &mit_term, double &cfd_term, int &dist_out)
 {
     mit_term = 0.0;
@@ -318,6 +321,206 @@ __device__ inline HitTerms hit_terms(const ImageView &v, uint64_t gsig, uint32_t
     t.rec.guide = g; t.rec.slice = slice; t.rec.pos = pos; t.rec.id = id;
     t.rec.dist = static_cast<uint32_t>(dist); t.rec.occ = occ;
     return t;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the exact test of one raw record (k_verify, and k_scan's tail: a scan wave verifies the chunks of records it has
+// filled itself, between two of its units)
+// ------------------------------------------------------------------------------------------------
+// One copy of the rules, in two steps so that a caller with several records per lane asks for all their loads before it
+// waits for any: verify_fetch -- the record's fields, the stream record and the guide's signature asked for together --
+// and verify_finish -- the exact test on the whole signatures, the first-matching-slice / reporter rule, the run-wise
+// count per guide, the terms, the hit slot or rank and terms by raw slot, the key written back unless the tail is lean.
+// SORTED_PRUNED: the caller knows that the batch ran the pruned plan on a sorted layout (k_scan's tail runs nowhere
+// else); the bucket tables and the list-order layouts then drop out of the code.  Every lane of the wave calls both steps
+// (verify_finish counts by wave); a lane without a record passes in_use = false.
+struct VerifyRec {
+    StreamRec sr;      // sorted layouts: what the stream holds at the record's place
+    uint64_t gsig;     // pruned plan: the guide's signature
+    uint32_t guide, bucket, slice, tile, offset;
+};
+
+// Ctx: VerifyCtx; k_scan's tail reads its own through the kernel-argument segment (KernargCtx: scalar loads made where the
+// tail runs -- loads of a by-value argument are made ahead of the scan's loop and held in registers through the passes).
+typedef const __attribute__((address_space(4))) VerifyCtx KernargCtx;
+template <bool SORTED_PRUNED, class Ctx>
+__device__ __forceinline__ VerifyRec verify_fetch(const Ctx &c, uint32_t prune_mode, uint64_t rec, bool in_use)
+{
+    const auto &v = c.v;
+    VerifyRec r;
+    r.sr = StreamRec{};
+    r.gsig = 0;
+    r.guide = kNoGuide; r.bucket = 0; r.slice = 0;
+    r.offset = static_cast<uint32_t>(rec) & (kTileCands - 1u);
+    r.tile = static_cast<uint32_t>(rec >> 11) & 0x3FFFFFFu;
+    const uint32_t gslot = static_cast<uint32_t>(rec >> 37); // pruned scan: the slot's id, not its number
+    // sorted layouts: what the stream holds at the record's place, asked for before anything else is known about it
+    if (in_use && v.srec) r.sr = v.srec[static_cast<uint64_t>(r.tile) * kTileCands + r.offset];
+    else if (in_use && v.sid) r.sr.id = v.sid[static_cast<uint64_t>(r.tile) * kTileCands + r.offset];
+    // Whose record it is.  Pruned scan: the record says so itself (slot_id: guide and slice; the bucket follows from the
+    // slice and the guide's signature, which is asked for beside the stream record, not behind it).  Bucket-level plan:
+    // the guide slot knows its guide and its bucket -- no search for the tile's.
+    if (in_use) {
+        if (SORTED_PRUNED || prune_mode) {
+            const uint64_t low = (1ull << v.slice_width) - 1ull;
+            if (gslot != kPadSlotId) slot_id_unpack(gslot, r.slice, r.guide);
+            if (r.guide >= c.n || r.slice >= v.n_slices) r.guide = kNoGuide; // (a padding slot, or no slot of this batch at all)
+            else {
+                r.gsig = c.guides[r.guide];
+                r.bucket = (r.slice << v.slice_width) + (static_cast<uint32_t>(r.gsig >> (v.slice_width * r.slice)) & static_cast<uint32_t>(low));
+            }
+        } else if constexpr (!SORTED_PRUNED) {
+            r.guide = c.gidx[gslot];
+            r.bucket = c.gbucket[gslot];
+            r.slice = r.bucket >> v.slice_width;
+        }
+    }
+    return r;
+}
+
+// `chunk`, `t`: the record's chunk and its slot there (1 .. kChunkRecs - 1 when in_use); lane: of the wave.
+template <bool SORTED_PRUNED, class Ctx>
+__device__ __forceinline__ void verify_finish(const Ctx &c, uint32_t prune_mode, const VerifyRec &r, bool in_use,
+                                              uint32_t chunk, uint32_t t, uint32_t lane)
+{
+    const auto &v = c.v;
+    const int max_dist = c.max_dist;
+    const bool calc_mit = c.calc_mit != 0u, calc_cfd = c.calc_cfd != 0u;
+    const uint64_t low = (1ull << v.slice_width) - 1ull;
+    const uint32_t guide = r.guide, bucket = r.bucket, slice = r.slice, tile = r.tile, offset = r.offset;
+    uint64_t gsig = r.gsig;
+    uint64_t key = kDeadKey;
+    double mit_term = 0.0, cfd_term = 0.0; // of a record that survives: computed here, one thread per hit, so that the
+                                           // replay (one wave per guide, a chain of dependent steps) only adds them up
+    uint64_t hit_gsig = 0, hit_ot = 0;     // ... from these
+    uint32_t hit_occ = 0;
+    const bool by_id = SORTED_PRUNED || v.srec || v.sid; // the scoring order is (slice, site id): ImageHeader
+    if (guide != kNoGuide) {
+        // Is the candidate the item's?  The scan notes only candidates of the item's own window (`keep`: not the zero
+        // padding behind a bucket, not the neighbouring group that shares the tile), so on the sorted layouts, which need
+        // nothing else from the bucket tables, the question is not asked again.  The list-order layouts find their list
+        // entry through the bucket's start and check on the way.
+        uint64_t start = 0, pos = 0;
+        bool mine = true;
+        if constexpr (!SORTED_PRUNED) if (!by_id) {
+            start = v.bucket_start[bucket];
+            pos = static_cast<uint64_t>(tile - v.tile_first[bucket]) * kTileCands + offset; // in the stream
+            mine = pos < v.bucket_start[bucket + 1] - start;
+        }
+        if (mine) {
+            if (!(SORTED_PRUNED || prune_mode)) gsig = c.guides[guide];
+            // sorted layouts: signature, site id (and a 24-bit copy of the count) come in one stream-order record, or --
+            // compact -- the id alone, with the signature behind it in the site table
+            StreamRec sr = r.sr;
+            if (v.sid) sr.sig = v.sites[sr.id]; // (the site table of a sorted layout: signature | 24-bit count << 40, like a stream record)
+            uint64_t ot = sr.sig & kSigMask;
+            if constexpr (!SORTED_PRUNED)
+                if (!by_id) ot = v.esig   ? v.esig[start + pos]
+                                 : v.occ8 ? candidate_signature(v, bucket, tile, offset) // cold sections in host memory
+                                          : v.sites[v.entries[start + pos] & 0xFFFFFFFFull];
+            if (__builtin_popcountll(mismatch_mask(gsig, ot)) <= max_dist) { // exact, full signatures (:376-382)
+                // First-matching-slice rule (equivalent of the seen bitmap, isslScoreOfftargets.cpp:385-390,463):
+                // the site was already met iff an earlier slice of the XOR is all zero.
+                const uint64_t x = gsig ^ ot;
+                if (!(SORTED_PRUNED || prune_mode)) {
+                    bool earlier = false;
+                    for (uint32_t j = 0; j < slice; ++j)
+                        if (((x >> (v.slice_width * j)) & low) == 0) earlier = true;
+                    if (!earlier) {
+                        // list-order layouts: the key carries the position in the bucket's list, which is the stream
+                        // position; sorted layouts: the site id (lists ascend by id, so the order is the same)
+                        const uint64_t lp = by_id ? sr.id : pos;
+                        key = (static_cast<uint64_t>(guide) << kKeyGuideShift) | (static_cast<uint64_t>(slice) << kKeySliceShift) | lp;
+                    }
+                } else {
+                    // Pruned scan: the guide meets this site once in every exactly matching slice whose successor
+                    // slice has at most `tol` mismatches (k_fine_count); the smallest such slice reports it, under
+                    // the slice the reference would meet it in first.
+                    const uint32_t tol = prune_mode - 1u; // 0, 1, 2 mismatches allowed in the successor slice
+                    const uint64_t mm = mismatch_mask(gsig, ot);
+                    uint32_t first = slice, reporter = slice;
+                    for (uint32_t j = slice; j-- > 0;) {
+                        if (((x >> (v.slice_width * j)) & low) != 0) continue;
+                        first = j;
+                        if (static_cast<uint32_t>(__builtin_popcount(succ_byte(mm, j, v.slice_width))) <= tol) reporter = j; // (the successor unit's flags)
+                    }
+                    if (reporter == slice)
+                        key = (static_cast<uint64_t>(guide) << kKeyGuideShift) | (static_cast<uint64_t>(first) << kKeySliceShift) | sr.id;
+                }
+                if (key != kDeadKey) { // the hit will be scored: what its terms are made of (:348)
+                    uint32_t occ = 0;
+                    if (by_id) {
+                        occ = static_cast<uint32_t>(sr.sig >> 40);
+                        if (occ == kOccSaturated) occ = v.site_occ[sr.id];
+                    } else if constexpr (!SORTED_PRUNED) {
+                        if (v.occ8) {
+                            occ = v.occ8[start + pos];
+                            if (occ == 255u) occ = static_cast<uint32_t>(v.entries[start + pos] >> 32); // (host memory)
+                        } else {
+                            occ = static_cast<uint32_t>(v.entries[start + pos] >> 32);
+                        }
+                    }
+                    hit_gsig = gsig; hit_ot = ot; hit_occ = occ;
+                }
+            }
+        }
+    }
+    // Count the hit for its guide.  The count doubles as the hit's place in the guide's segment, so that the grouping
+    // pass scatters without a second atomic (rank, by raw-record slot).  The hits of a guide in one unit lie side by
+    // side in the chunk (the scan wave notes them guide by guide): every RUN of neighbouring lanes with the same guide
+    // takes one atomic, issued by its first lane -- no loop, every run of the wave in the same instruction.  (The
+    // atomics are half of k_verify's time on a skewed index: profiles/r03_ablation_verify.log.)
+    const bool live = key != kDeadKey;
+    const uint32_t prev_guide = static_cast<uint32_t>(__shfl_up(static_cast<int>(live ? guide : kNoGuide), 1, 64));
+    const bool continues = live && lane != 0u && prev_guide == guide;    // (a dead lane never equals a live one: kNoGuide)
+    const uint64_t starts = __ballot(!continues);                        // first lanes of runs, and the dead lanes
+    uint32_t rank = 0;
+    if (starts == ~0ull) { // (uniform over the wave) no runs, the usual case on an even index: everybody for itself
+        if (live) rank = atomicAdd(&c.gcount[guide], 1u);
+    } else {
+        const uint64_t upto = (lane == 63u ? 0ull : (~0ull << (lane + 1u))); // the lanes above this one
+        const uint32_t head = 63u - static_cast<uint32_t>(__builtin_clzll(starts & ~upto)); // lane 0 always starts: never empty
+        const uint64_t later = starts & upto;
+        const uint32_t next = later ? static_cast<uint32_t>(__builtin_ctzll(later)) : 64u;
+        uint32_t base = 0;
+        if (live && !continues) base = atomicAdd(&c.gcount[guide], next - lane); // the run is [lane, next)
+        rank = static_cast<uint32_t>(__shfl(static_cast<int>(base), static_cast<int>(head), 64)) + (lane - head);
+    }
+    if (live && rank == kReplayLds) atomicAdd(&c.counters->overflowed, 1u); // the guide's first hit beyond what k_replay takes
+    if (live && rank < c.slot_hits) {
+        // hit slots (Workspace): the hit goes to its final place at once and takes no part in the grouping pass
+        int dist;
+        score_terms(v, hit_gsig, hit_ot, hit_occ, calc_mit, calc_cfd, mit_term, cfd_term, dist);
+        const uint64_t at = static_cast<uint64_t>(guide) * c.slot_hits + rank;
+        SlotRec s;
+        s.mit = mit_term; s.cfd = cfd_term; s.key = key;
+        s.pad = slot_pad(hit_occ, static_cast<uint32_t>(dist)); // (read by k_profile alone)
+        c.slots[at] = s;
+        key = kDeadKey;
+    } else if (live) {
+        const uint64_t slot = static_cast<uint64_t>(chunk) * (kChunkRecs - 1u) + (t - 1u); // < cap_chunks * 127 <= cap_hits
+        c.rank[slot] = rank;
+        // The terms (:392-460) -- unless the guide already has more hits than the replays that read them take
+        // (k_replay, k_replay_mid): the many-hit replay works out the terms of the hits it walks by itself, and on
+        // skewed data most hits belong to such guides and lie behind their early exit.
+        if (rank < kMidHits) {
+            int dist;
+            score_terms(v, hit_gsig, hit_ot, hit_occ, calc_mit, calc_cfd, mit_term, cfd_term, dist);
+            reinterpret_cast<double2 *>(c.pay)[slot] = make_double2(mit_term, cfd_term);
+        }
+    }
+    // (a lean batch has no grouping pass to read the keys back -- every hit went to its guide's slots, or the batch is run
+    // again in full: 8 bytes per record that need not be written)
+    if (in_use && !c.lean_tail) c.raw[static_cast<uint64_t>(chunk) * kChunkRecs + t] = key;
+}
+
+// Both steps at once: one record per lane (k_verify).
+template <bool SORTED_PRUNED, class Ctx>
+__device__ __forceinline__ void verify_record(const Ctx &c, uint32_t prune_mode, uint64_t rec, bool in_use, uint32_t chunk,
+                                              uint32_t t, uint32_t lane)
+{
+    const VerifyRec r = verify_fetch<SORTED_PRUNED>(c, prune_mode, rec, in_use);
+    verify_finish<SORTED_PRUNED>(c, prune_mode, r, in_use, chunk, t, lane);
 }
 
 } // namespace issl

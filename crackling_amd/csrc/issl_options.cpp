@@ -91,6 +91,8 @@ Tuning Tuning::from_env()
         if (o.put) o.put(t, o.def);
     const char *timing = std::getenv("ISSL_UPLOAD_TIMING"); // (environment only)
     t.upload_timing = timing && timing[0] == '1';
+    const char *scan_verify = std::getenv("ISSL_SCAN_VERIFY"); // (environment only; 0 = the scan's waves verify nothing, 1 = also every wave's last chunk)
+    t.scan_verify = !scan_verify ? -1 : std::strcmp(scan_verify, "0") == 0 ? 0 : std::strcmp(scan_verify, "1") == 0 ? 1 : -1; // (anything else: as unset)
     for (const Option &o : kOptions)
         if (const char *e = std::getenv(o.env)) (void)t.set(o.key, e); // values out of range leave the default
     return t;

@@ -64,6 +64,8 @@ void release_lanes(issl_index *ix)
     ix->proven_guides = 0;
     ix->proven_chunks = 0;
     ix->proven_dist = -1;
+    ix->plan_cands_per_guide = 0.0;
+    ix->plan_cands_prune = 0;
     ix->prev_scan_end = nullptr;
     ix->prev_batch_end = nullptr;
 }
@@ -238,6 +240,26 @@ int ensure_workspace(issl_index *ix, size_t n, Lane &lane, uint32_t fine_ways)
 // a batch run on the lane's stream, its verify / group / replay on the lane's high-priority tail stream; the scans of
 // consecutive batches are chained by events, so that they run one after the other at full speed while the short, latency-
 // bound tail of batch i runs beside the scan of batch i + 1 -- a step then costs max(bin + scan, tail) instead of their sum.
+// Is a batch worth the builds of scan and verify that can run the verify tail (Workspace::scan_verify)?  The batch's plan
+// decides on the device whether the tail is armed (PlanInfo::scan_tail: kScanTailCands planned comparisons per scan wave);
+// the launch that merely could arm it is measurably slower than the one that cannot (64 guides +2 %, 10 k guides x 50 M
+// sites +1.4 %, profiles/ab_scan_verify_bench.log), so the host asks the same question first with what it knows: the mean
+// group length of the index (an even index plans n x slices x ways x that), with a factor two of slack -- or, where the
+// handle has finished a batch under the same prune mode, what that batch's plan came to per guide (a clustered or skewed
+// index plans far more than its mean says).  A "no" here only means k_verify does the batch's records, as it always did.
+static uint32_t tail_worth_arming(const issl_index *ix, size_t n, uint32_t prune_mode)
+{
+    const Tuning &tn = ix->tuning;
+    if (tn.scan_verify == 0 || prune_mode == 0 || !(ix->view.srec || ix->view.sid)) return 0u;
+    if (tn.scan_verify > 0) return 2u;
+    const double want = static_cast<double>(kScanTailCands) * scan_waves(tn);
+    const double slices = static_cast<double>(ix->hdr.n_slices);
+    const double mean_group = static_cast<double>(ix->hdr.n_sites) * slices / (static_cast<double>(ix->hdr.n_buckets) * 256.0);
+    const double even = static_cast<double>(n) * slices * fine_ways_of(prune_mode) * mean_group;
+    const double learnt = ix->plan_cands_prune == prune_mode ? ix->plan_cands_per_guide * static_cast<double>(n) : 0.0;
+    return (2.0 * even >= want || learnt >= want) ? 1u : 0u;
+}
+
 static int enqueue_batch(issl_index *ix, Lane &lane, hipStream_t stream, const uint64_t *d_guides, size_t n, int max_dist,
                          double threshold, int method, double *d_mit, double *d_cfd, bool dump, bool staged,
                          int lanes_mode = 1, issl_profile *d_profile = nullptr)
@@ -276,6 +298,7 @@ static int enqueue_batch(issl_index *ix, Lane &lane, hipStream_t stream, const u
     // issl_dump_hits wants every hit of the batch in one array in guide order: no hit slots there
     ws.slot_hits = (!dump && tn.hit_slots && ws.cap_slot_guides >= n) ? ws.slot_width : 0u;
     ws.lean_tail = (lane.lean && ws.slot_hits >= kSlotHits && tn.lean_tail) ? 1u : 0u;
+    ws.scan_verify = max_dist < 0 ? 0u : tail_worth_arming(ix, n, prune_mode);
     ScoreParams p;
     p.max_dist = max_dist;
     p.method = method;
@@ -297,7 +320,7 @@ static int enqueue_batch(issl_index *ix, Lane &lane, hipStream_t stream, const u
     if (pipelined && ix->prev_scan_end) HIP_TRY(hipStreamWaitEvent(stream, ix->prev_scan_end, 0)); // one scan at a time
     if (bin_ahead && ix->prev_batch_end) HIP_TRY(hipStreamWaitEvent(stream, ix->prev_batch_end, 0)); // the batch before is through
     if (scan_pair) HIP_TRY(hipEventRecord(ix->ring[2 * slot], stream));
-    launch_scan(ix->view, ws, tn, d_guides, n32, max_dist, prune_mode, stream);
+    launch_scan(ix->view, ws, tn, d_guides, n32, p, prune_mode, stream);
     if (scan_pair) HIP_TRY(hipEventRecord(ix->ring[2 * slot + 1], stream));
     if (scan_pair) ix->n_ring += 1;
     if (staged) HIP_TRY(hipEventRecord(lane.ev[2], stream));
@@ -307,7 +330,7 @@ static int enqueue_batch(issl_index *ix, Lane &lane, hipStream_t stream, const u
         HIP_TRY(hipStreamWaitEvent(tail, ix->ring[2 * slot + 1], 0));
         ix->prev_scan_end = ix->ring[2 * slot + 1];
     }
-    launch_verify(ix->view, ws, d_guides, static_cast<uint32_t>(n), p, tail);
+    launch_verify(ix->view, ws, tn, d_guides, static_cast<uint32_t>(n), p, tail);
     if (staged) HIP_TRY(hipEventRecord(lane.ev[3], tail));
     launch_group_hits(ws, n32, tail);
     if (staged) HIP_TRY(hipEventRecord(lane.ev[4], tail));
@@ -383,9 +406,10 @@ int finish_batches(issl_index *ix, hipStream_t stream)
         // Hit slots: when a good part of the last batch's guides had more than kSlotHits hits -- an index of billions of sites, a
         // skewed genome -- the next batches get slots for kSlotHitsWide of them (6.5 GB per 100 k guides), so that only what
         // lies beyond THAT passes through the grouping pass.  A matter of speed only: the results do not depend on the width.
+        Counters c{};
+        HIP_TRY(hipMemcpy(&c, lp->ws.counters, sizeof c, hipMemcpyDeviceToHost));
+        lp->scan_verified = c.scan_verified; // (ws_scan_verified: the records of the lane's last batch that the scan's own waves verified)
         if (lp->ws.slots && lp->ws.slot_width == kSlotHits && ix->tuning.hit_slots && lp->last_n) {
-            Counters c{};
-            HIP_TRY(hipMemcpy(&c, lp->ws.counters, sizeof c, hipMemcpyDeviceToHost));
             const size_t want = lp->ws.cap_slot_guides * size_t(kSlotHitsWide) * sizeof(SlotRec);
             size_t free_b = 0, total_b = 0;
             if (c.overflowed > lp->last_n / 8 && want <= kSlotBytesMax && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
@@ -425,6 +449,10 @@ int finish_batches(issl_index *ix, hipStream_t stream)
     PlanInfo pl{};
     uint32_t total_hits = 0;
     HIP_TRY(hipMemcpy(&pl, lane.ws.plan, sizeof pl, hipMemcpyDeviceToHost));
+    if (pl.fine != 0u && lane.last_n != 0u && lane.last_max_dist >= 0) { // (tail_worth_arming)
+        ix->plan_cands_per_guide = static_cast<double>(pl.candidates) / lane.last_n;
+        ix->plan_cands_prune = pl.fine;
+    }
     {   // scored off-targets of the last batch before any early exit: the per-guide counts k_verify left
         std::vector<uint32_t> counts(lane.last_n);
         if (lane.last_n) HIP_TRY(hipMemcpy(counts.data(), lane.ws.gcount, 4 * counts.size(), hipMemcpyDeviceToHost));

@@ -285,7 +285,12 @@ int issl_index_attach_image_cold(int device, void *dev_buf, size_t bytes, void *
  *     high-priority stream beside the next batch's scan; with 3 only the BINNING of a batch (its short, latency-bound
  *     launches) runs beside the batch before it, the scan waits for that batch's replay.  Outputs of two consecutive
  *     batches must be different buffers with either
- *   scan_stamps (ISSL_SCAN_STAMPS) file for per-wave clocks (diagnostics) */
+ *   scan_stamps (ISSL_SCAN_STAMPS) file for per-wave clocks (diagnostics)
+ * Environment only (no key): ISSL_SCAN_VERIFY 0|1 (default: unset): behind the pruned plan on a sorted image a scan wave applies
+ *   the exact test to the chunks of records it has filled itself, between two of its units, while the other waves of its
+ *   SIMD go on comparing -- and, once it has filled a chunk, to its last one when its range is done; the verify kernel
+ *   takes the rest.  1: every wave's last chunk too (tests: the tail on batches of a few records); 0: every record is the
+ *   verify kernel's (A/B).  The results are the same with all three */
 int issl_index_set_option(issl_index *idx, const char *key, const char *value);
 /* Current value of an integer knob; also the read-only keys is_sorted, is_compact, cold_on_host, cold_sections (0, 1 =
  * slice lists, 3 = lists + site table in host memory), lists_absent, has_inline_sigs and dense_mit (layout of the uploaded image, -1
@@ -293,7 +298,8 @@ int issl_index_set_option(issl_index *idx, const char *key, const char *value);
  * refuses them with ISSL_E_ARG): ws_cap_guides (guides its arrays hold), ws_slot_width (hit slots per guide: 512 or 2048),
  * ws_fine_ways (placements per guide and bucket the pruned plan's arrays are sized for: 13 or 67), ws_cap_chunks (chunks of
  * the raw-record buffer), ws_cap_fitems (items of the pruned plan's list), ws_lean (1: the next batch is enqueued without
- * the grouping pass and the many-hit replays). */
+ * the grouping pass and the many-hit replays), ws_scan_verified (raw records of the lane's last finished batch that the scan's
+ * own waves verified; the verify kernel took the others). */
 int issl_index_get_option(const issl_index *idx, const char *key, long long *value);
 
 /* ---- guides (A2, isslScoreOfftargets.cpp:63-71,82-89,275-305) ---------------------------- */
