@@ -24,6 +24,8 @@ from .scorer import (  # noqa: F401
     PROFILE_DTYPE,
     SEARCH_HIT_DTYPE,
     SEARCH_QUERY_DTYPE,
+    SNP_DTYPE,
+    VARIANT_HIT_DTYPE,
     encode_guides,
     extract_offtargets,
     decode_guides,
@@ -32,6 +34,7 @@ from .scorer import (  # noqa: F401
     run_scorer_binary,
     parse_scorer_output,
     search_prepare,
+    vcf_snps,
     verdicts,
 )
 
@@ -76,5 +79,5 @@ __all__ = [
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",
     "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LANDING_DTYPE", "LANDING_PROFILE_DTYPE", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH", "SEARCH_HIT_DTYPE", "SEARCH_QUERY_DTYPE", "search_prepare",
-    "BULGE_HIT_DTYPE",
+    "BULGE_HIT_DTYPE", "VARIANT_HIT_DTYPE", "SNP_DTYPE", "vcf_snps",
 ]

@@ -98,6 +98,22 @@ class BulgeHit(C.Structure):
                 ("strand", C.c_uint8), ("dist", C.c_uint8), ("bulge", C.c_int8), ("at", C.c_uint8)]
 
 
+class VariantHit(C.Structure):
+    """issl_variant_hit: 40 bytes, no padding."""
+    _fields_ = [("pos", C.c_uint64), ("site", C.c_uint32 * 4), ("record", C.c_uint32), ("query", C.c_uint32), ("mism", C.c_uint32),
+                ("strand", C.c_uint8), ("dist", C.c_uint8), ("n_var", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class Snp(C.Structure):
+    """issl_snp: 16 bytes."""
+    _fields_ = [("pos", C.c_uint64), ("record", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class VcfCounts(C.Structure):
+    """issl_vcf_counts: 48 bytes."""
+    _fields_ = [(n, C.c_uint64) for n in ("lines", "snps", "alleles_skipped", "no_allele", "unknown_chrom", "beyond_record")]
+
+
 class TranscriptHitsRow(C.Structure):
     """issl_transcript_hits: 16 bytes."""
     _fields_ = [("hit", C.c_uint32), ("total", C.c_uint32), ("status", C.c_uint32), ("first", C.c_uint32)]
@@ -229,6 +245,14 @@ _protos = {
     "issl_genome_search_bulges_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "issl_genome_search_bulges_profile": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P]),
     "issl_genome_search_bulges_profile_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P]),
+    "issl_genome_search_variants": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_genome_search_variants_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_genome_search_variants_profile": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P]),
+    "issl_genome_search_variants_profile_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P]),
+    "issl_vcf_snps": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u64p, C.c_size_t, _P, C.c_size_t,
+                                C.POINTER(C.c_size_t), C.POINTER(VcfCounts)]),
+    "issl_genome_apply_snps": (C.c_int, [_P, _P, C.c_size_t, _u64p]),
+    "issl_genome_apply_vcf": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(VcfCounts), _u64p]),
     "issl_genome_occurrences": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P]),
     "issl_genome_occurrences_device": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "issl_genome_occurrences_paged": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P]),

@@ -1,6 +1,6 @@
 // bin/isslSearchGenome -- where queries bind in a genome with up to max_dist mismatches, for any PAM pattern:
 //
-//   isslSearchGenome [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R] <pattern> <query file> <max_dist> <FASTA ...|directory>
+//   isslSearchGenome [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R] [--variants N] [--vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>
 //
 // pattern: 1 to 32 IUPAC codes (ACGTRYSWKMBDHVN), e.g. NNNNNNNNNNNNNNNNNNNNNGG or TTTVNNNNNNNNNNNNNNNNNNNN.  The query file has
 // one query per line over ACGTN ("\n" or "\r\n" line ends, a trailing blank line is ignored), every line of the pattern's
@@ -18,6 +18,13 @@
 // bases are in lower case, its unpaired bases in upper case.  Nothing is filtered: a locus that matches without a bulge is
 // listed under the shifted windows of the other bulges too.  --profile then prints <query text> and the R + D + 1 groups
 // (R3.., 0, ..D3) of max_dist + 1 counts, tab-separated.  --dna-bulge or --rna-bulge without --guide is a usage error.
+// With --variants N the search reads IUPAC ambiguity codes in the genome as sets of bases (issl_genome_search_variants):
+// a window of the codes ACGTRYSWKMBDHV with at most N ambiguous positions is compared, and dist is the least distance over
+// the sequences it stands for.  --vcf FILE first writes the SNPs of a plain-text VCF into the resident genome as such codes
+// (issl_genome_apply_vcf; CHROM is a record's name up to its first blank) and prints one line of counts to stderr; without
+// --variants it implies --variants L, the pattern's length.  A row line is as without the option, the site in IUPAC
+// letters: lower case where the position does not match, upper case elsewhere.  --profile lines are as without the option.
+// --variants or --vcf together with --guide is a usage error.
 // The FASTA arguments follow bin/extractOfftargets: one input or several, a lone directory stands for its non-hidden
 // entries.  stdout carries data only, diagnostics go to stderr, exit status 1 on any error.
 //   ISSL_DEVICE=<n>       HIP device to use (default 0)
@@ -33,9 +40,11 @@
 #define ISSL_CLI_API(X)                                                                                                   \
     X(issl_last_error) X(issl_abi_version) X(issl_genome_open_files) X(issl_genome_record)                                  \
     X(issl_genome_search) X(issl_genome_search_profile) X(issl_genome_search_bulges) X(issl_genome_search_bulges_profile)             \
+    X(issl_genome_search_variants) X(issl_genome_search_variants_profile) X(issl_genome_apply_vcf)                          \
     X(issl_genome_close)
 #include "cli_api.hpp"
 #include "issl_search_text.hpp"
+#include "issl_variants_text.hpp"
 
 // The rows of one search, one line each: search(hits, cap, &total) is the library call -- asked for the total first, then
 // with room for it -- and line(record name, its length, row) appends a row's text.  ok: false after a short write on
@@ -64,19 +73,20 @@ int main(int argc, char **argv)
 {
     namespace st = issl::search_text;
     bool profile = false, usage = false;
-    const char *guide = nullptr, *dna = nullptr, *rna = nullptr;
+    const char *guide = nullptr, *dna = nullptr, *rna = nullptr, *variants = nullptr, *vcf = nullptr;
     std::vector<const char *> pos;
     for (int i = 1; i < argc; ++i) {
         const char **value = !std::strcmp(argv[i], "--guide") ? &guide : !std::strcmp(argv[i], "--dna-bulge") ? &dna
-                             : !std::strcmp(argv[i], "--rna-bulge") ? &rna : nullptr;
+                             : !std::strcmp(argv[i], "--rna-bulge") ? &rna : !std::strcmp(argv[i], "--variants") ? &variants
+                             : !std::strcmp(argv[i], "--vcf") ? &vcf : nullptr;
         if (value) {
             if (i + 1 < argc) *value = argv[++i];
             else usage = true;
         } else if (!std::strcmp(argv[i], "--profile")) profile = true;
         else pos.push_back(argv[i]);
     }
-    if (usage || pos.size() < 4 || ((dna || rna) && !guide)) {
-        std::fprintf(stderr, "Usage: %s [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R] <pattern> <query file> <max_dist> <FASTA ...|directory>\n",
+    if (usage || pos.size() < 4 || ((dna || rna) && !guide) || ((variants || vcf) && guide)) {
+        std::fprintf(stderr, "Usage: %s [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R] [--variants N] [--vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>\n",
                      argv[0]);
         return 1;
     }
@@ -114,7 +124,19 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "max_dist '%s': a number from 0 to the pattern's length %u\n", pos[2], pat.length);
         return 1;
     }
-    std::string text, packed;
+    long max_variants = static_cast<long>(pat.length); // (--vcf alone)
+    if (variants) {
+        max_variants = std::strtol(variants, &end, 10);
+        if (end == variants || *end || max_variants < 0 || max_variants > static_cast<long>(pat.length)) {
+            std::fprintf(stderr, "--variants '%s': a number from 0 to the pattern's length %u\n", variants, pat.length);
+            return 1;
+        }
+    }
+    std::string text, packed, vcf_text;
+    if (vcf && !read_text_file(vcf, vcf_text)) {
+        std::fprintf(stderr, "cannot open '%s'\n", vcf);
+        return 1;
+    }
     if (!read_text_file(pos[1], text)) {
         std::fprintf(stderr, "cannot open '%s'\n", pos[1]);
         return 1;
@@ -137,6 +159,16 @@ int main(int argc, char **argv)
     const char *dev = std::getenv("ISSL_DEVICE");
     issl_genome *g = nullptr;
     if (api.issl_genome_open_files(pos.data() + 3, static_cast<int>(pos.size() - 3), dev ? std::atoi(dev) : 0, &g)) return fail("cannot open genome");
+    if (vcf) {
+        issl_vcf_counts vc{};
+        uint64_t changed = 0;
+        if (api.issl_genome_apply_vcf(g, vcf_text.data(), vcf_text.size(), &vc, &changed)) return fail("cannot apply the VCF");
+        std::fprintf(stderr, "vcf: lines %llu snps %llu alleles_skipped %llu no_allele %llu unknown_chrom %llu beyond_record %llu changed %llu\n",
+                     static_cast<unsigned long long>(vc.lines), static_cast<unsigned long long>(vc.snps),
+                     static_cast<unsigned long long>(vc.alleles_skipped), static_cast<unsigned long long>(vc.no_allele),
+                     static_cast<unsigned long long>(vc.unknown_chrom), static_cast<unsigned long long>(vc.beyond_record),
+                     static_cast<unsigned long long>(changed));
+    }
     StdoutText so;
     bool ok = true;
     std::vector<uint64_t> offsets(n + 1);
@@ -155,6 +187,23 @@ int main(int argc, char **argv)
         };
         if (!print_rows<issl_bulge_hit>(g, so, ok, search, [&](const char *name, size_t name_len, const issl_bulge_hit &hit) {
             st::append_bulge_line(so.text, packed.data() + static_cast<size_t>(hit.query) * L, L, bg.guide_start, name, name_len, hit);
+            }))
+            return 1;
+    } else if ((variants || vcf) && profile) {
+        std::vector<uint64_t> counts(n * (D + 1));
+        if (api.issl_genome_search_variants_profile(g, &pat, queries.data(), n, static_cast<int>(D), static_cast<int>(max_variants), counts.data()))
+            return fail("search failed");
+        for (size_t k = 0; ok && k < n; ++k) {
+            st::append_profile_line(so.text, packed.data() + k * L, L, counts.data() + k * (D + 1), D);
+            ok = so.wrote();
+        }
+    } else if (variants || vcf) {
+        auto search = [&](issl_variant_hit *hits, size_t cap, size_t *total) {
+            return api.issl_genome_search_variants(g, &pat, queries.data(), n, static_cast<int>(D), static_cast<int>(max_variants),
+                                                   offsets.data(), hits, cap, total);
+        };
+        if (!print_rows<issl_variant_hit>(g, so, ok, search, [&](const char *name, size_t name_len, const issl_variant_hit &hit) {
+            issl::variants_text::append_variant_line(so.text, packed.data() + static_cast<size_t>(hit.query) * L, L, name, name_len, hit);
             }))
             return 1;
     } else if (profile) {

@@ -1,5 +1,6 @@
-// The text-search core of the index-free genome search: the protocol that k_search (issl_search.hip: mismatches only) and
-// k_bulge (issl_bulge.hip: DNA and RNA bulges beside them) follow, and the device pieces they share, __device__
+// The text-search core of the index-free genome search: the protocol that k_search (issl_search.hip: mismatches only),
+// k_bulge (issl_bulge.hip: DNA and RNA bulges beside them) and k_variants (issl_variants.hip: IUPAC codes in the text as
+// sets of bases, on bit planes in place of the 2-bit codes below) follow, and the device pieces they share, __device__
 // __forceinline__ in an anonymous namespace, one copy per translation unit, like issl_radix.hpp.
 //
 // One piece of queries (2^22 of them, less the low bits a unit adds to its hit word), everything on one stream, the
@@ -24,7 +25,7 @@
 // and distance (profile_hits); no row exists anywhere.
 // The host waits for the number of hit words (sizes the buffers of the sort) and for the end of a piece.
 //
-// What is not in here although both kernels have it: the tile front (pack16 loads, pattern test, compaction), the
+// What is not in here although the kernels have it: the tile front (pack16 loads, pattern test, compaction), the
 // survivor's fetch, the walk over the query groups and the kCount reduction.  The compiler finishes a function before it
 // inlines it, and each of these came back with operands of commutative instructions swapped or two instructions in the
 // other order (profiles/search_core_isa.txt); they stay written out until the kernels may change.

@@ -1,5 +1,5 @@
-// What the two kernel units of the genome search share (issl_search.hip: mismatches only; issl_bulge.hip: DNA and RNA
-// bulges beside them) beside the device pieces of issl_search_core.hpp: the tile's 16-base words, the query group a wave
+// What the kernel units of the genome search share (issl_search.hip: mismatches only; issl_bulge.hip: DNA and RNA
+// bulges beside them; issl_variants.hip: IUPAC codes in the text) beside the device pieces of issl_search_core.hpp: the tile's 16-base words, the query group a wave
 // fetches at once, the offsets kernel, the checks every entry point makes before any device work, and the host driver of
 // a unit (SearchDriver: pieces, rows, profile, the bodies of the entry points).  Kernels and device functions live in an
 // anonymous namespace, one copy per translation unit, like issl_radix.hpp.
@@ -116,8 +116,8 @@ inline int upload_queries(issl_genome *g, const issl_search_query *queries, size
 }
 
 // ---- the driver of a unit ------------------------------------------------------------------------------------------
-// The host side of the protocol (issl_search_core.hpp), once for both units.  A unit describes itself with a struct U:
-//   Row, Call              the row type; what a checked call carries to the launches (SearchArgs, BulgeCall)
+// The host side of the protocol (issl_search_core.hpp), once for every unit.  A unit describes itself with a struct U:
+//   Row, Call              the row type; what a checked call carries to the launches (SearchArgs, BulgeCall, VariantCall)
 //   kPieceQueries          queries per piece;  kLowBits: the bits of the hit word below the strand
 //   kTag, kRows            "[issl search]" / "hits" of the timing lines;  counted(c): what follows "N queries" there
 //   nothing(g, c, n)       is there nothing to search

@@ -22,6 +22,9 @@ OFFTARGET_DTYPE = np.dtype([("site", "<u8"), ("mit", "<f8"), ("cfd", "<f8"), ("g
 SEARCH_QUERY_DTYPE = np.dtype([("sig", "<u8"), ("care", "<u8")])  # issl_search_query (16 bytes)
 SEARCH_HIT_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
                              ("strand", "u1"), ("dist", "u1"), ("reserved", "u1", (2,))])  # issl_search_hit (32 bytes)
+VARIANT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("site", "<u4", (4,)), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
+                              ("strand", "u1"), ("dist", "u1"), ("n_var", "u1"), ("reserved", "u1")])  # issl_variant_hit (40 bytes)
+SNP_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("ref", "u1"), ("alt", "u1"), ("reserved", "u1", (2,))])  # issl_snp (16 bytes)
 BULGE_HIT_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
                             ("strand", "u1"), ("dist", "u1"), ("bulge", "i1"), ("at", "u1")])  # issl_bulge_hit (32 bytes)
 LOCATION_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("strand", "<u4")])  # issl_location (16 bytes)
@@ -494,6 +497,25 @@ def search_prepare(pattern, queries):
     return pat, out
 
 
+def vcf_snps(vcf, records):
+    """issl_vcf_snps: the SNPs of a VCF's text (bytes; plain text, no gzip) for records = [(name, length), ...] as
+    Genome.records lists them; CHROM is compared with a name up to its first blank.  -> (a SNP_DTYPE array, one entry per
+    usable line in file order, and a dict of counts: lines, snps, alleles_skipped, no_allele, unknown_chrom,
+    beyond_record).  No device needed.  A malformed line raises IsslError naming it."""
+    vcf = bytes(vcf)
+    names = [n.encode() if isinstance(n, str) else bytes(n) for n, _ in records]
+    k = len(names)
+    c_names = (C.c_char_p * max(k, 1))(*names)
+    c_lens = (C.c_size_t * max(k, 1))(*[len(n) for n in names])
+    c_lengths = (C.c_uint64 * max(k, 1))(*[int(length) for _, length in records])
+    n, counts = C.c_size_t(), _lib.VcfCounts()
+    check(lib.issl_vcf_snps(vcf, len(vcf), c_names, c_lens, c_lengths, k, None, 0, C.byref(n), C.byref(counts)))
+    out = np.zeros(n.value, dtype=SNP_DTYPE)
+    if n.value:
+        check(lib.issl_vcf_snps(vcf, len(vcf), c_names, c_lens, c_lengths, k, out.ctypes.data, n.value, C.byref(n), C.byref(counts)))
+    return out, {name: int(getattr(counts, name)) for name, _ in counts._fields_}
+
+
 def _search_pattern(pattern):
     return pattern if isinstance(pattern, _lib.SearchPattern) else search_prepare(pattern, [])[0]
 
@@ -578,40 +600,41 @@ class Genome:
         return n.value
 
     # The four call shapes of the search entry points; `extra` is what a unit passes between the pattern and the queries
-    # (nothing, or the bulge limits).
-    def _search_rows(self, fn, dtype, pattern, extra, queries, max_dist):
+    # (nothing, or the bulge limits), `after` what it passes behind max_dist (nothing, or max_variants).
+    def _search_rows(self, fn, dtype, pattern, extra, queries, max_dist, after=()):
         pat, q = _search_args(pattern, queries)
         offsets = np.zeros(len(q) + 1, dtype=np.uint64)
         n = C.c_size_t()
-        args = (self._h, C.byref(pat), *extra, q.ctypes.data if len(q) else None, len(q), int(max_dist), offsets.ctypes.data)
+        args = (self._h, C.byref(pat), *extra, q.ctypes.data if len(q) else None, len(q), int(max_dist), *after,
+                offsets.ctypes.data)
         check(fn(*args, None, 0, C.byref(n)))  # the counting call, then the filling call
         hits = np.zeros(n.value, dtype=dtype)
         if n.value:
             check(fn(*args, hits.ctypes.data, n.value, C.byref(n)))
         return offsets, hits
 
-    def _search_counts(self, fn, pattern, extra, queries, max_dist, shape):
+    def _search_counts(self, fn, pattern, extra, queries, max_dist, shape, after=()):
         pat, q = _search_args(pattern, queries)
         counts = np.zeros((len(q),) + shape, dtype=np.uint64)
-        check(fn(self._h, C.byref(pat), *extra, q.ctypes.data if len(q) else None, len(q), int(max_dist),
+        check(fn(self._h, C.byref(pat), *extra, q.ctypes.data if len(q) else None, len(q), int(max_dist), *after,
                  counts.ctypes.data if len(q) else None))
         return counts
 
-    def _search_rows_device(self, fn, dtype, pattern, extra, d_queries, max_dist, d_offsets, d_hits, stream):
+    def _search_rows_device(self, fn, dtype, pattern, extra, d_queries, max_dist, d_offsets, d_hits, stream, after=()):
         pat = _search_pattern(pattern)
         nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
         n = C.c_size_t()
         cap = d_hits.numel() * d_hits.element_size() // dtype.itemsize if d_hits is not None else 0
-        check(fn(self._h, C.byref(pat), *extra, d_queries.data_ptr() if nq else None, nq, int(max_dist), d_offsets.data_ptr(),
+        check(fn(self._h, C.byref(pat), *extra, d_queries.data_ptr() if nq else None, nq, int(max_dist), *after, d_offsets.data_ptr(),
                  d_hits.data_ptr() if cap else None, cap, C.byref(n), C.c_void_p(stream) if stream else None))
         return n.value
 
-    def _search_counts_device(self, fn, pattern, extra, d_queries, max_dist, d_counts, bins, words, stream):
+    def _search_counts_device(self, fn, pattern, extra, d_queries, max_dist, d_counts, bins, words, stream, after=()):
         pat = _search_pattern(pattern)
         nq = d_queries.numel() * d_queries.element_size() // SEARCH_QUERY_DTYPE.itemsize
         if d_counts.numel() * d_counts.element_size() < 8 * nq * bins:
             raise ValueError("d_counts holds fewer than " + words + " words")
-        check(fn(self._h, C.byref(pat), *extra, d_queries.data_ptr() if nq else None, nq, int(max_dist),
+        check(fn(self._h, C.byref(pat), *extra, d_queries.data_ptr() if nq else None, nq, int(max_dist), *after,
                  d_counts.data_ptr() if nq else None, C.c_void_p(stream) if stream else None))
 
     def search(self, pattern, queries, max_dist=4):
@@ -672,6 +695,53 @@ class Genome:
         self._search_counts_device(lib.issl_genome_search_bulges_profile_device, pattern, (C.byref(bg),), d_queries, max_dist, d_counts,
                                    (int(rna_bulge) + int(dna_bulge) + 1) * (int(max_dist) + 1),
                                    "n * (rna_bulge + dna_bulge + 1) * (max_dist + 1)", stream)
+
+    def search_variants(self, pattern, queries, max_dist=4, max_variants=2):
+        """search() on a text with IUPAC ambiguity codes read as sets of bases (issl_genome_search_variants of
+        include/issl_hip.h): a window of the 14 codes ACGTRYSWKMBDHV with at most max_variants ambiguous positions hits
+        when the least distance over the sequences it stands for is within max_dist.  -> (offsets uint64[n + 1], hits) as
+        search(), hits in VARIANT_HIT_DTYPE: `site` is four masks, site[b] bit i set when base b of ACGT is in the set the
+        strand reads at i; `n_var` the window's ambiguous positions."""
+        return self._search_rows(lib.issl_genome_search_variants, VARIANT_HIT_DTYPE, pattern, (), queries, max_dist, (int(max_variants),))
+
+    def search_variants_profile(self, pattern, queries, max_dist=4, max_variants=2):
+        """-> uint64 array [n, max_dist + 1]: the rows of search_variants() of query k at distance d, counted on the device."""
+        return self._search_counts(lib.issl_genome_search_variants_profile, pattern, (), queries, max_dist, (int(max_dist) + 1,),
+                                   (int(max_variants),))
+
+    def search_variants_device(self, pattern, d_queries, d_offsets, d_hits, max_dist=4, max_variants=2, stream=None):
+        """search_device() for search_variants(): d_hits is a uint8 CUDA tensor (40 bytes per row, VARIANT_HIT_DTYPE) or None
+        for the counting call.  -> the number of rows; nothing is written when they do not fit d_hits."""
+        return self._search_rows_device(lib.issl_genome_search_variants_device, VARIANT_HIT_DTYPE, pattern, (), d_queries, max_dist,
+                                        d_offsets, d_hits, stream, (int(max_variants),))
+
+    def search_variants_profile_device(self, pattern, d_queries, d_counts, max_dist=4, max_variants=2, stream=None):
+        """d_counts: int64 CUDA tensor of n * (max_dist + 1) words.  Returns when they are written."""
+        self._search_counts_device(lib.issl_genome_search_variants_profile_device, pattern, (), d_queries, max_dist, d_counts,
+                                   int(max_dist) + 1, "n * (max_dist + 1)", stream, (int(max_variants),))
+
+    def apply_snps(self, snps):
+        """Write SNPs into the resident text as ambiguity codes (issl_genome_apply_snps): snps is a SNP_DTYPE array (record,
+        0-based pos, ref as one bit of A C G T = 1 2 4 8, alt as a set of them).  -> the number of places whose byte
+        changed.  A ref the text does not hold raises IsslError and leaves the text as it was.  The text stays changed for
+        every later call on this handle; locate, occurrences, search and search_bulges skip windows over an ambiguity code."""
+        snps = np.ascontiguousarray(snps, dtype=SNP_DTYPE)
+        changed = C.c_uint64()
+        check(lib.issl_genome_apply_snps(self._h, snps.ctypes.data if len(snps) else None, len(snps), C.byref(changed)))
+        return changed.value
+
+    def apply_vcf(self, vcf):
+        """apply_snps() for the SNPs of a VCF (bytes, or a path to a plain-text file).  -> the counts of vcf_snps() with
+        "changed", the number of places whose byte changed."""
+        if not isinstance(vcf, (bytes, bytearray, memoryview)):
+            with open(vcf, "rb") as fh:
+                vcf = fh.read()
+        vcf = bytes(vcf)
+        counts, changed = _lib.VcfCounts(), C.c_uint64()
+        check(lib.issl_genome_apply_vcf(self._h, vcf, len(vcf), C.byref(counts), C.byref(changed)))
+        out = {name: int(getattr(counts, name)) for name, _ in counts._fields_}
+        out["changed"] = changed.value
+        return out
 
     def occurrences(self, sites, page_length=0, page_starts=None):
         """The Bowtie step (Crackling.py:600-725) as exact counts.  sites: 20-mer strings or a uint64 array of packed

@@ -624,6 +624,80 @@ int issl_genome_search_bulges_profile_device(issl_genome *g, const issl_search_p
                                              const issl_search_query *d_queries, size_t n, int max_dist, uint64_t *d_counts,
                                              void *stream);
 
+/* ---- variant-aware genome search: IUPAC codes in the text, SNPs from a VCF ------------------------------------------------ */
+/* A reference assembly is one haplotype; a SNP can create an off-target, or a PAM, that it does not show.  This search
+ * reads IUPAC ambiguity codes in the handle's text as sets of bases.  issl_genome_search_variants* is issl_genome_search*
+ * with the differences below; everything not named is the plain search's rule: pattern, query alphabet, pos in forward
+ * coordinates for both strands, the sort by (record, pos, strand), the capacity rule, *n_total, the limit of 2^32 - 1
+ * rows, n == 0, duplicated queries, "the bytes do not depend on the cut into pieces", the argument errors and
+ * ISSL_LOCATE_TIMING.
+ *   window    w = seq[pos : pos + L] of ONE record, every character one of the 14 codes A C G T R Y S W K M B D H V.  N
+ *             disqualifies the window, as does any other byte and the record separator: an assembly gap matches nothing.
+ *             S(c) is the set of bases code c stands for; a position is AMBIGUOUS when S(c) has more than one base.  A
+ *             window with more than max_variants ambiguous positions is disqualified (max_variants: 0..L)
+ *   strand    strand 0 reads the sets T[i] = S(w[i]); strand 1 reads T[i] = comp(S(w[L-1-i])), comp mapping a set base by
+ *             base, A<->T and C<->G: R<->Y, K<->M, B<->V, D<->H, S and W are their own complements
+ *   hit       A[i] = T[i] intersected with the bases pattern[i] allows.  The window-strand is admitted when every A[i] is
+ *             non-empty.  Position i MATCHES when q[i] is N or q[i] is in A[i]; dist is the number of positions that do not
+ *             match, and dist <= max_dist is a hit.  Equivalently dist is the least distance of issl_genome_search over all
+ *             the sequences the window stands for that the pattern admits: the positions are independent.  A base the
+ *             text's set holds but the pattern forbids is a mismatch
+ *   row       issl_variant_hit.  site[b] bit i is set when base b of A C G T is in T[i] -- the set the strand reads, NOT
+ *             intersected with the pattern; the convention of issl_search_pattern.allow.  mism bit i: position i does not
+ *             match.  n_var: the ambiguous positions of the window.  reserved = 0
+ *   profile   counts[k * (max_dist + 1) + d], as for issl_genome_search_profile
+ * max_variants outside 0..L: ISSL_E_ARG before any device work.  With max_variants = 0 on any text, and with any
+ * max_variants on a text without ambiguity codes, the rows are those of issl_genome_search field by field, site re-encoded
+ * one-hot and n_var = 0.  Bulges together with variants are not offered. */
+typedef struct { uint64_t pos; uint32_t site[4]; uint32_t record; uint32_t query; uint32_t mism;
+                 uint8_t strand; uint8_t dist; uint8_t n_var; uint8_t reserved; } issl_variant_hit; /* 40 B, no padding */
+int issl_genome_search_variants(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *queries, size_t n, int max_dist,
+                                int max_variants, uint64_t *offsets, issl_variant_hit *hits, size_t cap, size_t *n_total);
+int issl_genome_search_variants_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *d_queries, size_t n,
+                                       int max_dist, int max_variants, uint64_t *d_offsets, issl_variant_hit *d_hits, size_t cap,
+                                       size_t *n_total, void *stream);
+int issl_genome_search_variants_profile(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *queries, size_t n,
+                                        int max_dist, int max_variants, uint64_t *counts /* n * (max_dist + 1) */);
+int issl_genome_search_variants_profile_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *d_queries,
+                                               size_t n, int max_dist, int max_variants, uint64_t *d_counts, void *stream);
+
+/* SNPs onto a resident genome.  An issl_snp names a place (record, 0-based pos inside it), its reference base `ref` (one
+ * bit of A C G T = 1, 2, 4, 8) and a non-empty set `alt` of alternative bases (bits of the same).
+ *
+ * issl_vcf_snps reads them from the text of a VCF file (plain text, no gzip).  Host only, no device needed.  names,
+ * name_lens and lengths describe the n_records records as issl_genome_record gives them.
+ *   lines     end with "\n" or "\r\n"; empty lines and lines that begin with '#' are skipped.  Fields are tab-separated;
+ *             CHROM POS REF ALT are fields 1, 2, 4, 5.  A line with fewer than five fields or a POS that is not all digits:
+ *             ISSL_E_ARG, the message names the line (1-based)
+ *   CHROM     is compared with a record's name up to its first blank (space, TAB, LF, VT, FF, CR), the first record of a
+ *             name standing for it.  No such record: the line is skipped and counted in unknown_chrom
+ *   POS       1-based.  0 or beyond the record: skipped and counted in beyond_record
+ *   alleles   a line counts when REF is one base of ACGT (either case); of its comma-separated ALT alleles those that are
+ *             one base of ACGT are taken and ORed into one issl_snp.  Every other allele -- an indel, `*`, `.`, a symbolic
+ *             <...>, and every allele of a line whose REF is not one base -- is skipped and counted in alleles_skipped; a
+ *             line without a usable allele is counted in no_allele
+ * The checks are made in this order, and a skipped line is counted once.  out receives one entry per remaining line in file
+ * order; *n is always complete, and when *n > cap nothing is written (out == NULL with cap == 0 is the counting call).
+ * counts may be NULL.
+ *
+ * issl_genome_apply_snps writes them into the handle's text as ambiguity codes.  The host checks the ranges (record, pos,
+ * ref one bit, alt 1..15), sorts by (record, pos) and merges the entries of one place: their ref must agree, their alt is
+ * ORed.  On the device every place is checked first: the text byte must be one of the 14 codes and hold ref, and its set
+ * united with alt must not be all four bases (that letter is N, which no window may hold).  If any check
+ * fails the call returns ISSL_E_ARG, the message names the smallest failing input index, and the text is untouched.
+ * Otherwise the byte becomes the letter of S(byte) united with alt.  *n_changed (may be NULL): the places whose byte changed;
+ * applying the same list again changes nothing.  THE HANDLE'S TEXT IS CHANGED FOR EVERY LATER CALL: issl_genome_locate,
+ * issl_genome_occurrences, issl_genome_search and issl_genome_search_bulges skip every window over an ambiguity code as
+ * over any byte outside ACGT.  issl_genome_apply_vcf chains the two with the handle's own records. */
+typedef struct { uint64_t pos; uint32_t record; uint8_t ref; uint8_t alt; uint8_t reserved[2]; } issl_snp; /* 16 B */
+typedef struct { uint64_t lines;           /* data lines read */
+                 uint64_t snps;            /* entries they gave (*n) */
+                 uint64_t alleles_skipped; uint64_t no_allele; uint64_t unknown_chrom; uint64_t beyond_record; } issl_vcf_counts; /* 48 B */
+int issl_vcf_snps(const char *vcf, size_t len, const char *const *names, const size_t *name_lens, const uint64_t *lengths,
+                  size_t n_records, issl_snp *out, size_t cap, size_t *n, issl_vcf_counts *counts);
+int issl_genome_apply_snps(issl_genome *g, const issl_snp *snps, size_t n, uint64_t *n_changed);
+int issl_genome_apply_vcf(issl_genome *g, const char *vcf, size_t len, issl_vcf_counts *counts, uint64_t *n_changed);
+
 /* ---- the Bowtie step: exact occurrences of a guide's eight reads ----------------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:600-725 on a genome handle.  For every guide the reference aligns eight reads,
  * the guide's 20-mer followed by AGG, CGG, GGG, TGG, AAG, CAG, GAG, TAG (variants 0..7), and counts the reads that align
