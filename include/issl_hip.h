@@ -688,7 +688,12 @@ int issl_genome_search_variants_profile_device(issl_genome *g, const issl_search
  * Otherwise the byte becomes the letter of S(byte) united with alt.  *n_changed (may be NULL): the places whose byte changed;
  * applying the same list again changes nothing.  THE HANDLE'S TEXT IS CHANGED FOR EVERY LATER CALL: issl_genome_locate,
  * issl_genome_occurrences, issl_genome_search and issl_genome_search_bulges skip every window over an ambiguity code as
- * over any byte outside ACGT.  issl_genome_apply_vcf chains the two with the handle's own records. */
+ * over any byte outside ACGT, in their host and _device forms.  So do the other entry points that scan the handle's text,
+ * none of which keeps a copy of it or an index over it: issl_genome_occurrences_paged* (the pass of
+ * issl_genome_occurrences with other page boundaries) and issl_offtarget_landings* / issl_offtarget_landing_profile* (locate's
+ * scan: an off-target whose every place now holds a code is counted in `absent`, one that kept some of its places has fewer
+ * landings than `occ`, which stays the index's count).  Only issl_genome_search_variants* reads a code as a set of bases.
+ * issl_genome_apply_vcf chains the two with the handle's own records. */
 typedef struct { uint64_t pos; uint32_t record; uint8_t ref; uint8_t alt; uint8_t reserved[2]; } issl_snp; /* 16 B */
 typedef struct { uint64_t lines;           /* data lines read */
                  uint64_t snps;            /* entries they gave (*n) */
