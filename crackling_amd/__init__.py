@@ -10,6 +10,7 @@ library raises immediately -- there is no CPU fallback.
 from ._lib import lib, IsslError, LIB_PATH  # noqa: F401
 from .scorer import (  # noqa: F401
     BULGE_HIT_DTYPE,
+    BULGE_VARIANT_HIT_DTYPE,
     GUIDE_DTYPE,
     Genome,
     GuideSet,
@@ -79,5 +80,5 @@ __all__ = [
     "CONSENSUS_DTYPE", "Consensus", "FOLD_DTYPE", "SCAFFOLD", "load_sgrnascorer2", "read_rnafold_output",
     "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LANDING_DTYPE", "LANDING_PROFILE_DTYPE", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH", "SEARCH_HIT_DTYPE", "SEARCH_QUERY_DTYPE", "search_prepare",
-    "BULGE_HIT_DTYPE", "VARIANT_HIT_DTYPE", "SNP_DTYPE", "vcf_snps",
+    "BULGE_HIT_DTYPE", "VARIANT_HIT_DTYPE", "BULGE_VARIANT_HIT_DTYPE", "SNP_DTYPE", "vcf_snps",
 ]

@@ -104,6 +104,13 @@ class VariantHit(C.Structure):
                 ("strand", C.c_uint8), ("dist", C.c_uint8), ("n_var", C.c_uint8), ("reserved", C.c_uint8)]
 
 
+class BulgeVariantHit(C.Structure):
+    """issl_bulge_variant_hit: 48 bytes, no padding."""
+    _fields_ = [("pos", C.c_uint64), ("site", C.c_uint32 * 4), ("record", C.c_uint32), ("query", C.c_uint32), ("mism", C.c_uint32),
+                ("strand", C.c_uint8), ("dist", C.c_uint8), ("n_var", C.c_uint8), ("bulge", C.c_int8), ("at", C.c_uint8),
+                ("reserved", C.c_uint8 * 7)]
+
+
 class Snp(C.Structure):
     """issl_snp: 16 bytes."""
     _fields_ = [("pos", C.c_uint64), ("record", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8), ("reserved", C.c_uint8 * 2)]
@@ -245,6 +252,10 @@ _protos = {
     "issl_genome_search_bulges_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "issl_genome_search_bulges_profile": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P]),
     "issl_genome_search_bulges_profile_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P]),
+    "issl_genome_search_bulges_variants": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_genome_search_bulges_variants_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_genome_search_bulges_variants_profile": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P]),
+    "issl_genome_search_bulges_variants_profile_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P]),
     "issl_genome_search_variants": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "issl_genome_search_variants_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "issl_genome_search_variants_profile": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P]),

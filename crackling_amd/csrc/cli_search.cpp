@@ -1,6 +1,6 @@
 // bin/isslSearchGenome -- where queries bind in a genome with up to max_dist mismatches, for any PAM pattern:
 //
-//   isslSearchGenome [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R] [--variants N] [--vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>
+//   isslSearchGenome [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R [--guide-variants N] [--guide-vcf FILE]] [--variants N] [--vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>
 //
 // pattern: 1 to 32 IUPAC codes (ACGTRYSWKMBDHVN), e.g. NNNNNNNNNNNNNNNNNNNNNGG or TTTVNNNNNNNNNNNNNNNNNNNN.  The query file has
 // one query per line over ACGTN ("\n" or "\r\n" line ends, a trailing blank line is ignored), every line of the pattern's
@@ -25,6 +25,11 @@
 // --variants it implies --variants L, the pattern's length.  A row line is as without the option, the site in IUPAC
 // letters: lower case where the position does not match, upper case elsewhere.  --profile lines are as without the option.
 // --variants or --vcf together with --guide is a usage error.
+// With --guide, --guide-variants N and --guide-vcf FILE are their counterparts for the search with bulges
+// (issl_genome_search_bulges_variants): the window of L + bulge codes may hold at most N ambiguous positions, its unpaired
+// bases included; --guide-vcf applies the VCF first and prints the counts line to stderr, and alone it implies N = L.  A row
+// line is --guide's with the site in IUPAC letters: lower case where the position does not match, upper case elsewhere,
+// '-' at an RNA bulge.  --profile prints --guide's groups.  Either option without --guide is a usage error.
 // The FASTA arguments follow bin/extractOfftargets: one input or several, a lone directory stands for its non-hidden
 // entries.  stdout carries data only, diagnostics go to stderr, exit status 1 on any error.
 //   ISSL_DEVICE=<n>       HIP device to use (default 0)
@@ -41,8 +46,10 @@
     X(issl_last_error) X(issl_abi_version) X(issl_genome_open_files) X(issl_genome_record)                                  \
     X(issl_genome_search) X(issl_genome_search_profile) X(issl_genome_search_bulges) X(issl_genome_search_bulges_profile)             \
     X(issl_genome_search_variants) X(issl_genome_search_variants_profile) X(issl_genome_apply_vcf)                          \
+    X(issl_genome_search_bulges_variants) X(issl_genome_search_bulges_variants_profile)                                     \
     X(issl_genome_close)
 #include "cli_api.hpp"
+#include "issl_bulge_variants_text.hpp"
 #include "issl_search_text.hpp"
 #include "issl_variants_text.hpp"
 
@@ -73,20 +80,22 @@ int main(int argc, char **argv)
 {
     namespace st = issl::search_text;
     bool profile = false, usage = false;
-    const char *guide = nullptr, *dna = nullptr, *rna = nullptr, *variants = nullptr, *vcf = nullptr;
+    const char *guide = nullptr, *dna = nullptr, *rna = nullptr, *variants = nullptr, *vcf = nullptr, *guide_variants = nullptr,
+               *guide_vcf = nullptr;
     std::vector<const char *> pos;
     for (int i = 1; i < argc; ++i) {
         const char **value = !std::strcmp(argv[i], "--guide") ? &guide : !std::strcmp(argv[i], "--dna-bulge") ? &dna
                              : !std::strcmp(argv[i], "--rna-bulge") ? &rna : !std::strcmp(argv[i], "--variants") ? &variants
-                             : !std::strcmp(argv[i], "--vcf") ? &vcf : nullptr;
+                             : !std::strcmp(argv[i], "--vcf") ? &vcf : !std::strcmp(argv[i], "--guide-variants") ? &guide_variants
+                             : !std::strcmp(argv[i], "--guide-vcf") ? &guide_vcf : nullptr;
         if (value) {
             if (i + 1 < argc) *value = argv[++i];
             else usage = true;
         } else if (!std::strcmp(argv[i], "--profile")) profile = true;
         else pos.push_back(argv[i]);
     }
-    if (usage || pos.size() < 4 || ((dna || rna) && !guide) || ((variants || vcf) && guide)) {
-        std::fprintf(stderr, "Usage: %s [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R] [--variants N] [--vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>\n",
+    if (usage || pos.size() < 4 || ((dna || rna || guide_variants || guide_vcf) && !guide) || ((variants || vcf) && guide)) {
+        std::fprintf(stderr, "Usage: %s [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R [--guide-variants N] [--guide-vcf FILE]] [--variants N] [--vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>\n",
                      argv[0]);
         return 1;
     }
@@ -124,14 +133,17 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "max_dist '%s': a number from 0 to the pattern's length %u\n", pos[2], pat.length);
         return 1;
     }
-    long max_variants = static_cast<long>(pat.length); // (--vcf alone)
-    if (variants) {
-        max_variants = std::strtol(variants, &end, 10);
-        if (end == variants || *end || max_variants < 0 || max_variants > static_cast<long>(pat.length)) {
-            std::fprintf(stderr, "--variants '%s': a number from 0 to the pattern's length %u\n", variants, pat.length);
+    long max_variants = static_cast<long>(pat.length); // (--vcf or --guide-vcf alone)
+    if (variants || guide_variants) {
+        const char *given = variants ? variants : guide_variants;
+        max_variants = std::strtol(given, &end, 10);
+        if (end == given || *end || max_variants < 0 || max_variants > static_cast<long>(pat.length)) {
+            std::fprintf(stderr, "%s '%s': a number from 0 to the pattern's length %u\n", variants ? "--variants" : "--guide-variants", given,
+                         pat.length);
             return 1;
         }
     }
+    if (guide_vcf) vcf = guide_vcf; // (read and applied the same way)
     std::string text, packed, vcf_text;
     if (vcf && !read_text_file(vcf, vcf_text)) {
         std::fprintf(stderr, "cannot open '%s'\n", vcf);
@@ -173,7 +185,27 @@ int main(int argc, char **argv)
     bool ok = true;
     std::vector<uint64_t> offsets(n + 1);
     const uint32_t L = pat.length, D = static_cast<uint32_t>(max_dist);
-    if (guide && profile) {
+    if (guide && (guide_variants || guide_vcf) && profile) {
+        const uint32_t bins = (bg.max_rna + bg.max_dna + 1) * (D + 1);
+        std::vector<uint64_t> counts(n * bins);
+        if (api.issl_genome_search_bulges_variants_profile(g, &pat, &bg, queries.data(), n, static_cast<int>(D), static_cast<int>(max_variants),
+                                                           counts.data()))
+            return fail("search failed");
+        for (size_t k = 0; ok && k < n; ++k) {
+            st::append_profile_line(so.text, packed.data() + k * L, L, counts.data() + k * bins, bins - 1);
+            ok = so.wrote();
+        }
+    } else if (guide && (guide_variants || guide_vcf)) {
+        auto search = [&](issl_bulge_variant_hit *hits, size_t cap, size_t *total) {
+            return api.issl_genome_search_bulges_variants(g, &pat, &bg, queries.data(), n, static_cast<int>(D), static_cast<int>(max_variants),
+                                                          offsets.data(), hits, cap, total);
+        };
+        if (!print_rows<issl_bulge_variant_hit>(g, so, ok, search, [&](const char *name, size_t name_len, const issl_bulge_variant_hit &hit) {
+            issl::bulge_variants_text::append_bulge_variant_line(so.text, packed.data() + static_cast<size_t>(hit.query) * L, L, bg.guide_start,
+                                                                 name, name_len, hit);
+            }))
+            return 1;
+    } else if (guide && profile) {
         const uint32_t bins = (bg.max_rna + bg.max_dna + 1) * (D + 1);
         std::vector<uint64_t> counts(n * bins);
         if (api.issl_genome_search_bulges_profile(g, &pat, &bg, queries.data(), n, static_cast<int>(D), counts.data())) return fail("search failed");

@@ -1,6 +1,7 @@
 // The text-search core of the index-free genome search: the protocol that k_search (issl_search.hip: mismatches only),
-// k_bulge (issl_bulge.hip: DNA and RNA bulges beside them) and k_variants (issl_variants.hip: IUPAC codes in the text as
-// sets of bases, on bit planes in place of the 2-bit codes below) follow, and the device pieces they share, __device__
+// k_bulge (issl_bulge.hip: DNA and RNA bulges beside them), k_variants (issl_variants.hip: IUPAC codes in the text as
+// sets of bases, on bit planes in place of the 2-bit codes below) and k_bulge_variants (issl_bulge_variants.hip: the
+// bulges on those bit planes) follow, and the device pieces they share, __device__
 // __forceinline__ in an anonymous namespace, one copy per translation unit, like issl_radix.hpp.
 //
 // One piece of queries (2^22 of them, less the low bits a unit adds to its hit word), everything on one stream, the

@@ -1,5 +1,5 @@
 // What the kernel units of the genome search share (issl_search.hip: mismatches only; issl_bulge.hip: DNA and RNA
-// bulges beside them; issl_variants.hip: IUPAC codes in the text) beside the device pieces of issl_search_core.hpp: the tile's 16-base words, the query group a wave
+// bulges beside them; issl_variants.hip: IUPAC codes in the text; issl_bulge_variants.hip: both) beside the device pieces of issl_search_core.hpp: the tile's 16-base words, the query group a wave
 // fetches at once, the offsets kernel, the checks every entry point makes before any device work, and the host driver of
 // a unit (SearchDriver: pieces, rows, profile, the bodies of the entry points).  Kernels and device functions live in an
 // anonymous namespace, one copy per translation unit, like issl_radix.hpp.

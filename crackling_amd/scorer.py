@@ -25,6 +25,9 @@ SEARCH_HIT_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"),
 VARIANT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("site", "<u4", (4,)), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
                               ("strand", "u1"), ("dist", "u1"), ("n_var", "u1"), ("reserved", "u1")])  # issl_variant_hit (40 bytes)
 SNP_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("ref", "u1"), ("alt", "u1"), ("reserved", "u1", (2,))])  # issl_snp (16 bytes)
+BULGE_VARIANT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("site", "<u4", (4,)), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
+                                    ("strand", "u1"), ("dist", "u1"), ("n_var", "u1"), ("bulge", "i1"), ("at", "u1"),
+                                    ("reserved", "u1", (7,))])  # issl_bulge_variant_hit (48 bytes)
 BULGE_HIT_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
                             ("strand", "u1"), ("dist", "u1"), ("bulge", "i1"), ("at", "u1")])  # issl_bulge_hit (32 bytes)
 LOCATION_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("strand", "<u4")])  # issl_location (16 bytes)
@@ -719,6 +722,41 @@ class Genome:
         """d_counts: int64 CUDA tensor of n * (max_dist + 1) words.  Returns when they are written."""
         self._search_counts_device(lib.issl_genome_search_variants_profile_device, pattern, (), d_queries, max_dist, d_counts,
                                    int(max_dist) + 1, "n * (max_dist + 1)", stream, (int(max_variants),))
+
+    def search_bulges_variants(self, pattern, queries, span, max_dist=4, dna_bulge=1, rna_bulge=1, max_variants=2):
+        """search_bulges() on a text with IUPAC ambiguity codes read as sets of bases (issl_genome_search_bulges_variants of
+        include/issl_hip.h): the window of L + bulge codes ACGTRYSWKMBDHV may hold at most max_variants ambiguous
+        positions, its unpaired bases included, and `dist` is the least distance over the sequences it stands for and the
+        break points.  -> (offsets uint64[n + 1], hits) as search_bulges(), hits in BULGE_VARIANT_HIT_DTYPE: `site` is four
+        masks as in VARIANT_HIT_DTYPE, L + bulge positions; `n_var` the window's ambiguous positions."""
+        bg = _search_bulges(span, dna_bulge, rna_bulge)
+        return self._search_rows(lib.issl_genome_search_bulges_variants, BULGE_VARIANT_HIT_DTYPE, pattern, (C.byref(bg),), queries, max_dist,
+                                 (int(max_variants),))
+
+    def search_bulges_variants_profile(self, pattern, queries, span, max_dist=4, dna_bulge=1, rna_bulge=1, max_variants=2):
+        """-> uint64 array [n, rna_bulge + dna_bulge + 1, max_dist + 1]: the rows of search_bulges_variants() of query k with
+        bulge b (at index b + rna_bulge) at minimum distance d, counted on the device."""
+        bg = _search_bulges(span, dna_bulge, rna_bulge)
+        return self._search_counts(lib.issl_genome_search_bulges_variants_profile, pattern, (C.byref(bg),), queries, max_dist,
+                                   (int(rna_bulge) + int(dna_bulge) + 1, int(max_dist) + 1), (int(max_variants),))
+
+    def search_bulges_variants_device(self, pattern, d_queries, d_offsets, d_hits, span, max_dist=4, dna_bulge=1, rna_bulge=1,
+                                      max_variants=2, stream=None):
+        """search_bulges_device() for search_bulges_variants(): d_hits is a uint8 CUDA tensor (48 bytes per row,
+        BULGE_VARIANT_HIT_DTYPE) or None for the counting call.  -> the number of rows; nothing is written when they do not
+        fit d_hits."""
+        bg = _search_bulges(span, dna_bulge, rna_bulge)
+        return self._search_rows_device(lib.issl_genome_search_bulges_variants_device, BULGE_VARIANT_HIT_DTYPE, pattern, (C.byref(bg),),
+                                        d_queries, max_dist, d_offsets, d_hits, stream, (int(max_variants),))
+
+    def search_bulges_variants_profile_device(self, pattern, d_queries, d_counts, span, max_dist=4, dna_bulge=1, rna_bulge=1,
+                                              max_variants=2, stream=None):
+        """d_counts: int64 CUDA tensor of n * (rna_bulge + dna_bulge + 1) * (max_dist + 1) words.  Returns when they are
+        written."""
+        bg = _search_bulges(span, dna_bulge, rna_bulge)
+        self._search_counts_device(lib.issl_genome_search_bulges_variants_profile_device, pattern, (C.byref(bg),), d_queries, max_dist,
+                                   d_counts, (int(rna_bulge) + int(dna_bulge) + 1) * (int(max_dist) + 1),
+                                   "n * (rna_bulge + dna_bulge + 1) * (max_dist + 1)", stream, (int(max_variants),))
 
     def apply_snps(self, snps):
         """Write SNPs into the resident text as ambiguity codes (issl_genome_apply_snps): snps is a SNP_DTYPE array (record,

@@ -648,7 +648,7 @@ int issl_genome_search_bulges_profile_device(issl_genome *g, const issl_search_p
  *   profile   counts[k * (max_dist + 1) + d], as for issl_genome_search_profile
  * max_variants outside 0..L: ISSL_E_ARG before any device work.  With max_variants = 0 on any text, and with any
  * max_variants on a text without ambiguity codes, the rows are those of issl_genome_search field by field, site re-encoded
- * one-hot and n_var = 0.  Bulges together with variants are not offered. */
+ * one-hot and n_var = 0.  Bulges on such a text: issl_genome_search_bulges_variants*, below. */
 typedef struct { uint64_t pos; uint32_t site[4]; uint32_t record; uint32_t query; uint32_t mism;
                  uint8_t strand; uint8_t dist; uint8_t n_var; uint8_t reserved; } issl_variant_hit; /* 40 B, no padding */
 int issl_genome_search_variants(issl_genome *g, const issl_search_pattern *pat, const issl_search_query *queries, size_t n, int max_dist,
@@ -692,7 +692,8 @@ int issl_genome_search_variants_profile_device(issl_genome *g, const issl_search
  * none of which keeps a copy of it or an index over it: issl_genome_occurrences_paged* (the pass of
  * issl_genome_occurrences with other page boundaries) and issl_offtarget_landings* / issl_offtarget_landing_profile* (locate's
  * scan: an off-target whose every place now holds a code is counted in `absent`, one that kept some of its places has fewer
- * landings than `occ`, which stays the index's count).  Only issl_genome_search_variants* reads a code as a set of bases.
+ * landings than `occ`, which stays the index's count).  Only issl_genome_search_variants* and
+ * issl_genome_search_bulges_variants* read a code as a set of bases.
  * issl_genome_apply_vcf chains the two with the handle's own records. */
 typedef struct { uint64_t pos; uint32_t record; uint8_t ref; uint8_t alt; uint8_t reserved[2]; } issl_snp; /* 16 B */
 typedef struct { uint64_t lines;           /* data lines read */
@@ -702,6 +703,46 @@ int issl_vcf_snps(const char *vcf, size_t len, const char *const *names, const s
                   size_t n_records, issl_snp *out, size_t cap, size_t *n, issl_vcf_counts *counts);
 int issl_genome_apply_snps(issl_genome *g, const issl_snp *snps, size_t n, uint64_t *n_changed);
 int issl_genome_apply_vcf(issl_genome *g, const char *vcf, size_t len, issl_vcf_counts *counts, uint64_t *n_changed);
+
+/* ---- genome search with bulges on a variant-aware text ------------------------------------------------------------------ */
+/* Where a guide binds with mismatches and a bulge on any haplotype the text's ambiguity codes stand for: a SNP can create a
+ * bulged off-target that the reference assembly does not show, as it can create a mismatch one.
+ * issl_genome_search_bulges_variants* is issl_genome_search_bulges* with issl_genome_search_variants in the place where its
+ * definition names issl_genome_search.  Everything not named below is the bulge search's rule: the span, the limits D and R
+ * and their checks, the alignments (b, i) and the derived pairs P' and q', `at` as the smallest break point that reaches
+ * the minimum, mism in query coordinates, NO FILTERING, the order (record, pos, strand, bulge as a signed number), the
+ * capacity rule and *n_total, the limit of 2^32 - 1 rows, n == 0, duplicated queries, "the bytes do not depend on the cut
+ * into pieces" (of 2^19 queries), and every ISSL_E_ARG of the bulge search.
+ *   hit       alignment (b, i) hits at a window of L + b characters when that window is a hit of
+ *             issl_genome_search_variants for (P', q', max_dist, max_variants); dist(b, i) is that distance
+ *   window    every character is one of the 14 codes A C G T R Y S W K M B D H V; N, any other byte and a record end
+ *             disqualify it.  The ambiguous positions are counted over all L + b characters, the unpaired bases of a DNA
+ *             bulge included; more than max_variants of them disqualify the window for this b (and only for this b: the
+ *             windows of the other b at the same pos have other characters)
+ *   match     a position matches when the query's base is in the text's set cut by the pattern's; a base the text holds
+ *             but the pattern forbids is a mismatch; a window-strand is admitted when every position's cut set is non-empty
+ *   row       issl_bulge_variant_hit.  site: the sets the strand reads, NOT cut by the pattern, L + b positions, in
+ *             issl_variant_hit.site's convention; n_var: the ambiguous positions of the window; reserved = 0
+ *   profile   counts[(k * (R + D + 1) + (b + R)) * (max_dist + 1) + dist], as for issl_genome_search_bulges_profile
+ * max_variants outside 0..L: ISSL_E_ARG before any device work.  With D = R = 0 the rows are those of
+ * issl_genome_search_variants field by field, with bulge = at = 0.  With max_variants = 0 on any text, and with any
+ * max_variants on a text without ambiguity codes, the rows are those of issl_genome_search_bulges field by field, site
+ * re-encoded one-hot and n_var = 0.  ISSL_LOCATE_TIMING=1 prints one stderr line per piece, tagged [issl bulges+variants]. */
+typedef struct { uint64_t pos; uint32_t site[4]; uint32_t record; uint32_t query; uint32_t mism;
+                 uint8_t strand; uint8_t dist; uint8_t n_var; int8_t bulge; uint8_t at; uint8_t reserved[7]; } issl_bulge_variant_hit; /* 48 B, no padding */
+int issl_genome_search_bulges_variants(issl_genome *g, const issl_search_pattern *pat, const issl_search_bulges *bulges,
+                                       const issl_search_query *queries, size_t n, int max_dist, int max_variants, uint64_t *offsets,
+                                       issl_bulge_variant_hit *hits, size_t cap, size_t *n_total);
+int issl_genome_search_bulges_variants_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_bulges *bulges,
+                                              const issl_search_query *d_queries, size_t n, int max_dist, int max_variants,
+                                              uint64_t *d_offsets, issl_bulge_variant_hit *d_hits, size_t cap, size_t *n_total,
+                                              void *stream);
+int issl_genome_search_bulges_variants_profile(issl_genome *g, const issl_search_pattern *pat, const issl_search_bulges *bulges,
+                                               const issl_search_query *queries, size_t n, int max_dist, int max_variants,
+                                               uint64_t *counts /* n * (R + D + 1) * (max_dist + 1) */);
+int issl_genome_search_bulges_variants_profile_device(issl_genome *g, const issl_search_pattern *pat, const issl_search_bulges *bulges,
+                                                      const issl_search_query *d_queries, size_t n, int max_dist, int max_variants,
+                                                      uint64_t *d_counts, void *stream);
 
 /* ---- the Bowtie step: exact occurrences of a guide's eight reads ----------------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:600-725 on a genome handle.  For every guide the reference aligns eight reads,
