@@ -16,7 +16,7 @@ all: $(LIB) bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOffta
 # The library: one object per source under build/obj/, the same flags for kernels and host code; the header dependencies
 # come from the compiler (-MMD -MP).
 SRCS = issl_kernels.hip issl_bin.hip issl_verify.hip issl_group.hip issl_replay.hip issl_report.hip issl_extract.hip \
-       issl_locate.hip issl_search.hip issl_bulge.hip issl_variants.hip issl_bulge_variants.hip issl_landing.hip issl_occur.hip issl_guides.hip issl_consensus.hip issl_build.hip issl_transcripts.hip issl_results.hip issl_results.cpp issl_folds.hip issl_folds.cpp issl_runlog.hip issl_annotation.cpp issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
+       issl_locate.hip issl_search.hip issl_bulge.hip issl_variants.hip issl_bulge_variants.hip issl_haplotypes.hip issl_landing.hip issl_occur.hip issl_guides.hip issl_consensus.hip issl_build.hip issl_transcripts.hip issl_results.hip issl_results.cpp issl_folds.hip issl_folds.cpp issl_runlog.hip issl_annotation.cpp issl_capi.cpp issl_upload.cpp issl_pipeline.cpp issl_options.cpp issl_host.cpp issl_text.cpp issl_node.cpp
 OBJDIR = build/obj
 OBJS   = $(addprefix $(OBJDIR)/,$(addsuffix .o,$(SRCS)))  # (the suffix stays in the name: issl_results.hip and issl_results.cpp)
 COMPILE = $(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<
@@ -42,7 +42,7 @@ $(LIB): $(OBJS) $(CSRC)/libissl_hip.map
 #   isslLandOfftargets    off-target landings: guide, site, place in the genome, transcript hits (records or --profile)
 #   isslSearchGenome      index-free search: any PAM pattern, any length up to 32, up to k mismatches, with --guide also DNA and
 #                         RNA bulges, with --variants / --vcf IUPAC codes in the text and SNPs of a VCF, with --guide-variants /
-#                         --guide-vcf both together (rows or --profile)
+#                         --guide-vcf both together, with --indel-vcf the ALT haplotypes of a VCF's indels (rows or --profile)
 DLOPEN_EXES = bin/isslScoreOfftargets bin/isslReportOfftargets bin/isslLocateOfftargets bin/cracklingGuides bin/cracklingBowtie \
               bin/countHitTranscripts bin/isslLandOfftargets bin/isslSearchGenome
 bin/isslScoreOfftargets: $(CSRC)/cli_score.cpp $(CSRC)/issl_host.hpp
@@ -52,7 +52,7 @@ bin/cracklingGuides: $(CSRC)/cli_guides.cpp
 bin/cracklingBowtie: $(CSRC)/cli_bowtie.cpp
 bin/countHitTranscripts: $(CSRC)/cli_transcripts.cpp
 bin/isslLandOfftargets: $(CSRC)/cli_landing.cpp
-bin/isslSearchGenome: $(CSRC)/cli_search.cpp $(CSRC)/issl_search_text.hpp $(CSRC)/issl_variants_text.hpp $(CSRC)/issl_bulge_variants_text.hpp
+bin/isslSearchGenome: $(CSRC)/cli_search.cpp $(CSRC)/issl_search_text.hpp $(CSRC)/issl_variants_text.hpp $(CSRC)/issl_bulge_variants_text.hpp $(CSRC)/issl_haplotypes_text.hpp
 $(DLOPEN_EXES): $(CSRC)/cli_api.hpp include/issl_hip.h $(LIB)
 	@mkdir -p bin
 	g++ $(CXXFLAGS) -o $@ $(filter %.cpp,$^) -lpthread -ldl

@@ -12,6 +12,9 @@ from .scorer import (  # noqa: F401
     BULGE_HIT_DTYPE,
     BULGE_VARIANT_HIT_DTYPE,
     GUIDE_DTYPE,
+    HAPLOTYPE_HIT_DTYPE,
+    Haplotypes,
+    INDEL_DTYPE,
     Genome,
     GuideSet,
     IsslIndex,
@@ -35,6 +38,7 @@ from .scorer import (  # noqa: F401
     run_scorer_binary,
     parse_scorer_output,
     search_prepare,
+    vcf_indels,
     vcf_snps,
     verdicts,
 )
@@ -81,4 +85,5 @@ __all__ = [
     "GUIDE_DTYPE", "Genome", "GuideSet", "IsslIndex", "IsslNode", "IsslError", "LANDING_DTYPE", "LANDING_PROFILE_DTYPE", "LOCATION_DTYPE", "METHODS", "OFFTARGET_DTYPE", "PROFILE_DTYPE", "encode_guides", "extract_offtargets", "decode_guides", "format_scores", "format_scores_native",
     "run_scorer_binary", "parse_scorer_output", "verdicts", "lib", "LIB_PATH", "SEARCH_HIT_DTYPE", "SEARCH_QUERY_DTYPE", "search_prepare",
     "BULGE_HIT_DTYPE", "VARIANT_HIT_DTYPE", "BULGE_VARIANT_HIT_DTYPE", "SNP_DTYPE", "vcf_snps",
+    "INDEL_DTYPE", "HAPLOTYPE_HIT_DTYPE", "Haplotypes", "vcf_indels",
 ]

@@ -121,6 +121,24 @@ class VcfCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("lines", "snps", "alleles_skipped", "no_allele", "unknown_chrom", "beyond_record")]
 
 
+class Indel(C.Structure):
+    """issl_indel: 32 bytes."""
+    _fields_ = [("pos", C.c_uint64), ("record", C.c_uint32), ("ref_len", C.c_uint32), ("alt_len", C.c_uint32), ("ref_at", C.c_uint32),
+                ("alt_at", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class VcfIndelCounts(C.Structure):
+    """issl_vcf_indel_counts: 56 bytes."""
+    _fields_ = [(n, C.c_uint64) for n in ("lines", "indels", "alleles_skipped", "no_allele", "unknown_chrom", "beyond_record", "too_long")]
+
+
+class HaplotypeHit(C.Structure):
+    """issl_haplotype_hit: 48 bytes, no padding."""
+    _fields_ = [("pos", C.c_uint64), ("site", C.c_uint32 * 4), ("record", C.c_uint32), ("query", C.c_uint32), ("mism", C.c_uint32),
+                ("strand", C.c_uint8), ("dist", C.c_uint8), ("n_var", C.c_uint8), ("reserved", C.c_uint8), ("indel", C.c_uint32),
+                ("edit_at", C.c_int32)]
+
+
 class TranscriptHitsRow(C.Structure):
     """issl_transcript_hits: 16 bytes."""
     _fields_ = [("hit", C.c_uint32), ("total", C.c_uint32), ("status", C.c_uint32), ("first", C.c_uint32)]
@@ -262,6 +280,16 @@ _protos = {
     "issl_genome_search_variants_profile_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P]),
     "issl_vcf_snps": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u64p, C.c_size_t, _P, C.c_size_t,
                                 C.POINTER(C.c_size_t), C.POINTER(VcfCounts)]),
+    "issl_vcf_indels": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u64p, C.c_size_t, _P, C.c_size_t,
+                                  C.POINTER(C.c_size_t), _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(VcfIndelCounts)]),
+    "issl_haplotypes_open": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int, C.POINTER(_P)]),
+    "issl_haplotypes_open_vcf": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(VcfIndelCounts), C.POINTER(_P)]),
+    "issl_haplotypes_info": (C.c_int, [_P, _u64p, _u64p, C.POINTER(C.c_uint32)]),
+    "issl_haplotypes_close": (C.c_int, [_P]),
+    "issl_haplotypes_search": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "issl_haplotypes_search_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "issl_haplotypes_search_profile": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P]),
+    "issl_haplotypes_search_profile_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P]),
     "issl_genome_apply_snps": (C.c_int, [_P, _P, C.c_size_t, _u64p]),
     "issl_genome_apply_vcf": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(VcfCounts), _u64p]),
     "issl_genome_occurrences": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P]),

@@ -1,6 +1,6 @@
 // bin/isslSearchGenome -- where queries bind in a genome with up to max_dist mismatches, for any PAM pattern:
 //
-//   isslSearchGenome [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R [--guide-variants N] [--guide-vcf FILE]] [--variants N] [--vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>
+//   isslSearchGenome [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R [--guide-variants N] [--guide-vcf FILE]] [--variants N] [--vcf FILE] [--indel-vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>
 //
 // pattern: 1 to 32 IUPAC codes (ACGTRYSWKMBDHVN), e.g. NNNNNNNNNNNNNNNNNNNNNGG or TTTVNNNNNNNNNNNNNNNNNNNN.  The query file has
 // one query per line over ACGTN ("\n" or "\r\n" line ends, a trailing blank line is ignored), every line of the pattern's
@@ -30,6 +30,14 @@
 // bases included; --guide-vcf applies the VCF first and prints the counts line to stderr, and alone it implies N = L.  A row
 // line is --guide's with the site in IUPAC letters: lower case where the position does not match, upper case elsewhere,
 // '-' at an RNA bulge.  --profile prints --guide's groups.  Either option without --guide is a usage error.
+// With --indel-vcf FILE the search runs on the ALT haplotypes of FILE's indels instead of the reference text
+// (issl_haplotypes_search): every ALT allele over ACGT that is no SNP, one at a time, at the windows of the pattern's length
+// that overlap its edit.  --vcf is applied first, so the bases around an edit carry its SNPs; without --variants it implies
+// --variants L.  One line of counts goes to stderr.  A row line is --variants' followed by
+//   \t<POS>:<REF>><ALT>\t<edit_at>
+// POS 1-based and REF, ALT of the edit with its common suffix and then its common prefix removed ('-' for none), edit_at the
+// window index of the first ALT base or of the first base behind a deletion (negative: the window starts inside ALT).
+// --profile lines are as without the option.  Together with --guide it is a usage error: bulges on haplotypes are not built.
 // The FASTA arguments follow bin/extractOfftargets: one input or several, a lone directory stands for its non-hidden
 // entries.  stdout carries data only, diagnostics go to stderr, exit status 1 on any error.
 //   ISSL_DEVICE=<n>       HIP device to use (default 0)
@@ -47,9 +55,12 @@
     X(issl_genome_search) X(issl_genome_search_profile) X(issl_genome_search_bulges) X(issl_genome_search_bulges_profile)             \
     X(issl_genome_search_variants) X(issl_genome_search_variants_profile) X(issl_genome_apply_vcf)                          \
     X(issl_genome_search_bulges_variants) X(issl_genome_search_bulges_variants_profile)                                     \
+    X(issl_genome_info) X(issl_vcf_indels) X(issl_haplotypes_open) X(issl_haplotypes_search) X(issl_haplotypes_search_profile)  \
+    X(issl_haplotypes_close)                                                                                              \
     X(issl_genome_close)
 #include "cli_api.hpp"
 #include "issl_bulge_variants_text.hpp"
+#include "issl_haplotypes_text.hpp"
 #include "issl_search_text.hpp"
 #include "issl_variants_text.hpp"
 
@@ -81,21 +92,22 @@ int main(int argc, char **argv)
     namespace st = issl::search_text;
     bool profile = false, usage = false;
     const char *guide = nullptr, *dna = nullptr, *rna = nullptr, *variants = nullptr, *vcf = nullptr, *guide_variants = nullptr,
-               *guide_vcf = nullptr;
+               *guide_vcf = nullptr, *indel_vcf = nullptr;
     std::vector<const char *> pos;
     for (int i = 1; i < argc; ++i) {
         const char **value = !std::strcmp(argv[i], "--guide") ? &guide : !std::strcmp(argv[i], "--dna-bulge") ? &dna
                              : !std::strcmp(argv[i], "--rna-bulge") ? &rna : !std::strcmp(argv[i], "--variants") ? &variants
                              : !std::strcmp(argv[i], "--vcf") ? &vcf : !std::strcmp(argv[i], "--guide-variants") ? &guide_variants
-                             : !std::strcmp(argv[i], "--guide-vcf") ? &guide_vcf : nullptr;
+                             : !std::strcmp(argv[i], "--guide-vcf") ? &guide_vcf : !std::strcmp(argv[i], "--indel-vcf") ? &indel_vcf
+                             : nullptr;
         if (value) {
             if (i + 1 < argc) *value = argv[++i];
             else usage = true;
         } else if (!std::strcmp(argv[i], "--profile")) profile = true;
         else pos.push_back(argv[i]);
     }
-    if (usage || pos.size() < 4 || ((dna || rna || guide_variants || guide_vcf) && !guide) || ((variants || vcf) && guide)) {
-        std::fprintf(stderr, "Usage: %s [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R [--guide-variants N] [--guide-vcf FILE]] [--variants N] [--vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>\n",
+    if (usage || pos.size() < 4 || ((dna || rna || guide_variants || guide_vcf) && !guide) || ((variants || vcf || indel_vcf) && guide)) {
+        std::fprintf(stderr, "Usage: %s [--profile] [--guide START:LEN --dna-bulge D --rna-bulge R [--guide-variants N] [--guide-vcf FILE]] [--variants N] [--vcf FILE] [--indel-vcf FILE] <pattern> <query file> <max_dist> <FASTA ...|directory>\n",
                      argv[0]);
         return 1;
     }
@@ -144,7 +156,11 @@ int main(int argc, char **argv)
         }
     }
     if (guide_vcf) vcf = guide_vcf; // (read and applied the same way)
-    std::string text, packed, vcf_text;
+    std::string text, packed, vcf_text, indel_text;
+    if (indel_vcf && !read_text_file(indel_vcf, indel_text)) {
+        std::fprintf(stderr, "cannot open '%s'\n", indel_vcf);
+        return 1;
+    }
     if (vcf && !read_text_file(vcf, vcf_text)) {
         std::fprintf(stderr, "cannot open '%s'\n", vcf);
         return 1;
@@ -185,7 +201,54 @@ int main(int argc, char **argv)
     bool ok = true;
     std::vector<uint64_t> offsets(n + 1);
     const uint32_t L = pat.length, D = static_cast<uint32_t>(max_dist);
-    if (guide && (guide_variants || guide_vcf) && profile) {
+    if (indel_vcf) {
+        // the indels against the handle's records, then their strips for windows of the pattern's length
+        uint64_t n_records = 0, n_bases = 0;
+        if (api.issl_genome_info(g, &n_records, &n_bases)) return fail("cannot read the genome's records");
+        std::vector<const char *> names(n_records);
+        std::vector<size_t> name_lens(n_records);
+        std::vector<uint64_t> lengths(n_records);
+        for (uint64_t r = 0; r < n_records; ++r)
+            if (api.issl_genome_record(g, r, &names[r], &name_lens[r], &lengths[r])) return fail("record out of range");
+        size_t n_indels = 0, n_alleles = 0;
+        issl_vcf_indel_counts ic{};
+        if (api.issl_vcf_indels(indel_text.data(), indel_text.size(), names.data(), name_lens.data(), lengths.data(), n_records, nullptr, 0,
+                                &n_indels, nullptr, 0, &n_alleles, &ic))
+            return fail("cannot read the indel VCF");
+        std::vector<issl_indel> indels(n_indels);
+        std::string alleles(n_alleles, '\0');
+        if (n_indels && api.issl_vcf_indels(indel_text.data(), indel_text.size(), names.data(), name_lens.data(), lengths.data(), n_records,
+                                            indels.data(), indels.size(), &n_indels, &alleles[0], alleles.size(), &n_alleles, &ic))
+            return fail("cannot read the indel VCF");
+        std::fprintf(stderr, "indel-vcf: lines %llu indels %llu alleles_skipped %llu no_allele %llu unknown_chrom %llu beyond_record %llu too_long %llu\n",
+                     static_cast<unsigned long long>(ic.lines), static_cast<unsigned long long>(ic.indels),
+                     static_cast<unsigned long long>(ic.alleles_skipped), static_cast<unsigned long long>(ic.no_allele),
+                     static_cast<unsigned long long>(ic.unknown_chrom), static_cast<unsigned long long>(ic.beyond_record),
+                     static_cast<unsigned long long>(ic.too_long));
+        issl_haplotypes *h = nullptr;
+        if (api.issl_haplotypes_open(g, indels.data(), indels.size(), alleles.data(), alleles.size(), static_cast<int>(L), &h))
+            return fail("cannot build the haplotypes");
+        if (profile) {
+            std::vector<uint64_t> counts(n * (D + 1));
+            if (api.issl_haplotypes_search_profile(h, &pat, queries.data(), n, static_cast<int>(D), static_cast<int>(max_variants), counts.data()))
+                return fail("search failed");
+            for (size_t k = 0; ok && k < n; ++k) {
+                st::append_profile_line(so.text, packed.data() + k * L, L, counts.data() + k * (D + 1), D);
+                ok = so.wrote();
+            }
+        } else {
+            auto search = [&](issl_haplotype_hit *hits, size_t cap, size_t *total) {
+                return api.issl_haplotypes_search(h, &pat, queries.data(), n, static_cast<int>(D), static_cast<int>(max_variants), offsets.data(),
+                                                  hits, cap, total);
+            };
+            if (!print_rows<issl_haplotype_hit>(g, so, ok, search, [&](const char *name, size_t name_len, const issl_haplotype_hit &hit) {
+                issl::haplotypes_text::append_haplotype_line(so.text, packed.data() + static_cast<size_t>(hit.query) * L, L, name, name_len, hit,
+                                                             indels[hit.indel], alleles.data());
+                }))
+                return 1;
+        }
+        api.issl_haplotypes_close(h);
+    } else if (guide && (guide_variants || guide_vcf) && profile) {
         const uint32_t bins = (bg.max_rna + bg.max_dna + 1) * (D + 1);
         std::vector<uint64_t> counts(n * bins);
         if (api.issl_genome_search_bulges_variants_profile(g, &pat, &bg, queries.data(), n, static_cast<int>(D), static_cast<int>(max_variants),

@@ -237,20 +237,32 @@ inline uint8_t allele_bit(const char *p, size_t len)
     return c < 4 ? static_cast<uint8_t>(1u << c) : 0;
 }
 
-// The entries and counts of a VCF's text; the rules are in include/issl_hip.h.  false + message (a malformed line, named).
-inline bool read_vcf(const char *vcf, size_t len, const char *const *names, const size_t *name_lens, const uint64_t *lengths,
-                     size_t n_records, std::vector<issl_snp> &found, issl_vcf_counts &c, std::string &err)
+// A record's name up to its first blank -> its number (the first record of a name keeps it): what CHROM is looked up in.
+using RecordNames = std::unordered_map<std::string, uint32_t>;
+inline RecordNames record_names(const char *const *names, const size_t *name_lens, size_t n_records)
 {
-    std::unordered_map<std::string, uint32_t> by_name;
+    RecordNames by_name;
     for (size_t r = 0; r < n_records; ++r) {
         size_t e = 0;
         while (e < name_lens[r] && !is_blank(names[r][e])) ++e;
-        by_name.emplace(std::string(names[r], e), static_cast<uint32_t>(r)); // (the first record of a name keeps it)
+        by_name.emplace(std::string(names[r], e), static_cast<uint32_t>(r));
     }
-    c = issl_vcf_counts{};
-    found.clear();
-    size_t line_no = 0;
-    for (size_t p = 0; p < len;) {
+    return by_name;
+}
+
+// One data line of a VCF: where its first five fields lie in the text, and POS (huge: it does not fit 64 bits).
+struct VcfLine {
+    size_t f_at[5], f_len[5];
+    uint64_t pos;
+    bool huge;
+};
+
+// The line splitter of the VCF readers (read_vcf here, read_vcf_indels of issl_haplotypes_text.hpp): the next data line from
+// p on, empty lines and '#' lines skipped, p and line_no moved behind it.  1: a line; 0: the text's end; -1 + message: a
+// malformed line, named.
+inline int next_vcf_line(const char *vcf, size_t len, size_t &p, size_t &line_no, VcfLine &out, std::string &err)
+{
+    while (p < len) {
         const char *nl = static_cast<const char *>(std::memchr(vcf + p, '\n', len - p));
         size_t e = nl ? static_cast<size_t>(nl - vcf) : len;
         const size_t next = nl ? e + 1 : len;
@@ -259,41 +271,70 @@ inline bool read_vcf(const char *vcf, size_t len, const char *const *names, cons
         p = next;
         ++line_no;
         if (e == from || vcf[from] == '#') continue;
-        size_t f_at[5], f_len[5], fields = 0;
+        size_t fields = 0;
         for (size_t q = from; fields < 5;) {
             const char *tab = static_cast<const char *>(std::memchr(vcf + q, '\t', e - q));
             const size_t fe = tab ? static_cast<size_t>(tab - vcf) : e;
-            f_at[fields] = q;
-            f_len[fields++] = fe - q;
+            out.f_at[fields] = q;
+            out.f_len[fields++] = fe - q;
             if (!tab) break;
             q = fe + 1;
         }
         if (fields < 5) {
             err = "VCF line " + std::to_string(line_no) + ": fewer than five tab-separated fields";
-            return false;
+            return -1;
         }
-        uint64_t pos = 0;
-        bool numeric = f_len[1] > 0, huge = false;
-        for (size_t i = 0; i < f_len[1] && numeric; ++i) {
-            const char d = vcf[f_at[1] + i];
+        out.pos = 0;
+        out.huge = false;
+        bool numeric = out.f_len[1] > 0;
+        for (size_t i = 0; i < out.f_len[1] && numeric; ++i) {
+            const char d = vcf[out.f_at[1] + i];
             if (d < '0' || d > '9') numeric = false;
-            else if (pos > (0xFFFFFFFFFFFFFFFFull - 9) / 10) huge = true;
-            else pos = pos * 10 + static_cast<uint64_t>(d - '0');
+            else if (out.pos > (0xFFFFFFFFFFFFFFFFull - 9) / 10) out.huge = true;
+            else out.pos = out.pos * 10 + static_cast<uint64_t>(d - '0');
         }
         if (!numeric) {
             err = "VCF line " + std::to_string(line_no) + ": POS is not a number";
-            return false;
+            return -1;
         }
-        ++c.lines;
-        const auto rec = by_name.find(std::string(vcf + f_at[0], f_len[0]));
-        if (rec == by_name.end()) {
-            ++c.unknown_chrom;
-            continue;
-        }
-        if (huge || pos == 0 || pos > lengths[rec->second]) {
-            ++c.beyond_record;
-            continue;
-        }
+        return 1;
+    }
+    return 0;
+}
+
+// The record a data line names, counted in c (lines, unknown_chrom, beyond_record: the fields both readers' counts have).
+// false: the line is skipped.
+template <class Counts>
+inline bool vcf_line_record(const char *vcf, const VcfLine &l, const RecordNames &by_name, const uint64_t *lengths, Counts &c, uint32_t &record)
+{
+    ++c.lines;
+    const auto rec = by_name.find(std::string(vcf + l.f_at[0], l.f_len[0]));
+    if (rec == by_name.end()) {
+        ++c.unknown_chrom;
+        return false;
+    }
+    if (l.huge || l.pos == 0 || l.pos > lengths[rec->second]) {
+        ++c.beyond_record;
+        return false;
+    }
+    record = rec->second;
+    return true;
+}
+
+// The entries and counts of a VCF's text; the rules are in include/issl_hip.h.  false + message (a malformed line, named).
+inline bool read_vcf(const char *vcf, size_t len, const char *const *names, const size_t *name_lens, const uint64_t *lengths,
+                     size_t n_records, std::vector<issl_snp> &found, issl_vcf_counts &c, std::string &err)
+{
+    const RecordNames by_name = record_names(names, name_lens, n_records);
+    c = issl_vcf_counts{};
+    found.clear();
+    size_t line_no = 0, p = 0;
+    VcfLine l;
+    for (int got; (got = next_vcf_line(vcf, len, p, line_no, l, err)) != 0;) {
+        if (got < 0) return false;
+        uint32_t record = 0;
+        if (!vcf_line_record(vcf, l, by_name, lengths, c, record)) continue;
+        const size_t *f_at = l.f_at, *f_len = l.f_len;
         const uint8_t ref = allele_bit(vcf + f_at[3], f_len[3]);
         uint8_t alt = 0;
         for (size_t q = f_at[4], end = f_at[4] + f_len[4];;) {
@@ -310,8 +351,8 @@ inline bool read_vcf(const char *vcf, size_t len, const char *const *names, cons
             continue;
         }
         issl_snp s{};
-        s.pos = pos - 1;
-        s.record = rec->second;
+        s.pos = l.pos - 1;
+        s.record = record;
         s.ref = ref;
         s.alt = alt;
         found.push_back(s);

@@ -25,6 +25,11 @@ SEARCH_HIT_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"),
 VARIANT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("site", "<u4", (4,)), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
                               ("strand", "u1"), ("dist", "u1"), ("n_var", "u1"), ("reserved", "u1")])  # issl_variant_hit (40 bytes)
 SNP_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("ref", "u1"), ("alt", "u1"), ("reserved", "u1", (2,))])  # issl_snp (16 bytes)
+INDEL_DTYPE = np.dtype([("pos", "<u8"), ("record", "<u4"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("ref_at", "<u4"), ("alt_at", "<u4"),
+                        ("reserved", "<u4")])  # issl_indel (32 bytes)
+HAPLOTYPE_HIT_DTYPE = np.dtype([("pos", "<u8"), ("site", "<u4", (4,)), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
+                                ("strand", "u1"), ("dist", "u1"), ("n_var", "u1"), ("reserved", "u1"), ("indel", "<u4"),
+                                ("edit_at", "<i4")])  # issl_haplotype_hit (48 bytes)
 BULGE_VARIANT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("site", "<u4", (4,)), ("record", "<u4"), ("query", "<u4"), ("mism", "<u4"),
                                     ("strand", "u1"), ("dist", "u1"), ("n_var", "u1"), ("bulge", "i1"), ("at", "u1"),
                                     ("reserved", "u1", (7,))])  # issl_bulge_variant_hit (48 bytes)
@@ -45,6 +50,7 @@ LANDING_DTYPE = np.dtype([("site", "<u8"), ("pos", "<u8"), ("record", "<u4"), ("
 LANDING_PROFILE_DTYPE = np.dtype([("located", "<u8", (_lib.PROFILE_BINS,)), ("in_exon", "<u8", (_lib.PROFILE_BINS,)),
                                   ("absent", "<u4", (_lib.PROFILE_BINS,)), ("pad", "<u4")])
 assert LANDING_DTYPE.itemsize == 64 and LANDING_PROFILE_DTYPE.itemsize == 144
+assert INDEL_DTYPE.itemsize == 32 and HAPLOTYPE_HIT_DTYPE.itemsize == 48
 
 
 def _method_code(method):
@@ -519,6 +525,29 @@ def vcf_snps(vcf, records):
     return out, {name: int(getattr(counts, name)) for name, _ in counts._fields_}
 
 
+def vcf_indels(vcf, records):
+    """issl_vcf_indels: the indels of a VCF's text (bytes; plain text, no gzip) -- every ALT allele over ACGT that differs
+    from REF and is no SNP: deletions, insertions, multi-base substitutions, complex alleles -- for records = [(name,
+    length), ...] as Genome.records lists them.  -> (an INDEL_DTYPE array, one entry per allele in file order; the allele
+    text as bytes, REF then ALT of every entry, which ref_at / alt_at index; a dict of counts: lines, indels,
+    alleles_skipped, no_allele, unknown_chrom, beyond_record, too_long).  No device needed.  A malformed line raises
+    IsslError naming it."""
+    vcf = bytes(vcf)
+    names = [n.encode() if isinstance(n, str) else bytes(n) for n, _ in records]
+    k = len(names)
+    c_names = (C.c_char_p * max(k, 1))(*names)
+    c_lens = (C.c_size_t * max(k, 1))(*[len(n) for n in names])
+    c_lengths = (C.c_uint64 * max(k, 1))(*[int(length) for _, length in records])
+    n, n_bytes, counts = C.c_size_t(), C.c_size_t(), _lib.VcfIndelCounts()
+    args = (vcf, len(vcf), c_names, c_lens, c_lengths, k)
+    check(lib.issl_vcf_indels(*args, None, 0, C.byref(n), None, 0, C.byref(n_bytes), C.byref(counts)))
+    out = np.zeros(n.value, dtype=INDEL_DTYPE)
+    alleles = C.create_string_buffer(max(n_bytes.value, 1))
+    if n.value:
+        check(lib.issl_vcf_indels(*args, out.ctypes.data, n.value, C.byref(n), alleles, n_bytes.value, C.byref(n_bytes), C.byref(counts)))
+    return out, alleles.raw[:n_bytes.value], {name: int(getattr(counts, name)) for name, _ in counts._fields_}
+
+
 def _search_pattern(pattern):
     return pattern if isinstance(pattern, _lib.SearchPattern) else search_prepare(pattern, [])[0]
 
@@ -781,6 +810,30 @@ class Genome:
         out["changed"] = changed.value
         return out
 
+    def haplotypes(self, indels, alleles, window):
+        """The ALT haplotypes of indels as a second resident text (issl_haplotypes_open of include/issl_hip.h): indels is an
+        INDEL_DTYPE array (record, 0-based pos, ref_len, alt_len, and where the bases start in `alleles`, bytes over ACGT in
+        either case), window the one pattern length (1..32) the handle serves.  Every REF is checked against the resident
+        text, where a SNP applied earlier is fine; a REF the text does not hold raises IsslError naming the smallest such
+        entry.  -> Haplotypes, a snapshot: SNPs applied to this genome later do not reach it."""
+        indels = np.ascontiguousarray(indels, dtype=INDEL_DTYPE)
+        alleles = bytes(alleles)
+        h = C.c_void_p()
+        check(lib.issl_haplotypes_open(self._h, indels.ctypes.data if len(indels) else None, len(indels), alleles if alleles else None,
+                                       len(alleles), int(window), C.byref(h)))
+        return Haplotypes(h)
+
+    def haplotypes_vcf(self, vcf, window):
+        """haplotypes() for the indels of a VCF (bytes, or a path to a plain-text file).  -> (Haplotypes, the counts of
+        vcf_indels())."""
+        if not isinstance(vcf, (bytes, bytearray, memoryview)):
+            with open(vcf, "rb") as fh:
+                vcf = fh.read()
+        vcf = bytes(vcf)
+        h, counts = C.c_void_p(), _lib.VcfIndelCounts()
+        check(lib.issl_haplotypes_open_vcf(self._h, vcf, len(vcf), int(window), C.byref(counts), C.byref(h)))
+        return Haplotypes(h), {name: int(getattr(counts, name)) for name, _ in counts._fields_}
+
     def occurrences(self, sites, page_length=0, page_starts=None):
         """The Bowtie step (Crackling.py:600-725) as exact counts.  sites: 20-mer strings or a uint64 array of packed
         signatures, duplicates allowed; page_length: the reference's [bowtie2] page-length (0: one page).  -> structured
@@ -836,6 +889,67 @@ class Genome:
     def close(self):
         if self._h:
             lib.issl_genome_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Haplotypes:
+    """The ALT haplotypes of a set of indels, resident on the GPU as strips of text (issl_haplotypes_* of
+    include/issl_hip.h; Genome.haplotypes makes it).  The searches are Genome.search_variants* on the ALT haplotype of one
+    indel at a time, at the windows that overlap its edit; rows are in HAPLOTYPE_HIT_DTYPE: the variant search's fields,
+    `indel` the input index, `record` and `pos` in reference coordinates, `edit_at` the window index of the first ALT base
+    (or of the first base behind a deletion's junction; negative when the window starts inside the ALT allele).  Nothing
+    is filtered, two indels are never combined, and there are no bulges: the strips serve one window length."""
+
+    _search_rows = Genome._search_rows
+    _search_counts = Genome._search_counts
+    _search_rows_device = Genome._search_rows_device
+    _search_counts_device = Genome._search_counts_device
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def info(self):
+        """-> {"n_indels", "text_bytes" (of the strip text, separators included), "window"}."""
+        n, text, window = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        check(lib.issl_haplotypes_info(self._h, C.byref(n), C.byref(text), C.byref(window)))
+        return {"n_indels": n.value, "text_bytes": text.value, "window": window.value}
+
+    def search(self, pattern, queries, max_dist=4, max_variants=2):
+        """-> (offsets uint64[n + 1], hits in HAPLOTYPE_HIT_DTYPE): query k owns hits[offsets[k]:offsets[k + 1]], sorted by
+        (indel, offset of the window in its strip, strand).  The pattern's length must be the handle's window."""
+        return self._search_rows(lib.issl_haplotypes_search, HAPLOTYPE_HIT_DTYPE, pattern, (), queries, max_dist, (int(max_variants),))
+
+    def search_profile(self, pattern, queries, max_dist=4, max_variants=2):
+        """-> uint64 array [n, max_dist + 1]: the rows of search() of query k at distance d, counted on the device."""
+        return self._search_counts(lib.issl_haplotypes_search_profile, pattern, (), queries, max_dist, (int(max_dist) + 1,),
+                                   (int(max_variants),))
+
+    def search_device(self, pattern, d_queries, d_offsets, d_hits, max_dist=4, max_variants=2, stream=None):
+        """Genome.search_device() for search(): d_hits is a uint8 CUDA tensor (48 bytes per row, HAPLOTYPE_HIT_DTYPE) or None
+        for the counting call.  -> the number of rows; nothing is written when they do not fit d_hits."""
+        return self._search_rows_device(lib.issl_haplotypes_search_device, HAPLOTYPE_HIT_DTYPE, pattern, (), d_queries, max_dist,
+                                        d_offsets, d_hits, stream, (int(max_variants),))
+
+    def search_profile_device(self, pattern, d_queries, d_counts, max_dist=4, max_variants=2, stream=None):
+        """d_counts: int64 CUDA tensor of n * (max_dist + 1) words.  Returns when they are written."""
+        self._search_counts_device(lib.issl_haplotypes_search_profile_device, pattern, (), d_queries, max_dist, d_counts,
+                                   int(max_dist) + 1, "n * (max_dist + 1)", stream, (int(max_variants),))
+
+    def close(self):
+        if self._h:
+            lib.issl_haplotypes_close(self._h)
             self._h = None
 
     def __enter__(self):

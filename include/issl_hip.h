@@ -744,6 +744,90 @@ int issl_genome_search_bulges_variants_profile_device(issl_genome *g, const issl
                                                       const issl_search_query *d_queries, size_t n, int max_dist, int max_variants,
                                                       uint64_t *d_counts, void *stream);
 
+/* ---- the ALT haplotypes of indels ------------------------------------------------------------------------------------------ */
+/* An insertion or a deletion moves a PAM against a protospacer: it creates and destroys off-targets that no substitution can,
+ * and issl_vcf_snps skips every such allele.  Here the ALT haplotype of an indel is searched as TEXT: for one window length W
+ * an indel becomes a STRIP -- the W - 1 bases ahead of the edit, the ALT allele, the W - 1 bases behind it, cut from the
+ * resident text as it stands (with the ambiguity codes applied SNPs left there) -- and the strips, one per indel, are the
+ * records of a second resident text that issl_genome_search_variants searches as it is.  A strip holds exactly the windows of
+ * the ALT haplotype that overlap the edit, and none that the reference text shows at those coordinates.
+ *
+ * An issl_indel replaces ref_len >= 1 bases at (record, 0-based pos) by alt_len >= 1 bases, as a VCF line gives them with
+ * the anchor base: deletions, insertions, multi-base substitutions and complex alleles are this one thing.  Its bases are
+ * alleles[ref_at .. ref_at + ref_len) and alleles[alt_at .. alt_at + alt_len), a caller-owned buffer over ACGT in either
+ * case (upper-cased on the way in); each length is at most ISSL_INDEL_MAX_ALLELE.
+ *   trim      the common suffix of REF and ALT is removed first, then the common prefix of what is left: (p, REF', ALT') with
+ *             p = pos + the prefix removed.  One of REF', ALT' is non-empty: an entry that changes nothing is refused
+ *             (ISSL_E_ARG).  Nothing is re-aligned against the genome
+ *
+ * issl_vcf_indels reads them from a VCF's text.  Host only.  Lines, fields, CHROM, the two malformed-line errors,
+ * unknown_chrom and beyond_record (POS) are issl_vcf_snps's.  Then, in this order: a REF that is empty or not all ACGT --
+ * every ALT allele of the line is counted in alleles_skipped and the line in no_allele; a REF that runs past the record's
+ * end -- beyond_record; then per ALT allele, left to right, the allele is taken when it is one or more bases of ACGT, differs
+ * from REF ignoring case, and REF and ALT are not both one base long (a SNP: issl_vcf_snps's share).  A taken allele whose REF
+ * or ALT is longer than ISSL_INDEL_MAX_ALLELE is counted in too_long instead; every other allele in alleles_skipped; a line
+ * that gave nothing in no_allele.  out receives one issl_indel per taken allele in file order, and its REF bytes, then its ALT
+ * bytes, as they stand in the file, are appended to `alleles`.  *n and *alleles_len are always complete; nothing is written
+ * to either buffer when one of them exceeds its capacity (NULL with capacity 0 is the counting call).  counts may be NULL.
+ *
+ * issl_haplotypes_open builds the strips for ONE window length `window` (1..32, never guessed) on g's device.  The host
+ * checks every entry (ISSL_E_ARG, the message names it): record in range, pos + ref_len within the record, the lengths
+ * 1..ISSL_INDEL_MAX_ALLELE, the offsets inside `alleles`, every byte one of ACGT, not a no-op.  With
+ *   left = min(window - 1, p),  right = min(window - 1, length - p - |REF'|)
+ * strip k is the `left` text bytes ahead of p, ALT', the `right` text bytes from p + |REF'| on, and a separator; strips lie in
+ * input order.  On the device every base of the UNTRIMMED REF must lie in the set of its text byte (so a SNP applied there
+ * earlier is fine); if any entry fails the call returns ISSL_E_ARG, the message names the smallest failing input index, and
+ * no handle is made.  Then the strips are gathered.  THE STRIPS ARE A SNAPSHOT: SNPs applied to g after the open do not
+ * reach them, and g may be closed before h.  n == 0 gives a handle without strips.  A strip text of 2^41 bytes or more, or
+ * more than 2^32 - 1 entries: ISSL_E_UNSUPPORTED.  Memory: about 2 * window + |ALT'| + 33 bytes per indel (text, an 8-byte
+ * start and a 32-byte table entry), plus 40 bytes per row of scratch during a search call.
+ * issl_haplotypes_open_vcf chains issl_vcf_indels and issl_haplotypes_open with the handle's own records.
+ *
+ * issl_haplotypes_search* have the signatures of issl_genome_search_variants* with h in the place of g.
+ * pat->length != window: ISSL_E_ARG before any device work.
+ *   hit       a hit of issl_genome_search_variants on the ALT haplotype of ONE indel, taken alone on the text as it stood at
+ *             the open, at a window that overlaps the edit: with ALT' non-empty the window holds at least one base of ALT';
+ *             with ALT' empty it holds both the base ahead of the junction and the base behind it
+ *   row       issl_haplotype_hit.  site, mism, dist, n_var, strand, query: the variant search's.  indel: the input index;
+ *             record: the reference record.  With s the window's start in its strip, edit_at = left - s: the window index
+ *             of the first ALT' base, or of the first base behind a deletion's junction; negative when the window starts
+ *             inside ALT'.  pos is the reference position of the window's first base: p - left + s for s < left; p for
+ *             left <= s < left + |ALT'|; p + |REF'| + (s - left - |ALT'|) behind that.  reserved = 0
+ *   NO FILTERING: in a repeat such a window can spell what the reference text spells too; it is listed.  ONE INDEL AT A
+ *             TIME: two indels closer than a window are never combined, and an indel given twice gives its rows twice.
+ *             No bulges: the strips serve one window length
+ *   order     query k owns hits[offsets[k] .. offsets[k + 1]), sorted by (indel, s, strand)
+ *   profile   counts[k * (max_dist + 1) + d], the variant profile of the strips
+ * Everything else is the variant search's rule: the capacity rule, *n_total, n == 0, duplicated queries, pieces, the
+ * argument errors, max_variants. */
+#define ISSL_INDEL_MAX_ALLELE 65535
+typedef struct { uint64_t pos;        /* 0-based inside the record, of the first REF base */
+                 uint32_t record, ref_len, alt_len;
+                 uint32_t ref_at, alt_at;   /* where the REF / ALT bases start in the allele text */
+                 uint32_t reserved; } issl_indel;                          /* 32 B */
+typedef struct { uint64_t lines, indels, alleles_skipped, no_allele, unknown_chrom, beyond_record, too_long; } issl_vcf_indel_counts; /* 56 B */
+typedef struct { uint64_t pos; uint32_t site[4]; uint32_t record; uint32_t query; uint32_t mism;
+                 uint8_t strand, dist, n_var, reserved; uint32_t indel; int32_t edit_at; } issl_haplotype_hit; /* 48 B, no padding */
+typedef struct issl_haplotypes issl_haplotypes; /* opaque; owns device memory */
+int issl_vcf_indels(const char *vcf, size_t len, const char *const *names, const size_t *name_lens, const uint64_t *lengths,
+                    size_t n_records, issl_indel *out, size_t cap, size_t *n, char *alleles, size_t alleles_cap, size_t *alleles_len,
+                    issl_vcf_indel_counts *counts);
+int issl_haplotypes_open(issl_genome *g, const issl_indel *indels, size_t n, const char *alleles, size_t alleles_len, int window,
+                         issl_haplotypes **out);
+int issl_haplotypes_open_vcf(issl_genome *g, const char *vcf, size_t len, int window, issl_vcf_indel_counts *counts,
+                             issl_haplotypes **out);
+int issl_haplotypes_info(const issl_haplotypes *h, uint64_t *n_indels, uint64_t *text_bytes, uint32_t *window);
+int issl_haplotypes_close(issl_haplotypes *h);
+int issl_haplotypes_search(issl_haplotypes *h, const issl_search_pattern *pat, const issl_search_query *queries, size_t n, int max_dist,
+                           int max_variants, uint64_t *offsets, issl_haplotype_hit *hits, size_t cap, size_t *n_total);
+int issl_haplotypes_search_device(issl_haplotypes *h, const issl_search_pattern *pat, const issl_search_query *d_queries, size_t n,
+                                  int max_dist, int max_variants, uint64_t *d_offsets, issl_haplotype_hit *d_hits, size_t cap,
+                                  size_t *n_total, void *stream);
+int issl_haplotypes_search_profile(issl_haplotypes *h, const issl_search_pattern *pat, const issl_search_query *queries, size_t n,
+                                   int max_dist, int max_variants, uint64_t *counts /* n * (max_dist + 1) */);
+int issl_haplotypes_search_profile_device(issl_haplotypes *h, const issl_search_pattern *pat, const issl_search_query *d_queries,
+                                          size_t n, int max_dist, int max_variants, uint64_t *d_counts, void *stream);
+
 /* ---- the Bowtie step: exact occurrences of a guide's eight reads ----------------------------------------------------- */
 /* Counterpart of src/crackling/Crackling.py:600-725 on a genome handle.  For every guide the reference aligns eight reads,
  * the guide's 20-mer followed by AGG, CGG, GGG, TGG, AAG, CAG, GAG, TAG (variants 0..7), and counts the reads that align

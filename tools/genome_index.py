@@ -35,7 +35,15 @@ k_scan -- for the largest.  With --search-bulges V ... the largest query set is 
 span (0, 20), D = R = V) and, as the yardstick, through the variant expansion: every alignment (b, i) as a derived
 (pattern, query) set, each a full Genome.search (74 sets at V = 2).  Both on the same handle without timing, alternating
 after one warm-up each; stage times, rows, windows and comparisons per second of the count pass come from one more call
-on the timed handle, --bulge-valu is read off tools/isa_stats.py k_bulge."""
+on the timed handle, --bulge-valu is read off tools/isa_stats.py k_bulge.
+
+--haplotypes: instead of the chain, the genome is opened under ISSL_LOCATE_TIMING=1, the seeded SNPs of
+tools/bench_variants.py (one base in 300) are applied, and --haplotype-indels seeded indels (default 100 000: deletions
+and insertions of 1 to 10 bases behind an anchor, spread over the records) become a crackling_amd.Haplotypes for windows
+of 23: the device times of the open (check, upload, build).  Then the largest of --search-queries (guide + NNN,
+NNNNNNNNNNNNNNNNNNNNNGG, max_dist 4, max_variants 2) is searched on the strips and, in the same run, with
+Genome.search_variants on the reference text: stage times and counters of both filling calls, and the figure to read --
+device time per admitted window-strand on the strips over the same quotient on the reference text."""
 import argparse
 import filecmp
 import json
@@ -274,6 +282,81 @@ def bulge_leg(ca, fa, timed, pattern, max_dist, prepared, limits, valu_per_compa
     return res
 
 
+def haplotypes_leg(fa, n_indels, n_queries, seed, window=23, max_variants=2):
+    import crackling_amd as ca
+    sys.path.insert(0, str(ROOT / "tools"))
+    import bench_variants as bv
+    pattern, max_dist = "N" * 21 + "GG", 4
+    os.environ["ISSL_LOCATE_TIMING"] = "1"   # read when a handle is made
+    timed = ca.Genome.open([str(fa)])
+    recs = [b"".join(r.split(b"\n")[1:]) for r in pathlib.Path(fa).read_bytes().split(b">")[1:]]  # as sample_sites reads them
+    snps = bv.seeded_snps(ca, timed, 300, seed, lambda r: np.frombuffer(recs[r], dtype=np.uint8))
+    changed = timed.apply_snps(snps)
+    # the indels: REF as the reference has it (a code an applied SNP left there holds it), half deletions, half insertions
+    rng = np.random.default_rng(seed + 1)
+    indels = np.zeros(n_indels, dtype=ca.INDEL_DTYPE)
+    alleles, at = [], 0
+    per = -(-n_indels // len(recs))
+    k = 0
+    for r, rec in enumerate(recs):
+        for pos in np.sort(rng.choice(len(rec) - 16, size=min(per, n_indels - k), replace=False)):
+            pos, size = int(pos), int(rng.integers(1, 11))
+            if k % 2:
+                ref, alt = rec[pos:pos + 1 + size], rec[pos:pos + 1]
+            else:
+                ref, alt = rec[pos:pos + 1], rec[pos:pos + 1] + bytes(b"ACGT"[i] for i in rng.integers(0, 4, size=size))
+            indels[k] = (pos, r, len(ref), len(alt), at, at + len(ref), 0)
+            alleles.append(ref + alt)
+            at += len(ref) + len(alt)
+            k += 1
+    alleles = b"".join(alleles)
+    sites = sample_sites(fa, n_queries, seed + n_queries)
+    text = np.frombuffer(b"ACGT", dtype=np.uint8)[((sites[:, None] >> (2 * np.arange(20, dtype=np.uint64))) & np.uint64(3)).astype(np.int64)]
+    pat, q = ca.search_prepare(pattern, [bytes(row) + b"NNN" for row in text])
+
+    def stages_of(err, tag):
+        lines = [ln for ln in err.splitlines() if ln.startswith(tag)]
+        fill = lines[len(lines) // 2:]   # the filling call's lines (the counting call's come first)
+        stages = {m.group(1): float(m.group(2)) for ln in fill for m in re.finditer(r" (\w+) ([0-9.]+) ms", ln)}
+        ctr = {m.group(1): int(m.group(2)) for ln in fill for m in re.finditer(r"(windows|admitted|hits) (\d+)", ln)}
+        return {"filling_call_stages_ms": stages, "device_ms_filling_call": sum(stages.values()), "scan_counters": ctr}
+
+    stderr_of(lambda: timed.haplotypes(indels[:64], alleles, window).close())  # code objects
+    t = time.perf_counter()
+    h, err = stderr_of(lambda: timed.haplotypes(indels, alleles, window))
+    open_wall = time.perf_counter() - t
+    os.environ.pop("ISSL_LOCATE_TIMING")
+    line = [ln for ln in err.splitlines() if ln.startswith("[issl haplotypes]")][-1]
+    open_stages = {m.group(1): float(m.group(2)) for m in re.finditer(r" (\w+) ([0-9.]+) ms", line)}
+    stderr_of(lambda: (h.search(pat, q[:8], max_dist, max_variants), timed.search_variants(pat, q[:8], max_dist, max_variants)))
+    t = time.perf_counter()
+    (_, rows), err = stderr_of(lambda: h.search(pat, q, max_dist, max_variants))
+    strips_wall = time.perf_counter() - t
+    strips = stages_of(err, "[issl variants]")
+    strips["map_ms"] = [float(m.group(1)) for m in re.finditer(r"\[issl haplotypes\] map ([0-9.]+) ms", err)][-1] if len(rows) else 0.0
+    t = time.perf_counter()
+    (_, ref_rows), err = stderr_of(lambda: timed.search_variants(pat, q, max_dist, max_variants))
+    ref_wall = time.perf_counter() - t
+    ref = stages_of(err, "[issl variants]")
+    info = h.info()
+    h.close()
+    timed.close()
+
+    def per_admitted(leg, stage=None):
+        ms = leg["filling_call_stages_ms"][stage] if stage else leg["device_ms_filling_call"]
+        return ms * 1e6 / max(leg["scan_counters"]["admitted"], 1)   # ns
+
+    return {"pattern": pattern, "max_dist": max_dist, "max_variants": max_variants, "window": window, "queries": int(len(q)),
+            "n_bases": timed.n_bases, "records": len(recs), "snps_applied": int(changed), "indels": int(n_indels),
+            "strip_text_bytes": info["text_bytes"], "open_wall_ms": open_wall * 1e3, "open_device_stages_ms": open_stages,
+            "strips": dict(strips, rows=int(len(rows)), wall_ms_counting_and_filling_call=strips_wall * 1e3),
+            "reference_text": dict(ref, rows=int(len(ref_rows)), wall_ms_counting_and_filling_call=ref_wall * 1e3),
+            "ns_per_admitted_window_strand": {"strips_count_stage": per_admitted(strips, "count"), "reference_count_stage": per_admitted(ref, "count"),
+                                              "strips_device": per_admitted(strips), "reference_device": per_admitted(ref)},
+            "strips_over_reference_per_admitted_window_strand": {"count_stage": per_admitted(strips, "count") / per_admitted(ref, "count"),
+                                                                 "device": per_admitted(strips) / per_admitted(ref)}}
+
+
 def guides_leg(fa, torch):
     import crackling_amd as ca
     ca.GuideSet.extract([b">w\n" + b"ACGTTGCAGGTACCAGTAGGCAGG" * 100 + b"\n"]).close()   # code objects
@@ -296,7 +379,7 @@ def guides_leg(fa, torch):
             "hbm_high_water_per_match": hbm.peak / max(n_matches, 1), "resident_bytes_of_the_set": resident}
 
 
-def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, locate_sites=None, guides=False, search=None):
+def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, locate_sites=None, guides=False, search=None, haplotypes=None):
     import torch
     import crackling_amd as ca
     fa = work / f"genome_{kind}_{mbp:g}.fa"
@@ -304,6 +387,10 @@ def run(mbp, kind, seed, width, work, chain_max_mbp, write_max_mbp, timeout, loc
     fa_bytes = genome(fa, mbp, kind, seed)
     res = {"genome_mbp": mbp, "kind": kind, "seed": seed, "slice_width": width, "fasta_bytes": fa_bytes,
            "generate_s": time.perf_counter() - t}
+    if haplotypes:   # (no index is built: the handle's text is all this leg reads)
+        res["haplotypes"] = haplotypes_leg(fa, haplotypes[0], haplotypes[1], seed)
+        fa.unlink()
+        return res
     os.environ["ISSL_UPLOAD_TIMING"] = "1"   # read when the call starts (Tuning::from_env)
     with HbmWatch(torch) as hbm:
         t = time.perf_counter()
@@ -380,6 +467,9 @@ def main():
     ap.add_argument("--search-bulges", type=int, nargs="*", default=[], help="with --search: also Genome.search_bulges at D = R = each of these "
                     "limits for the largest query count, against the variant expansion through Genome.search")
     ap.add_argument("--bulge-valu", type=float, default=12.75, help="wave64 VALU instructions per 64 comparisons in k_bulge's compare loop")
+    ap.add_argument("--haplotypes", action="store_true", help="the ALT haplotypes of seeded indels: the open's device times, and the search on the "
+                    "strips beside the variant search on the reference text, instead of running the chain")
+    ap.add_argument("--haplotype-indels", type=int, default=100000)
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -391,9 +481,10 @@ def main():
     results = []
     with tempfile.TemporaryDirectory(dir=a.workdir) as tmp:
         for mbp in a.mbp:
-            no_chain = a.locate or a.guides or a.search
+            no_chain = a.locate or a.guides or a.search or a.haplotypes
             r = run(mbp, a.kind, a.seed, a.width, pathlib.Path(tmp), 0.0 if no_chain else a.chain_max_mbp, 0.0 if no_chain else a.write_max_mbp, a.timeout,
-                    a.locate_sites if a.locate else None, a.guides, (a.search_queries, a.search_valu, (a.search_bulges, a.bulge_valu) if a.search_bulges else None) if a.search else None)
+                    a.locate_sites if a.locate else None, a.guides, (a.search_queries, a.search_valu, (a.search_bulges, a.bulge_valu) if a.search_bulges else None) if a.search else None,
+                    (a.haplotype_indels, max(a.search_queries)) if a.haplotypes else None)
             print(json.dumps(r), flush=True)
             results.append(r)
     if a.out:
