@@ -1,9 +1,10 @@
 // Genome search with DNA and RNA bulges beside the mismatches (issl_genome_search_bulges*, include/issl_hip.h): where a
-// query binds when up to D bases of the site, or up to R bases of the query, pair with nothing.  The protocol is that of
-// issl_search_core.hpp, its host side SearchDriver<BulgeSearch> (issl_search_device.hpp); a piece has up to 2^19 queries.
-// This unit's own:
-//   count    k_bulge<kCount>, one launch per bulge b = -R..D (at most seven) with the SearchArgs of that b's pattern P':
-//            the windows have L + b bases.  A lane holds one survivor's packed word t and the same word shifted by b
+// query binds when up to D bases of the site, or up to R bases of the query, pair with nothing.  The second unit of
+// SearchDriver (issl_search_device.hpp) with the protocol and the device pieces of issl_search_core.hpp.  Tile, pattern
+// test and survivor queue are k_search's text for windows of L + b bases (the core header says why they are no
+// function).  A piece has up to 2^19 queries.  This unit's own:
+//   count    k_bulge<kCount>, one launch per bulge b = -R..D (at most seven) with the SearchArgs of that b's pattern P'.
+//            A lane holds one survivor's packed word t and the same word shifted by b
 //            (a DNA bulge; for an RNA bulge the wave-uniform query is shifted instead: k_bulge<, kRna>); against the query
 //            it forms A & B, the positions that differ at both shifts, whose count is a lower bound of the distance at
 //            every break point (bulge_both, issl_search_text.hpp).  On random text the bound of a 20-mer lies near 11,
@@ -150,17 +151,7 @@ __global__ __launch_bounds__(256) void k_bulge(const uint8_t *__restrict__ s, ui
         for (; qi < mine_q.hi; ++qi) walk(q[qi], qi);
         if (kMode == kCount && valid) found += mine;
     }
-    if (kMode == kCount) {
-        for (int d = 32; d > 0; d >>= 1) {
-            windows += __shfl_down(windows, d, 64);
-            found += __shfl_down(found, d, 64);
-        }
-        if (lane == 0) {
-            if (found) atomicAdd(ctr, found);
-            if (windows) atomicAdd(ctr + 3, static_cast<unsigned long long>(windows));
-        }
-        if (threadIdx.x == 0 && n_q) atomicAdd(ctr + 2, static_cast<unsigned long long>(n_q));
-    }
+    if (kMode == kCount) count_totals(windows, found, n_q, lane, ctr);
 }
 
 // Row j is sorted word j: the window of L + b bases is read again, as text.
@@ -172,11 +163,9 @@ __global__ __launch_bounds__(256) void k_bulge_finish(const uint64_t *__restrict
 {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= total) return;
-    const uint64_t w = words[j];
-    const uint32_t slot = static_cast<uint32_t>(w) & ((1u << kSlotBits) - 1);
-    const uint32_t strand = static_cast<uint32_t>(w >> kSlotBits) & 1u;
-    const uint64_t pos = (w >> (1 + kSlotBits)) & ((1ull << pos_bits) - 1);
-    const uint32_t qi = static_cast<uint32_t>(w >> (pos_bits + 1 + kSlotBits));
+    uint32_t qi, strand, slot;
+    uint64_t pos;
+    decode_hit<kSlotBits>(words[j], pos_bits, qi, pos, strand, slot);
     const int32_t b = static_cast<int32_t>(slot) - static_cast<int32_t>(bg.max_rna);
     const uint32_t window = static_cast<uint32_t>(static_cast<int32_t>(length) + b);
     uint64_t f = 0;
@@ -233,10 +222,11 @@ struct BulgeSearch {
         return n == 0 || !any;
     }
     static size_t bins(const Call &c) { return static_cast<size_t>(c.bg.max_rna + c.bg.max_dna + 1) * (c.max_dist + 1); }
+    static size_t scratch_bytes(const Call &, size_t) { return 0; }
 
     template <int kMode>
-    static void launch(const issl_genome *g, const Call &c, const issl_search_query *d_q, uint32_t n, unsigned long long *ctr, uint64_t *words,
-                       uint64_t cap, unsigned long long *counts, hipStream_t stream)
+    static void launch(const issl_genome *g, const Call &c, const issl_search_query *d_q, uint32_t n, void *, unsigned long long *ctr,
+                       uint64_t *words, uint64_t cap, unsigned long long *counts, hipStream_t stream)
     {
         for_each_launch(g, c, [&](const SearchArgs &a, const BulgeArgs &b) {
             launch_bulge<kMode>(b.r != 0, text_blocks(g), stream, static_cast<const uint8_t *>(g->seq.p), g->len, a, b, d_q, n, g->pos_bits, ctr,

@@ -1,9 +1,9 @@
 // Genome search with DNA and RNA bulges on a variant-aware text (issl_genome_search_bulges_variants*, include/issl_hip.h):
 // the bulge search with IUPAC ambiguity codes in the text read as sets of bases.  The fourth unit of SearchDriver
-// (issl_search_device.hpp) with the protocol of issl_search_core.hpp; a piece has up to 2^19 queries.  This unit's own:
-//   front    k_variants': four planes and a validity plane of the tile in LDS, 32 positions per word; a window of W = L + b
-//            codes is four funnel shifts; the ambiguity count over all W codes; both strands tested on the forward window,
-//            against P' and its reversed complement; the survivors compacted into the queue of 13-bit tags
+// (issl_search_device.hpp) with the protocol of issl_search_core.hpp; a piece has up to 2^19 queries.  The front is
+// k_variants', from issl_planes_device.hpp, for windows of W = L + b codes: planes and validity plane of the tile in LDS,
+// the ambiguity count over all W codes, both strands tested on the forward window against P' and its reversed
+// complement, the survivors compacted into the queue of 13-bit tags.  This unit's own:
 //   count    k_bulge_variants<kCount>, one launch per bulge b = -R..D (at most seven) with that b's P' and window.  A lane
 //            holds one survivor's planes cut by P' and, for a DNA bulge, the same planes shifted down by b; for an RNA
 //            bulge the wave-uniform query planes are shifted instead (k_bulge_variants<, kRna>).  Against a query it forms
@@ -30,45 +30,16 @@
 #include "issl_genome_handle.hpp"
 #include "issl_host.hpp"
 #include "issl_match.hpp"
-#include "issl_search_core.hpp"
+#include "issl_planes_device.hpp"
 
 namespace issl {
 namespace {
 
-namespace vt = variants_text;
 namespace bvt = bulge_variants_text;
 using bvt::BulgeVariantArgs;
-using vt::Planes;
 
-constexpr uint32_t kSlotBits = 3;                        // b + R: 0..6
-constexpr uint32_t kPlaneWords = kPosPerBlock / 32 + 1; // 32 positions per word; the halo of up to 31 is one more word
-static_assert(sizeof(issl_bulge_variant_hit) == 48 && sizeof(issl_search_bulges) == 16 && sizeof(Planes) == 16,
-              "the layouts of include/issl_hip.h");
-
-// 16 bytes of text at `at` (a multiple of 16) -> 16 bits of every plane and one bit per byte that is none of the 14
-// codes; what lies behind the text is such a byte.
-__device__ __forceinline__ void planes16(const uint8_t *__restrict__ s, uint64_t at, uint64_t len, uint32_t (&plane)[4], uint32_t &bad)
-{
-    plane[0] = plane[1] = plane[2] = plane[3] = 0;
-    bad = 0;
-    uint32_t w[4] = {0, 0, 0, 0}; // (a zero byte is no code)
-    if (at + 16 <= len) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(s + at);
-        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-    } else {
-        for (uint32_t i = 0; i < 16; ++i)
-            if (at + i < len) w[i >> 2] |= static_cast<uint32_t>(s[at + i]) << (8 * (i & 3));
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 16; ++i) {
-        const uint32_t set = vt::text_set(static_cast<uint8_t>(w[i >> 2] >> (8 * (i & 3))));
-        plane[0] |= (set & 1u) << i;
-        plane[1] |= (set >> 1 & 1u) << i;
-        plane[2] |= (set >> 2 & 1u) << i;
-        plane[3] |= (set >> 3) << i;
-        bad |= (set ? 0u : 1u) << i;
-    }
-}
+constexpr uint32_t kSlotBits = 3; // b + R: 0..6
+static_assert(sizeof(issl_bulge_variant_hit) == 48 && sizeof(issl_search_bulges) == 16, "the layouts of include/issl_hip.h");
 
 // The queries of a piece as planes over their own L positions: out[k], and behind them for every r = 1..max_rna the planes
 // the bound of an RNA bulge of r bases takes, out[r * n + k] = the query's planes united with the same shifted down by r.
@@ -81,8 +52,6 @@ __global__ __launch_bounds__(256) void k_bulge_variant_queries(const issl_search
     out[k] = one;
     for (uint32_t r = 1; r <= max_rna; ++r) out[static_cast<size_t>(r) * n + k] = bvt::united(one, bvt::shifted_query(one, r));
 }
-
-struct PlaneGroup { Planes q[kQueryGroup]; };
 
 // ctr[0]: rows; ctr[1]: the cursor of k_bulge_variants<kEmit>; ctr[2]: window-strands the patterns admit; ctr[3]: windows
 // of codes with at most max_variants ambiguous positions, summed over the launches of a piece (the figures of the timing
@@ -101,56 +70,12 @@ __global__ __launch_bounds__(256) void k_bulge_variants(const uint8_t *__restric
     const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kPosPerBlock;
     const uint32_t lane = threadIdx.x & 63;
     if (threadIdx.x == 0) q_count = 0;
-    {
-        uint32_t plane[4], bad;
-        planes16(s, base + 16ull * threadIdx.x, len, plane, bad);
-#pragma unroll
-        for (uint32_t b = 0; b < 4; ++b) reinterpret_cast<uint16_t *>(tile[b])[threadIdx.x] = static_cast<uint16_t>(plane[b]);
-        reinterpret_cast<uint16_t *>(tile[4])[threadIdx.x] = static_cast<uint16_t>(bad);
-        if (threadIdx.x < 2) {
-            planes16(s, base + kPosPerBlock + 16ull * threadIdx.x, len, plane, bad);
-#pragma unroll
-            for (uint32_t b = 0; b < 4; ++b) reinterpret_cast<uint16_t *>(tile[b])[256 + threadIdx.x] = static_cast<uint16_t>(plane[b]);
-            reinterpret_cast<uint16_t *>(tile[4])[256 + threadIdx.x] = static_cast<uint16_t>(bad);
-        }
-    }
+    fill_planes16(s, base + 16ull * threadIdx.x, len, tile, threadIdx.x);
+    if (threadIdx.x < 2) fill_planes16(s, base + kPosPerBlock + 16ull * threadIdx.x, len, tile, 256 + threadIdx.x); // the halo
     __syncthreads();
-
-    // -- the pattern P' on the thread's 16 windows of W codes, both strands: two bits per window
-    uint32_t pass = 0, windows = 0;
-    {
-        const uint32_t wi = threadIdx.x >> 1, s0 = (threadIdx.x & 1u) << 4;
-        uint32_t lo[5], hi[5];
-#pragma unroll
-        for (uint32_t b = 0; b < 5; ++b) lo[b] = tile[b][wi], hi[b] = tile[b][wi + 1];
-#pragma unroll
-        for (uint32_t k = 0; k < 16; ++k) {
-            if (vt::funnel(lo[4], hi[4], s0 + k) & a.win_mask) continue;
-            const Planes f{{vt::funnel(lo[0], hi[0], s0 + k) & a.win_mask, vt::funnel(lo[1], hi[1], s0 + k) & a.win_mask,
-                            vt::funnel(lo[2], hi[2], s0 + k) & a.win_mask, vt::funnel(lo[3], hi[3], s0 + k) & a.win_mask}};
-            if (static_cast<uint32_t>(__builtin_popcount(vt::ambiguous(f))) > a.max_variants) continue;
-            ++windows;
-            if (vt::admits(f, a.allow, a.win_mask)) pass |= 1u << (2 * k);
-            if (vt::admits(f, a.allow_rc, a.win_mask)) pass |= 2u << (2 * k);
-        }
-    }
-    // -- the survivors into the queue: a scan inside the wave, one LDS atomic per wave
-    {
-        const uint32_t cnt = static_cast<uint32_t>(__builtin_popcount(pass));
-        uint32_t incl = cnt;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += y;
-        }
-        uint32_t wave_base = 0;
-        if (lane == 63 && incl) wave_base = atomicAdd(&q_count, incl);
-        wave_base = __shfl(wave_base, 63, 64);
-        uint32_t at = wave_base + incl - cnt;
-        for (uint32_t m = pass; m; m &= m - 1) {
-            const uint32_t bit = static_cast<uint32_t>(__builtin_ctz(m));
-            queue[at++] = static_cast<uint16_t>(((threadIdx.x * 16 + (bit >> 1)) << 1) | (bit & 1u));
-        }
-    }
+    uint32_t pass, windows; // the pattern P' on the windows of W codes
+    test_plane_windows(a, tile, pass, windows);
+    queue_survivors(pass, lane, queue, q_count);
     __syncthreads();
     const uint32_t n_q = q_count;
 
@@ -167,10 +92,7 @@ __global__ __launch_bounds__(256) void k_bulge_variants(const uint8_t *__restric
         Planes t{{0, 0, 0, 0}}; // what the strand reads, cut by P': nothing matches where there is no survivor
         if (valid) {
             tag = queue[j];
-            const uint32_t p = tag >> 1, wi = p >> 5, sh = p & 31u;
-            const Planes f{{vt::funnel(tile[0][wi], tile[0][wi + 1], sh) & a.win_mask, vt::funnel(tile[1][wi], tile[1][wi + 1], sh) & a.win_mask,
-                            vt::funnel(tile[2][wi], tile[2][wi + 1], sh) & a.win_mask, vt::funnel(tile[3][wi], tile[3][wi + 1], sh) & a.win_mask}};
-            t = vt::intersect((tag & 1u) ? vt::strand1(f, a.rev_shift) : f, a.allow);
+            t = survivor_planes(tag, tile, a);
         }
         const Planes tb = bvt::shifted_text(t, v.g.b); // (an RNA bulge: t itself, no further registers)
         // the positions of one query that match at either shift (match_either), the two shifts folded into one operand: the
@@ -215,17 +137,7 @@ __global__ __launch_bounds__(256) void k_bulge_variants(const uint8_t *__restric
         for (; qi < mine_q.hi; ++qi) walk(qs[qi], qi);
         if (kMode == kCount && valid) found += mine;
     }
-    if (kMode == kCount) {
-        for (int d = 32; d > 0; d >>= 1) {
-            windows += __shfl_down(windows, d, 64);
-            found += __shfl_down(found, d, 64);
-        }
-        if (lane == 0) {
-            if (found) atomicAdd(ctr, found);
-            if (windows) atomicAdd(ctr + 3, static_cast<unsigned long long>(windows));
-        }
-        if (threadIdx.x == 0 && n_q) atomicAdd(ctr + 2, static_cast<unsigned long long>(n_q));
-    }
+    if (kMode == kCount) count_totals(windows, found, n_q, lane, ctr);
 }
 
 // What the finish kernel takes: the launches of a call by slot b + R.
@@ -239,11 +151,9 @@ __global__ __launch_bounds__(256) void k_bulge_variants_finish(const uint64_t *_
 {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= total) return;
-    const uint64_t w = words[j];
-    const uint32_t slot = static_cast<uint32_t>(w) & ((1u << kSlotBits) - 1);
-    const uint32_t strand = static_cast<uint32_t>(w >> kSlotBits) & 1u;
-    const uint64_t pos = (w >> (1 + kSlotBits)) & ((1ull << pos_bits) - 1);
-    const uint32_t qi = static_cast<uint32_t>(w >> (pos_bits + 1 + kSlotBits));
+    uint32_t qi, strand, slot;
+    uint64_t pos;
+    decode_hit<kSlotBits>(words[j], pos_bits, qi, pos, strand, slot);
     const BulgeVariantArgs &v = slots.v[slot < 7 ? slot : 0];
     bvt::RowFields f{};
     (void)bvt::window_row(s + pos, v, strand, q[qi].sig, q[qi].care, f);
@@ -268,12 +178,11 @@ template <int kMode, class... Args> void launch_bulge_variants(bool rna, uint32_
     else hipLaunchKernelGGL((k_bulge_variants<kMode, false>), dim3(blocks), dim3(256), 0, stream, args...);
 }
 
-// One call: the launches of its b in ascending order (launch k has slot k), and room for the planes of a piece's queries.
+// One call: the launches of its b in ascending order (launch k has slot k).
 struct BulgeVariantCall {
     issl_search_bulges bg{};
     uint32_t max_dist = 0, max_variants = 0, query_mask = 0, n_launches = 0;
     BulgeVariantSlots s{};
-    Planes *q_planes = nullptr;
 };
 
 // The launches whose window fits the text.
@@ -301,17 +210,20 @@ struct BulgeVariantSearch {
         return n == 0 || !any;
     }
     static size_t bins(const Call &c) { return static_cast<size_t>(c.bg.max_rna + c.bg.max_dna + 1) * (c.max_dist + 1); }
+    // the planes of a piece's queries and one more set per r
+    static size_t scratch_bytes(const Call &c, size_t n) { return sizeof(Planes) * n * (1 + c.bg.max_rna); }
 
     // The first launch of a piece (kCount, or kProfile alone) expands its queries; kEmit follows kCount on the same piece.
     template <int kMode>
-    static void launch(const issl_genome *g, const Call &c, const issl_search_query *d_q, uint32_t n, unsigned long long *ctr, uint64_t *words,
-                       uint64_t cap, unsigned long long *counts, hipStream_t stream)
+    static void launch(const issl_genome *g, const Call &c, const issl_search_query *d_q, uint32_t n, void *scratch, unsigned long long *ctr,
+                       uint64_t *words, uint64_t cap, unsigned long long *counts, hipStream_t stream)
     {
+        Planes *q_planes = static_cast<Planes *>(scratch);
         if (kMode != kEmit)
-            hipLaunchKernelGGL(k_bulge_variant_queries, dim3((n + 255) / 256), dim3(256), 0, stream, d_q, n, c.query_mask, c.bg.max_rna, c.q_planes);
+            hipLaunchKernelGGL(k_bulge_variant_queries, dim3((n + 255) / 256), dim3(256), 0, stream, d_q, n, c.query_mask, c.bg.max_rna, q_planes);
         for_each_launch(g, c, [&](const BulgeVariantArgs &v) {
             launch_bulge_variants<kMode>(v.g.r != 0, text_blocks(g), stream, static_cast<const uint8_t *>(g->seq.p), g->len, v,
-                                         static_cast<const Planes *>(c.q_planes), n, g->pos_bits, ctr, words, cap, counts);
+                                         static_cast<const Planes *>(q_planes), n, g->pos_bits, ctr, words, cap, counts);
         });
     }
 
@@ -346,16 +258,6 @@ int check_bulge_variant_call(const issl_search_pattern *pat, const issl_search_b
     return ISSL_OK;
 }
 
-// Room for the planes of one piece's queries, on the handle's device.
-int piece_planes(issl_genome *g, size_t n, DevBuf &buf, BulgeVariantCall *c)
-{
-    HIP_TRY(hipSetDevice(g->device));
-    const size_t piece = std::min(n, BulgeVariantSearch::kPieceQueries);
-    if (piece) HIP_TRY(hipMalloc(&buf.p, sizeof(Planes) * piece * (1 + c->bg.max_rna))); // the queries' planes and one set per r
-    c->q_planes = static_cast<Planes *>(buf.p);
-    return ISSL_OK;
-}
-
 } // namespace
 } // namespace issl
 
@@ -369,9 +271,6 @@ int issl_genome_search_bulges_variants(issl_genome *g, const issl_search_pattern
     return issl::abi_call([&]() -> int {
         issl::BulgeVariantCall c;
         if (int rc = issl::check_bulge_variant_call(pat, bulges, max_dist, max_variants, n, &c)) return rc;
-        if (int rc = issl::check_host_queries(queries, n, pat->length)) return rc;
-        issl::DevBuf planes;
-        if (int rc = issl::piece_planes(g, n, planes, &c)) return rc;
         return issl::BulgedVariants::host_rows(g, c, pat->length, queries, n, offsets, hits, cap, n_total);
     });
 }
@@ -386,8 +285,6 @@ int issl_genome_search_bulges_variants_device(issl_genome *g, const issl_search_
     return issl::abi_call([&]() -> int {
         issl::BulgeVariantCall c;
         if (int rc = issl::check_bulge_variant_call(pat, bulges, max_dist, max_variants, n, &c)) return rc;
-        issl::DevBuf planes;
-        if (int rc = issl::piece_planes(g, n, planes, &c)) return rc;
         return issl::BulgedVariants::device_rows(g, c, d_queries, n, d_offsets, d_hits, cap, n_total, stream);
     });
 }
@@ -400,9 +297,6 @@ int issl_genome_search_bulges_variants_profile(issl_genome *g, const issl_search
     return issl::abi_call([&]() -> int {
         issl::BulgeVariantCall c;
         if (int rc = issl::check_bulge_variant_call(pat, bulges, max_dist, max_variants, n, &c)) return rc;
-        if (int rc = issl::check_host_queries(queries, n, pat->length)) return rc;
-        issl::DevBuf planes;
-        if (int rc = issl::piece_planes(g, n, planes, &c)) return rc;
         return issl::BulgedVariants::host_profile(g, c, pat->length, queries, n, counts);
     });
 }
@@ -415,8 +309,6 @@ int issl_genome_search_bulges_variants_profile_device(issl_genome *g, const issl
     return issl::abi_call([&]() -> int {
         issl::BulgeVariantCall c;
         if (int rc = issl::check_bulge_variant_call(pat, bulges, max_dist, max_variants, n, &c)) return rc;
-        issl::DevBuf planes;
-        if (int rc = issl::piece_planes(g, n, planes, &c)) return rc;
         return issl::BulgedVariants::device_profile(g, c, d_queries, n, d_counts, stream);
     });
 }

@@ -17,3 +17,25 @@ struct issl_genome {
     std::vector<issl::FastaRecord> records;
 };
 
+namespace issl {
+
+// A handle's records as the arrays the readers of VCF, SNPs and indels take (issl_variants_text.hpp,
+// issl_haplotypes_text.hpp).  The names point into the handle.
+struct RecordTable {
+    std::vector<const char *> names;
+    std::vector<size_t> name_lens;
+    std::vector<uint64_t> starts, lengths;
+    explicit RecordTable(const issl_genome *g)
+    {
+        for (const FastaRecord &r : g->records) {
+            names.push_back(r.name.data());
+            name_lens.push_back(r.name.size());
+            starts.push_back(r.start);
+            lengths.push_back(r.length);
+        }
+    }
+    size_t size() const { return starts.size(); }
+};
+
+} // namespace issl
+

@@ -92,15 +92,14 @@ int open_haplotypes(issl_genome *g, const issl_indel *indels, size_t n, const ch
         set_error("more than 2^32 - 1 indels");
         return ISSL_E_UNSUPPORTED;
     }
-    std::vector<uint64_t> rec_starts(g->records.size()), lengths(g->records.size());
-    for (size_t r = 0; r < g->records.size(); ++r) rec_starts[r] = g->records[r].start, lengths[r] = g->records[r].length;
+    const RecordTable table(g);
     std::vector<ht::Strip> strips;
     std::vector<ht::StripSource> sources;
     std::vector<ht::RefPlace> places;
     std::vector<uint64_t> starts;
     uint64_t text_len = 0;
     std::string upper, err;
-    if (!ht::plan_strips(indels, n, alleles, alleles_len, rec_starts.data(), lengths.data(), rec_starts.size(), static_cast<uint32_t>(window),
+    if (!ht::plan_strips(indels, n, alleles, alleles_len, table.starts.data(), table.lengths.data(), table.size(), static_cast<uint32_t>(window),
                          strips, sources, places, starts, text_len, upper, err)) {
         set_error(err);
         return ISSL_E_ARG;
@@ -232,19 +231,12 @@ int issl_haplotypes_open_vcf(issl_genome *g, const char *vcf, size_t len, int wi
     if (out) *out = nullptr;
     if (!g || !out || (!vcf && len)) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
-        const size_t n_records = g->records.size();
-        std::vector<const char *> names(n_records);
-        std::vector<size_t> name_lens(n_records);
-        std::vector<uint64_t> lengths(n_records);
-        for (size_t r = 0; r < n_records; ++r) {
-            names[r] = g->records[r].name.data();
-            name_lens[r] = g->records[r].name.size();
-            lengths[r] = g->records[r].length;
-        }
+        const issl::RecordTable table(g);
         std::string err, alleles;
         std::vector<issl_indel> indels;
         issl_vcf_indel_counts c{};
-        if (!issl::haplotypes_text::read_vcf_indels(vcf, len, names.data(), name_lens.data(), lengths.data(), n_records, indels, alleles, c, err)) {
+        if (!issl::haplotypes_text::read_vcf_indels(vcf, len, table.names.data(), table.name_lens.data(), table.lengths.data(), table.size(), indels,
+                                                    alleles, c, err)) {
             issl::set_error(err);
             return ISSL_E_ARG;
         }

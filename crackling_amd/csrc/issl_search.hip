@@ -1,9 +1,11 @@
 // Genome search: where a query binds with at most max_dist mismatches, for any PAM pattern and any length up to 32
 // (issl_genome_search*, include/issl_hip.h).  No index: the resident text of a genome handle (issl_genome_handle.hpp) is
-// compared with every query.  The protocol -- count, emit, sort, offsets, finish, and the profile -- is that of
-// issl_search_core.hpp, its host side SearchDriver<PlainSearch> (issl_search_device.hpp); issl_bulge.hip follows it too.
-// This unit's own: k_search's comparison, one distance per survivor and query; a hit word is query | text position |
-// strand with nothing below; k_search_finish writes site, mism, dist and the record of a row.
+// compared with every query.  The first unit of SearchDriver (issl_search_device.hpp: the host side, once for all units)
+// with the protocol of issl_search_core.hpp -- count, emit, sort, offsets, finish, and the profile -- and that header's
+// device pieces: the split of the queries over the waves, the sinks, the hit word, the kCount reduction.  This unit's
+// own: k_search with the two-bit front (issl_bulge.hip has the same text; the core header says why it is no function),
+// the walk over the queries and the comparison, one distance per survivor and query; a hit word with nothing below the
+// strand; k_search_finish, which writes site, mism, dist and the record of a row.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -126,17 +128,7 @@ __global__ __launch_bounds__(256) void k_search(const uint8_t *__restrict__ s, u
         for (; qi < mine_q.hi; ++qi) compare(q[qi], qi);
         if (kMode == kCount && valid) found += mine;
     }
-    if (kMode == kCount) {
-        for (int d = 32; d > 0; d >>= 1) {
-            windows += __shfl_down(windows, d, 64);
-            found += __shfl_down(found, d, 64);
-        }
-        if (lane == 0) {
-            if (found) atomicAdd(ctr, found);
-            if (windows) atomicAdd(ctr + 3, static_cast<unsigned long long>(windows));
-        }
-        if (threadIdx.x == 0 && n_q) atomicAdd(ctr + 2, static_cast<unsigned long long>(n_q));
-    }
+    if (kMode == kCount) count_totals(windows, found, n_q, lane, ctr);
 }
 
 // Row j is sorted word j: the window is read again, as text.
@@ -147,10 +139,9 @@ __global__ __launch_bounds__(256) void k_search_finish(const uint64_t *__restric
 {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= total) return;
-    const uint64_t w = words[j];
-    const uint32_t strand = static_cast<uint32_t>(w & 1u);
-    const uint64_t pos = (w >> 1) & ((1ull << pos_bits) - 1);
-    const uint32_t qi = static_cast<uint32_t>(w >> (pos_bits + 1));
+    uint32_t qi, strand, low;
+    uint64_t pos;
+    decode_hit<0>(words[j], pos_bits, qi, pos, strand, low);
     uint64_t f = 0;
     for (uint32_t i = 0; i < a.length; ++i) f |= static_cast<uint64_t>(base_code(s[pos + i]) & 3u) << (2 * i);
     const uint64_t t = strand ? reverse_complement(f, a.rev_shift) : f;
@@ -174,10 +165,11 @@ struct PlainSearch {
     static std::string counted(const Call &) { return ""; }
     static bool nothing(const issl_genome *g, const Call &a, size_t n) { return n == 0 || g->len < a.length; }
     static size_t bins(const Call &a) { return a.max_dist + 1; }
+    static size_t scratch_bytes(const Call &, size_t) { return 0; }
 
     template <int kMode>
-    static void launch(const issl_genome *g, const Call &a, const issl_search_query *d_q, uint32_t n, unsigned long long *ctr, uint64_t *words,
-                       uint64_t cap, unsigned long long *counts, hipStream_t stream)
+    static void launch(const issl_genome *g, const Call &a, const issl_search_query *d_q, uint32_t n, void *, unsigned long long *ctr,
+                       uint64_t *words, uint64_t cap, unsigned long long *counts, hipStream_t stream)
     {
         hipLaunchKernelGGL(k_search<kMode>, dim3(text_blocks(g)), dim3(256), 0, stream, static_cast<const uint8_t *>(g->seq.p), g->len, a, d_q,
                            n, g->pos_bits, ctr, words, cap, counts);

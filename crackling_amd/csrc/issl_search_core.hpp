@@ -26,10 +26,26 @@
 // and distance (profile_hits); no row exists anywhere.
 // The host waits for the number of hit words (sizes the buffers of the sort) and for the end of a piece.
 //
-// What is not in here although the kernels have it: the tile front (pack16 loads, pattern test, compaction), the
-// survivor's fetch, the walk over the query groups and the kCount reduction.  The compiler finishes a function before it
-// inlines it, and each of these came back with operands of commutative instructions swapped or two instructions in the
-// other order (profiles/search_core_isa.txt); they stay written out until the kernels may change.
+// What is shared and what is not.  Shared: the split of the queries over the waves (wave_queries), the kCount reduction
+// (count_totals) and the hit word both ways (emit_hits, decode_hit) in all four kernels; the compaction
+// (queue_survivors) in the two plane kernels, whose whole front is one copy in issl_planes_device.hpp.  The LDS arrays
+// stay declared in the kernels and come in by reference: one __shared__ struct around them moved their offsets and cost
+// k_variants instructions and a register.  As functions the pieces do not come back instruction for instruction (the
+// operands of commutative instructions swap, v_or3 becomes two v_or), so the bar is that of
+// profiles/search_core_isa.txt: the loops over the query groups hold the same instructions, registers, scratch and LDS
+// are what they were, and so is the time (profiles/search_fold_ab.json).
+// Not shared, with the reason:
+//   the two-bit front of k_search and k_bulge (pattern test on the 16 windows, compaction, survivor fetch) is written
+//   out in both kernels, the same text.  With test_windows(), queue_survivors() and survivor_word() in its place every
+//   loop kept its opcodes and every register count, and the count stage got faster, but the emit stage of 10 000 queries
+//   on 200 Mbp went from 72.3 to 73.3 ms in k_search and from 936.3 to 938.3 ms in k_bulge (D = R = 2), outside the
+//   parent's spread of 0.3 and 0.8 ms.  The compaction alone as a function still changes 119 lines of k_search<kEmit>;
+//   written out, k_search<kEmit | kProfile> and k_bulge<kEmit | kProfile, *> are the parent's text
+//   the two calls that fill a tile and its halo: wrapped into one function they cost k_variants three registers, 63 to
+//   66, beyond the 64 that eight waves per SIMD allow
+//   the walk over the query groups and what it calls (the lambdas compare, bound and walk): it is the hot loop; it has two
+//   shapes (compare each query: k_search, k_variants; the group's bound first: k_bulge, k_bulge_variants) over two query
+//   types, and as a function taking the lambdas it is as much text as the loops of eight lines it would replace
 #pragma once
 #include "issl_search_device.hpp"
 
@@ -44,6 +60,43 @@ __device__ __forceinline__ QueryRange wave_queries(uint32_t n)
 {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     return {static_cast<uint32_t>(static_cast<uint64_t>(n) * wave / 4), static_cast<uint32_t>(static_cast<uint64_t>(n) * (wave + 1) / 4)};
+}
+
+// The survivors of the workgroup into the queue: bit 2k + strand of `pass` is window k of the thread's 16, its tag the
+// position in the tile << 1 | strand.  A scan inside the wave and one LDS atomic per wave; q_count is valid behind the
+// caller's __syncthreads().
+__device__ __forceinline__ void queue_survivors(uint32_t pass, uint32_t lane, uint16_t (&queue)[2 * kPosPerBlock], uint32_t &q_count)
+{
+    const uint32_t cnt = static_cast<uint32_t>(__builtin_popcount(pass));
+    uint32_t incl = cnt;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += y;
+    }
+    uint32_t wave_base = 0;
+    if (lane == 63 && incl) wave_base = atomicAdd(&q_count, incl);
+    wave_base = __shfl(wave_base, 63, 64);
+    uint32_t at = wave_base + incl - cnt;
+    for (uint32_t m = pass; m; m &= m - 1) {
+        const uint32_t bit = static_cast<uint32_t>(__builtin_ctz(m));
+        queue[at++] = static_cast<uint16_t>(((threadIdx.x * 16 + (bit >> 1)) << 1) | (bit & 1u));
+    }
+}
+
+// kCount, at the end of the workgroup: ctr[0] += the hits its lanes found, ctr[3] += the windows they tested, ctr[2] +=
+// the survivors of the tile; one atomic per wave and figure that is not zero.
+__device__ __forceinline__ void count_totals(uint32_t windows, unsigned long long found, uint32_t n_q, uint32_t lane,
+                                             unsigned long long *__restrict__ ctr)
+{
+    for (int d = 32; d > 0; d >>= 1) {
+        windows += __shfl_down(windows, d, 64);
+        found += __shfl_down(found, d, 64);
+    }
+    if (lane == 0) {
+        if (found) atomicAdd(ctr, found);
+        if (windows) atomicAdd(ctr + 3, static_cast<unsigned long long>(windows));
+    }
+    if (threadIdx.x == 0 && n_q) atomicAdd(ctr + 2, static_cast<unsigned long long>(n_q));
 }
 
 // kEmit: the hits `who` of the wave against query qi, one word each, query | text position | strand | low (kLowBits
@@ -62,6 +115,16 @@ __device__ __forceinline__ void emit_hits(uint64_t who, bool hit, uint32_t lane,
     if (hit && at < cap)
         words[at] = (static_cast<uint64_t>(qi) << (pos_bits + 1 + kLowBits)) | ((base + (tag >> 1)) << (1 + kLowBits)) |
                     (static_cast<uint64_t>(tag & 1u) << kLowBits) | low;
+}
+
+// The finish kernels: what emit_hits put into the word w, the position as a text position.
+template <uint32_t kLowBits>
+__device__ __forceinline__ void decode_hit(uint64_t w, uint32_t pos_bits, uint32_t &qi, uint64_t &pos, uint32_t &strand, uint32_t &low)
+{
+    low = static_cast<uint32_t>(w) & ((1u << kLowBits) - 1);
+    strand = static_cast<uint32_t>(w >> kLowBits) & 1u;
+    pos = (w >> (1 + kLowBits)) & ((1ull << pos_bits) - 1);
+    qi = static_cast<uint32_t>(w >> (pos_bits + 1 + kLowBits));
 }
 
 // kProfile: counts[row * bins + dist] += the wave's hits at that distance, one atomic per distance that occurs among

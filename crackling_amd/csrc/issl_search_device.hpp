@@ -117,11 +117,14 @@ inline int upload_queries(issl_genome *g, const issl_search_query *queries, size
 
 // ---- the driver of a unit ------------------------------------------------------------------------------------------
 // The host side of the protocol (issl_search_core.hpp), once for every unit.  A unit describes itself with a struct U:
-//   Row, Call              the row type; what a checked call carries to the launches (SearchArgs, BulgeCall, VariantCall)
+//   Row, Call              the row type; what a checked call carries to the launches (SearchArgs, BulgeCall, VariantArgs,
+//                          BulgeVariantCall)
 //   kPieceQueries          queries per piece;  kLowBits: the bits of the hit word below the strand
 //   kTag, kRows            "[issl search]" / "hits" of the timing lines;  counted(c): what follows "N queries" there
 //   nothing(g, c, n)       is there nothing to search
-//   launch<kMode>(g, c, d_q, n, ctr, words, cap, counts, stream)   enqueue the count / emit / profile launches of a piece
+//   scratch_bytes(c, n)    device memory a piece of n queries needs beside its queries, 0 for none: the driver allocates
+//                          it once per call for the largest piece and hands it to every launch
+//   launch<kMode>(g, c, d_q, n, scratch, ctr, words, cap, counts, stream)   enqueue the count / emit / profile launches of a piece
 //   finish(g, c, words, total, d_q, q_base, rows, stream)          enqueue the finish kernel
 //   bins(c)                counts per query of the profile
 
@@ -136,15 +139,15 @@ template <class U> struct SearchDriver {
     using Row = typename U::Row;
 
     // Everything of a piece of n <= kPieceQueries queries but the rows: d_offsets[0..n] = base + the piece's offsets.
-    static int piece(const issl_genome *g, const Call &c, const issl_search_query *d_q, uint32_t n, uint64_t base, uint64_t *d_offsets,
-                     hipStream_t stream, SearchPiece &pc)
+    static int piece(const issl_genome *g, const Call &c, const issl_search_query *d_q, uint32_t n, void *scratch, uint64_t base,
+                     uint64_t *d_offsets, hipStream_t stream, SearchPiece &pc)
     {
         StageTimer clock(g->timing, stream);
         DevBuf ctrb;
         HIP_TRY(hipMalloc(&ctrb.p, 64));
         unsigned long long *ctr = static_cast<unsigned long long *>(ctrb.p);
         HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
-        U::template launch<kCount>(g, c, d_q, n, ctr, nullptr, 0, nullptr, stream);
+        U::template launch<kCount>(g, c, d_q, n, scratch, ctr, nullptr, 0, nullptr, stream);
         HIP_TRY(hipGetLastError());
         unsigned long long seen[4] = {};
         HIP_TRY(hipMemcpyAsync(seen, ctr, sizeof seen, hipMemcpyDeviceToHost, stream));
@@ -159,7 +162,7 @@ template <class U> struct SearchDriver {
                          o_hh = ha.reserve(4 * radix_hist_words(radix_sort_blocks(pc.n_words)));
             HIP_TRY(hipMalloc(&ha.buf.p, ha.size));
             uint64_t *ha_w = ha.at<uint64_t>(o_ha), *hb_w = ha.at<uint64_t>(o_hb);
-            U::template launch<kEmit>(g, c, d_q, n, ctr, ha_w, pc.n_words, nullptr, stream);
+            U::template launch<kEmit>(g, c, d_q, n, scratch, ctr, ha_w, pc.n_words, nullptr, stream);
             clock.note("emit");
             pc.words = radix_sort_async(ha_w, hb_w, pc.n_words, 0, shift + bits_for(n), ha.at<uint32_t>(o_hh), stream);
             clock.note("sort");
@@ -172,6 +175,14 @@ template <class U> struct SearchDriver {
         if (g->timing)
             std::fprintf(stderr, "%s %u queries%s:%s | windows %llu admitted %llu %s %llu\n", U::kTag, n, U::counted(c).c_str(),
                          clock.line.c_str(), seen[3], seen[2], U::kRows, seen[0]);
+        return ISSL_OK;
+    }
+
+    // The scratch of the call's largest piece, on the handle's device, which the caller has made current.
+    static int piece_scratch(const Call &c, size_t n, DevBuf &buf)
+    {
+        const size_t bytes = U::scratch_bytes(c, std::min(n, U::kPieceQueries));
+        if (bytes) HIP_TRY(hipMalloc(&buf.p, bytes));
         return ISSL_OK;
     }
 
@@ -201,6 +212,8 @@ template <class U> struct SearchDriver {
             HIP_TRY(hipStreamSynchronize(stream));
             return ISSL_OK;
         }
+        DevBuf scratch;
+        if (int rc = piece_scratch(c, n, scratch)) return rc;
         auto rows_of = [&](const SearchPiece &pc, size_t at, uint64_t base) -> int {
             if (!rows_to_host) return finish(g, c, pc, d_q + at, static_cast<uint32_t>(at), hits + base, stream);
             if (pc.n_words == 0) return ISSL_OK;
@@ -217,7 +230,7 @@ template <class U> struct SearchDriver {
             const uint32_t cnt = static_cast<uint32_t>(std::min(kPiece, n - at));
             SearchPiece pc;
             bases.push_back(total);
-            if (int rc = piece(g, c, d_q + at, cnt, total, d_offsets + at, stream, pc)) return rc;
+            if (int rc = piece(g, c, d_q + at, cnt, scratch.p, total, d_offsets + at, stream, pc)) return rc;
             total += pc.n_words;
             if (total > 0xFFFFFFFFull) return too_many(total);
             if (n <= kPiece && hits && total <= cap)
@@ -228,7 +241,7 @@ template <class U> struct SearchDriver {
         for (size_t at = 0, k = 0; at < n; at += kPiece, ++k) {
             const uint32_t cnt = static_cast<uint32_t>(std::min(kPiece, n - at));
             SearchPiece pc;
-            if (int rc = piece(g, c, d_q + at, cnt, bases[k], d_offsets + at, stream, pc)) return rc;
+            if (int rc = piece(g, c, d_q + at, cnt, scratch.p, bases[k], d_offsets + at, stream, pc)) return rc;
             if (int rc = rows_of(pc, at, bases[k])) return rc;
         }
         return ISSL_OK;
@@ -240,12 +253,14 @@ template <class U> struct SearchDriver {
         if (n == 0) return ISSL_OK;
         const size_t bins = U::bins(c);
         HIP_TRY(hipMemsetAsync(d_counts, 0, 8 * n * bins, stream));
+        DevBuf scratch; // until the launches have run
         if (!U::nothing(g, c, n)) {
+            if (int rc = piece_scratch(c, n, scratch)) return rc;
             StageTimer clock(g->timing, stream);
             for (size_t at = 0; at < n; at += kPiece) {
                 const uint32_t cnt = static_cast<uint32_t>(std::min(kPiece, n - at));
-                U::template launch<kProfile>(g, c, d_q + at, cnt, nullptr, nullptr, 0, reinterpret_cast<unsigned long long *>(d_counts + at * bins),
-                                             stream);
+                U::template launch<kProfile>(g, c, d_q + at, cnt, scratch.p, nullptr, nullptr, 0,
+                                             reinterpret_cast<unsigned long long *>(d_counts + at * bins), stream);
                 HIP_TRY(hipGetLastError());
                 clock.note("profile");
             }

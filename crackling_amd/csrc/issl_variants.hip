@@ -1,13 +1,11 @@
 // Variant-aware genome search: issl_genome_search with IUPAC ambiguity codes in the text read as sets of bases
 // (issl_genome_search_variants*, include/issl_hip.h), and SNPs written onto a resident genome (issl_vcf_snps,
-// issl_genome_apply_snps, issl_genome_apply_vcf).  The third unit of SearchDriver (issl_search_device.hpp) beside
-// issl_search.hip and issl_bulge.hip, with the protocol of issl_search_core.hpp: count, emit, sort, offsets, finish, and
-// the one-pass profile.  This unit's own: bit planes in place of 2-bit codes.  The tile goes to LDS as four planes (A C G
-// T; plane b bit i: base b is in the set of text position i) and a validity bit per base, 32 bases per word; a window is
-// four words cut out with a funnel shift; the pattern is four plane masks, and strand 1 is tested on the forward window
-// with the reversed, complemented pattern, so no window is reversed in the front.  A piece's queries are expanded once
-// into 16-byte records of planes (k_variant_queries), the same 16 B and the same group loads as the plain search's.  The
-// comparison is four ANDs ORed together for all 32 positions, five instructions and a popcount.  The plane arithmetic is issl_variants_text.hpp's, which
+// issl_genome_apply_snps, issl_genome_apply_vcf).  The third unit of SearchDriver (issl_search_device.hpp) with the
+// protocol of issl_search_core.hpp; the text as bit planes in place of 2-bit codes, and the front on them, is
+// issl_planes_device.hpp's, which issl_bulge_variants.hip includes as well.  This unit's own: a piece's queries are
+// expanded once into 16-byte records of planes (k_variant_queries, into the driver's scratch), the same 16 B and the same
+// group loads as the plain search's; the comparison is four ANDs ORed together for all 32 positions, five instructions
+// and a popcount; k_variants_finish; the SNP kernels.  The plane arithmetic is issl_variants_text.hpp's, which
 // tools/variants_sanitize.cpp checks on the CPU.
 #include <hip/hip_runtime.h>
 
@@ -18,50 +16,12 @@
 #include "issl_genome_handle.hpp"
 #include "issl_host.hpp"
 #include "issl_match.hpp"
-#include "issl_search_core.hpp"
-#include "issl_variants_text.hpp"
+#include "issl_planes_device.hpp"
 
 namespace issl {
 namespace {
 
-namespace vt = variants_text;
-using vt::Planes;
-using vt::VariantArgs;
-
-constexpr uint32_t kPlaneWords = kPosPerBlock / 32 + 1; // 32 bases per word; the halo of up to 31 bases is one more word
-static_assert(sizeof(issl_variant_hit) == 40 && sizeof(issl_snp) == 16 && sizeof(vt::SnpPlace) == 16 && sizeof(Planes) == 16,
-              "the layouts of include/issl_hip.h");
-
-// What a checked call carries to the launches: the pattern and limits, and room for the planes of a piece's queries.
-struct VariantCall {
-    VariantArgs a;
-    Planes *q_planes;
-};
-
-// 16 bytes of text at `at` (a multiple of 16) -> 16 bits of every plane and one bit per base that is none of the 14
-// codes; what lies behind the text is such a base.
-__device__ __forceinline__ void planes16(const uint8_t *__restrict__ s, uint64_t at, uint64_t len, uint32_t (&plane)[4], uint32_t &bad)
-{
-    plane[0] = plane[1] = plane[2] = plane[3] = 0;
-    bad = 0;
-    uint32_t w[4] = {0, 0, 0, 0}; // (a zero byte is no code)
-    if (at + 16 <= len) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(s + at);
-        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-    } else {
-        for (uint32_t i = 0; i < 16; ++i)
-            if (at + i < len) w[i >> 2] |= static_cast<uint32_t>(s[at + i]) << (8 * (i & 3));
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 16; ++i) {
-        const uint32_t set = vt::text_set(static_cast<uint8_t>(w[i >> 2] >> (8 * (i & 3))));
-        plane[0] |= (set & 1u) << i;
-        plane[1] |= (set >> 1 & 1u) << i;
-        plane[2] |= (set >> 2 & 1u) << i;
-        plane[3] |= (set >> 3) << i;
-        bad |= (set ? 0u : 1u) << i;
-    }
-}
+static_assert(sizeof(issl_variant_hit) == 40 && sizeof(issl_snp) == 16 && sizeof(vt::SnpPlace) == 16, "the layouts of include/issl_hip.h");
 
 // The queries of a piece as planes: a compared position in its base's plane alone, an N position in all four.
 __global__ __launch_bounds__(256) void k_variant_queries(const issl_search_query *__restrict__ q, uint32_t n, uint32_t win_mask,
@@ -70,8 +30,6 @@ __global__ __launch_bounds__(256) void k_variant_queries(const issl_search_query
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k < n) out[k] = vt::query_planes(q[k].sig, q[k].care, win_mask);
 }
-
-struct PlaneGroup { Planes q[kQueryGroup]; };
 
 // ctr[0]: hits; ctr[1]: the cursor of k_variants<kEmit>; ctr[2]: window-strands the pattern admits; ctr[3]: windows of L
 // codes with at most max_variants ambiguous positions (the figures of the timing line, kCount only).
@@ -88,56 +46,12 @@ __global__ __launch_bounds__(256) void k_variants(const uint8_t *__restrict__ s,
     const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kPosPerBlock;
     const uint32_t lane = threadIdx.x & 63;
     if (threadIdx.x == 0) q_count = 0;
-    {
-        uint32_t plane[4], bad;
-        planes16(s, base + 16ull * threadIdx.x, len, plane, bad);
-#pragma unroll
-        for (uint32_t b = 0; b < 4; ++b) reinterpret_cast<uint16_t *>(tile[b])[threadIdx.x] = static_cast<uint16_t>(plane[b]);
-        reinterpret_cast<uint16_t *>(tile[4])[threadIdx.x] = static_cast<uint16_t>(bad);
-        if (threadIdx.x < 2) {
-            planes16(s, base + kPosPerBlock + 16ull * threadIdx.x, len, plane, bad);
-#pragma unroll
-            for (uint32_t b = 0; b < 4; ++b) reinterpret_cast<uint16_t *>(tile[b])[256 + threadIdx.x] = static_cast<uint16_t>(plane[b]);
-            reinterpret_cast<uint16_t *>(tile[4])[256 + threadIdx.x] = static_cast<uint16_t>(bad);
-        }
-    }
+    fill_planes16(s, base + 16ull * threadIdx.x, len, tile, threadIdx.x);
+    if (threadIdx.x < 2) fill_planes16(s, base + kPosPerBlock + 16ull * threadIdx.x, len, tile, 256 + threadIdx.x); // the halo
     __syncthreads();
-
-    // -- the pattern on the thread's 16 windows, both strands: two bits per window
-    uint32_t pass = 0, windows = 0;
-    {
-        const uint32_t wi = threadIdx.x >> 1, s0 = (threadIdx.x & 1u) << 4;
-        uint32_t lo[5], hi[5];
-#pragma unroll
-        for (uint32_t b = 0; b < 5; ++b) lo[b] = tile[b][wi], hi[b] = tile[b][wi + 1];
-#pragma unroll
-        for (uint32_t k = 0; k < 16; ++k) {
-            if (vt::funnel(lo[4], hi[4], s0 + k) & a.win_mask) continue;
-            const Planes f{{vt::funnel(lo[0], hi[0], s0 + k) & a.win_mask, vt::funnel(lo[1], hi[1], s0 + k) & a.win_mask,
-                            vt::funnel(lo[2], hi[2], s0 + k) & a.win_mask, vt::funnel(lo[3], hi[3], s0 + k) & a.win_mask}};
-            if (static_cast<uint32_t>(__builtin_popcount(vt::ambiguous(f))) > a.max_variants) continue;
-            ++windows;
-            if (vt::admits(f, a.allow, a.win_mask)) pass |= 1u << (2 * k);
-            if (vt::admits(f, a.allow_rc, a.win_mask)) pass |= 2u << (2 * k);
-        }
-    }
-    // -- the survivors into the queue: a scan inside the wave, one LDS atomic per wave
-    {
-        const uint32_t cnt = static_cast<uint32_t>(__builtin_popcount(pass));
-        uint32_t incl = cnt;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += y;
-        }
-        uint32_t wave_base = 0;
-        if (lane == 63 && incl) wave_base = atomicAdd(&q_count, incl);
-        wave_base = __shfl(wave_base, 63, 64);
-        uint32_t at = wave_base + incl - cnt;
-        for (uint32_t m = pass; m; m &= m - 1) {
-            const uint32_t bit = static_cast<uint32_t>(__builtin_ctz(m));
-            queue[at++] = static_cast<uint16_t>(((threadIdx.x * 16 + (bit >> 1)) << 1) | (bit & 1u));
-        }
-    }
+    uint32_t pass, windows;
+    test_plane_windows(a, tile, pass, windows);
+    queue_survivors(pass, lane, queue, q_count);
     __syncthreads();
     const uint32_t n_q = q_count;
 
@@ -151,10 +65,7 @@ __global__ __launch_bounds__(256) void k_variants(const uint8_t *__restrict__ s,
         Planes t{{0, 0, 0, 0}}; // what the strand reads, cut by the pattern: nothing matches where there is no survivor
         if (valid) {
             tag = queue[j];
-            const uint32_t p = tag >> 1, wi = p >> 5, sh = p & 31u;
-            const Planes f{{vt::funnel(tile[0][wi], tile[0][wi + 1], sh) & a.win_mask, vt::funnel(tile[1][wi], tile[1][wi + 1], sh) & a.win_mask,
-                            vt::funnel(tile[2][wi], tile[2][wi + 1], sh) & a.win_mask, vt::funnel(tile[3][wi], tile[3][wi + 1], sh) & a.win_mask}};
-            t = vt::intersect((tag & 1u) ? vt::strand1(f, a.rev_shift) : f, a.allow);
+            t = survivor_planes(tag, tile, a);
         }
         const uint64_t live = __ballot(valid);
         uint32_t mine = 0; // kCount: at most 2^22 hits of this lane's survivor
@@ -185,17 +96,7 @@ __global__ __launch_bounds__(256) void k_variants(const uint8_t *__restrict__ s,
         for (; qi < mine_q.hi; ++qi) compare(q[qi], qi);
         if (kMode == kCount && valid) found += mine;
     }
-    if (kMode == kCount) {
-        for (int d = 32; d > 0; d >>= 1) {
-            windows += __shfl_down(windows, d, 64);
-            found += __shfl_down(found, d, 64);
-        }
-        if (lane == 0) {
-            if (found) atomicAdd(ctr, found);
-            if (windows) atomicAdd(ctr + 3, static_cast<unsigned long long>(windows));
-        }
-        if (threadIdx.x == 0 && n_q) atomicAdd(ctr + 2, static_cast<unsigned long long>(n_q));
-    }
+    if (kMode == kCount) count_totals(windows, found, n_q, lane, ctr);
 }
 
 // Row j is sorted word j: the window is read again, as text.
@@ -206,10 +107,9 @@ __global__ __launch_bounds__(256) void k_variants_finish(const uint64_t *__restr
 {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= total) return;
-    const uint64_t w = words[j];
-    const uint32_t strand = static_cast<uint32_t>(w & 1u);
-    const uint64_t pos = (w >> 1) & ((1ull << pos_bits) - 1);
-    const uint32_t qi = static_cast<uint32_t>(w >> (pos_bits + 1));
+    uint32_t qi, strand, low;
+    uint64_t pos;
+    decode_hit<0>(words[j], pos_bits, qi, pos, strand, low);
     vt::RowFields f{};
     vt::window_row(s + pos, a, strand, q[qi].sig, q[qi].care, f);
     const uint32_t rec = last_not_above(starts, n_records, pos);
@@ -251,37 +151,38 @@ __global__ __launch_bounds__(256) void k_snp_apply(uint8_t *__restrict__ s, cons
 
 struct VariantSearch {
     using Row = issl_variant_hit;
-    using Call = VariantCall;
+    using Call = VariantArgs;
     static constexpr size_t kPieceQueries = size_t(1) << 22; // 22 bits of query + 41 of position + 1 of strand = one word
     static constexpr uint32_t kLowBits = 0;
     static constexpr const char *kTag = "[issl variants]", *kRows = "hits";
-    static std::string counted(const Call &c) { return ", at most " + std::to_string(c.a.max_variants) + " variants"; }
-    static bool nothing(const issl_genome *g, const Call &c, size_t n) { return n == 0 || g->len < c.a.length; }
-    static size_t bins(const Call &c) { return c.a.max_dist + 1; }
+    static std::string counted(const Call &a) { return ", at most " + std::to_string(a.max_variants) + " variants"; }
+    static bool nothing(const issl_genome *g, const Call &a, size_t n) { return n == 0 || g->len < a.length; }
+    static size_t bins(const Call &a) { return a.max_dist + 1; }
+    static size_t scratch_bytes(const Call &, size_t n) { return sizeof(Planes) * n; } // the planes of a piece's queries
 
     // The first launch of a piece (kCount, or kProfile alone) expands its queries; kEmit follows kCount on the same piece.
     template <int kMode>
-    static void launch(const issl_genome *g, const Call &c, const issl_search_query *d_q, uint32_t n, unsigned long long *ctr, uint64_t *words,
-                       uint64_t cap, unsigned long long *counts, hipStream_t stream)
+    static void launch(const issl_genome *g, const Call &a, const issl_search_query *d_q, uint32_t n, void *scratch, unsigned long long *ctr,
+                       uint64_t *words, uint64_t cap, unsigned long long *counts, hipStream_t stream)
     {
-        if (kMode != kEmit)
-            hipLaunchKernelGGL(k_variant_queries, dim3((n + 255) / 256), dim3(256), 0, stream, d_q, n, c.a.win_mask, c.q_planes);
-        hipLaunchKernelGGL(k_variants<kMode>, dim3(text_blocks(g)), dim3(256), 0, stream, static_cast<const uint8_t *>(g->seq.p), g->len, c.a,
-                           static_cast<const Planes *>(c.q_planes), n, g->pos_bits, ctr, words, cap, counts);
+        Planes *q_planes = static_cast<Planes *>(scratch);
+        if (kMode != kEmit) hipLaunchKernelGGL(k_variant_queries, dim3((n + 255) / 256), dim3(256), 0, stream, d_q, n, a.win_mask, q_planes);
+        hipLaunchKernelGGL(k_variants<kMode>, dim3(text_blocks(g)), dim3(256), 0, stream, static_cast<const uint8_t *>(g->seq.p), g->len, a,
+                           static_cast<const Planes *>(q_planes), n, g->pos_bits, ctr, words, cap, counts);
     }
 
-    static void finish(const issl_genome *g, const Call &c, const uint64_t *words, uint32_t total, const issl_search_query *d_q,
+    static void finish(const issl_genome *g, const Call &a, const uint64_t *words, uint32_t total, const issl_search_query *d_q,
                        uint32_t q_base, uint64_t *rows, hipStream_t stream)
     {
         hipLaunchKernelGGL(k_variants_finish, dim3((total + 255) / 256), dim3(256), 0, stream, words, total,
-                           static_cast<const uint8_t *>(g->seq.p), c.a, d_q, q_base, static_cast<const uint64_t *>(g->starts.p),
+                           static_cast<const uint8_t *>(g->seq.p), a, d_q, q_base, static_cast<const uint64_t *>(g->starts.p),
                            static_cast<uint32_t>(g->records.size()), g->pos_bits, rows);
     }
 };
 using Variants = SearchDriver<VariantSearch>;
 
-// The checks of a call before any device work.  ISSL_OK: c->a is what the kernels take.
-int check_variant_call(const issl_search_pattern *pat, int max_dist, int max_variants, size_t n, VariantCall *c)
+// The checks of a call before any device work.  ISSL_OK: *a is what the kernels take.
+int check_variant_call(const issl_search_pattern *pat, int max_dist, int max_variants, size_t n, VariantArgs *a)
 {
     SearchArgs plain;
     if (int rc = check_call(pat, max_dist, n, &plain)) return rc;
@@ -290,18 +191,7 @@ int check_variant_call(const issl_search_pattern *pat, int max_dist, int max_var
         set_error(err);
         return ISSL_E_ARG;
     }
-    c->a = vt::make_args(*pat, max_dist, max_variants);
-    c->q_planes = nullptr;
-    return ISSL_OK;
-}
-
-// Room for the planes of one piece's queries, on the handle's device.
-int piece_planes(issl_genome *g, size_t n, DevBuf &buf, VariantCall *c)
-{
-    HIP_TRY(hipSetDevice(g->device));
-    const size_t piece = std::min(n, VariantSearch::kPieceQueries);
-    if (piece) HIP_TRY(hipMalloc(&buf.p, sizeof(Planes) * piece));
-    c->q_planes = static_cast<Planes *>(buf.p);
+    *a = vt::make_args(*pat, max_dist, max_variants);
     return ISSL_OK;
 }
 
@@ -312,11 +202,10 @@ int apply_snps(issl_genome *g, const issl_snp *snps, size_t n, uint64_t *n_chang
         set_error("more than 2^32 - 1 snps in one call");
         return ISSL_E_UNSUPPORTED;
     }
-    std::vector<uint64_t> starts(g->records.size()), lengths(g->records.size());
-    for (size_t r = 0; r < g->records.size(); ++r) starts[r] = g->records[r].start, lengths[r] = g->records[r].length;
+    const RecordTable table(g);
     std::vector<vt::SnpPlace> places;
     std::string err;
-    if (!vt::merge_snps(snps, n, starts.data(), lengths.data(), starts.size(), places, err)) {
+    if (!vt::merge_snps(snps, n, table.starts.data(), table.lengths.data(), table.size(), places, err)) {
         set_error(err);
         return ISSL_E_ARG;
     }
@@ -356,12 +245,9 @@ int issl_genome_search_variants(issl_genome *g, const issl_search_pattern *pat, 
 {
     if (!g || !pat || (!queries && n) || !offsets || !n_total || (!hits && cap)) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
-        issl::VariantCall c;
-        if (int rc = issl::check_variant_call(pat, max_dist, max_variants, n, &c)) return rc;
-        if (int rc = issl::check_host_queries(queries, n, pat->length)) return rc;
-        issl::DevBuf planes;
-        if (int rc = issl::piece_planes(g, n, planes, &c)) return rc;
-        return issl::Variants::host_rows(g, c, pat->length, queries, n, offsets, hits, cap, n_total);
+        issl::VariantArgs a;
+        if (int rc = issl::check_variant_call(pat, max_dist, max_variants, n, &a)) return rc;
+        return issl::Variants::host_rows(g, a, pat->length, queries, n, offsets, hits, cap, n_total);
     });
 }
 
@@ -371,11 +257,9 @@ int issl_genome_search_variants_device(issl_genome *g, const issl_search_pattern
 {
     if (!g || !pat || (!d_queries && n) || !d_offsets || !n_total || (!d_hits && cap)) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
-        issl::VariantCall c;
-        if (int rc = issl::check_variant_call(pat, max_dist, max_variants, n, &c)) return rc;
-        issl::DevBuf planes;
-        if (int rc = issl::piece_planes(g, n, planes, &c)) return rc;
-        return issl::Variants::device_rows(g, c, d_queries, n, d_offsets, d_hits, cap, n_total, stream);
+        issl::VariantArgs a;
+        if (int rc = issl::check_variant_call(pat, max_dist, max_variants, n, &a)) return rc;
+        return issl::Variants::device_rows(g, a, d_queries, n, d_offsets, d_hits, cap, n_total, stream);
     });
 }
 
@@ -384,12 +268,9 @@ int issl_genome_search_variants_profile(issl_genome *g, const issl_search_patter
 {
     if (!g || !pat || (n && (!queries || !counts))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
-        issl::VariantCall c;
-        if (int rc = issl::check_variant_call(pat, max_dist, max_variants, n, &c)) return rc;
-        if (int rc = issl::check_host_queries(queries, n, pat->length)) return rc;
-        issl::DevBuf planes;
-        if (int rc = issl::piece_planes(g, n, planes, &c)) return rc;
-        return issl::Variants::host_profile(g, c, pat->length, queries, n, counts);
+        issl::VariantArgs a;
+        if (int rc = issl::check_variant_call(pat, max_dist, max_variants, n, &a)) return rc;
+        return issl::Variants::host_profile(g, a, pat->length, queries, n, counts);
     });
 }
 
@@ -398,11 +279,9 @@ int issl_genome_search_variants_profile_device(issl_genome *g, const issl_search
 {
     if (!g || !pat || (n && (!d_queries || !d_counts))) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
-        issl::VariantCall c;
-        if (int rc = issl::check_variant_call(pat, max_dist, max_variants, n, &c)) return rc;
-        issl::DevBuf planes;
-        if (int rc = issl::piece_planes(g, n, planes, &c)) return rc;
-        return issl::Variants::device_profile(g, c, d_queries, n, d_counts, stream);
+        issl::VariantArgs a;
+        if (int rc = issl::check_variant_call(pat, max_dist, max_variants, n, &a)) return rc;
+        return issl::Variants::device_profile(g, a, d_queries, n, d_counts, stream);
     });
 }
 
@@ -428,19 +307,11 @@ int issl_genome_apply_vcf(issl_genome *g, const char *vcf, size_t len, issl_vcf_
 {
     if (!g || (!vcf && len)) return issl::fail(ISSL_E_ARG, "null argument");
     return issl::abi_call([&]() -> int {
-        const size_t n_records = g->records.size();
-        std::vector<const char *> names(n_records);
-        std::vector<size_t> name_lens(n_records);
-        std::vector<uint64_t> lengths(n_records);
-        for (size_t r = 0; r < n_records; ++r) {
-            names[r] = g->records[r].name.data();
-            name_lens[r] = g->records[r].name.size();
-            lengths[r] = g->records[r].length;
-        }
+        const issl::RecordTable table(g);
         std::string err;
         std::vector<issl_snp> snps;
         issl_vcf_counts c{};
-        if (!issl::variants_text::read_vcf(vcf, len, names.data(), name_lens.data(), lengths.data(), n_records, snps, c, err)) {
+        if (!issl::variants_text::read_vcf(vcf, len, table.names.data(), table.name_lens.data(), table.lengths.data(), table.size(), snps, c, err)) {
             issl::set_error(err);
             return ISSL_E_ARG;
         }
