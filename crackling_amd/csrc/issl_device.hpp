@@ -346,6 +346,9 @@ struct Counters {
     uint32_t raw_overflow; // set when the raw buffer was too small
     uint32_t overflowed;  // hit slots: guides with more than kReplayLds hits (k_verify); 0 = nothing to group, no many-hit replay
     uint32_t scan_verified; // records the scan's own waves verified (k_scan's tail); the others are k_verify's
+    uint32_t lds_chunks;  // buffers of records that the scan's waves verified from their LDS (scan_tail_lds): chunks' worth that took no
+                          // chunk of the raw buffer -- and would, were the batch run again in full: the host adds them to raw_chunks
+    uint32_t raw_top;     // k_scan<THR, true> on the pruned plan: one past the last chunk that was given a fill count
     uint32_t replay_next[3]; // tickets of the many-hit replays (k_replay_mid, k_replay_big<256>, k_replay_big<1024>): the next entry
                              // of the shared guide list a workgroup of that kernel takes
 };

@@ -68,8 +68,19 @@ struct RawWriter {
                        // is a chain of six dependent accesses behind its last unit, with nothing on the CU to hide it:
                        // 64 guides 0.058 -> 0.076 ms, 10 k guides x 50 M sites 0.29 -> 0.42 ms per step with every wave's
                        // last chunk taken.  k_verify does those chunks at full occupancy, as before.)
+    uint32_t lbuf;     // the tail build on the pruned plan notes into LDS (wave_recs): byte address there of the buffer being filled
+                       // (`fill` counts ITS slots); the other buffer is lbuf ^ kRecBufBytes.  Everything else the buffers need is
+                       // looked at when one is full and lives in LDS (slot 0 of a waiting buffer, wave_bufs): the scalar registers
+                       // are all taken, and one more carried through the passes is one more spilt to a vector register's lanes
+    uint32_t budget;   // chunks' worth of records the wave may still take on for its tail: a buffer drained from LDS costs one, a
+                       // listed reservation its chunks -- in all the chunks of a full list (wave_runs), whichever way the records go
 };
 constexpr uint32_t kTailOn = 4u, kTailPending = 1u, kTailRangeDone = 2u, kTailLast = 8u;
+// ... of the LDS buffers: kTailLds: the other buffer is full and the tail's; kTailHave: `chunk` is a chunk nothing has been
+// copied to yet; kTailLean: a full buffer may wait in LDS for the tail (a lean batch: nothing wants its records' raw slots)
+constexpr uint32_t kTailLds = 16u, kTailHave = 32u, kTailLean = 64u;
+constexpr uint32_t kListChunks = 64u; // chunks of a full list: 1 + 1 + 2 + 4 + 8 + 16 + 16 + 16
+static_assert(kScanVerifyRuns == 8u, "kListChunks: the chunks of run_chunks(0 .. kScanVerifyRuns - 1)");
 // The wave's list in LDS for its verify tail: [0] = runs listed, then the first chunk of each -- run 0 is the wave's own
 // chunk, run k >= 1 its k-th reservation, min(1 << (k - 1), 16) chunks.  A list that is full stays as it is: what the wave
 // reserves from then on is k_verify's.  Behind the list: the tail's cursor (run, chunk of the run) and its count of
@@ -82,17 +93,42 @@ __device__ __forceinline__ uint32_t *wave_runs()
     return runs[threadIdx.x >> 6];
 }
 __device__ __forceinline__ uint32_t run_chunks(uint32_t k) { return k == 0u ? 1u : k > 4u ? 16u : 1u << (k - 1u); }
+// ... and, in the build for lean batches, two words for the wave's record buffers in LDS (wave_recs).  kBufDrained:
+// buffers the tail has drained from LDS; kBufTop: one past the last chunk the wave has given a fill count (k_verify stops at
+// the launch's largest).  Looked at when a buffer is full or drained, by lane 0.
+constexpr uint32_t kBufDrained = 0u, kBufTop = 1u;
+__device__ __forceinline__ uint32_t *wave_bufs()
+{
+    __shared__ uint32_t bufs[16][2];
+    return bufs[threadIdx.x >> 6];
+}
+// The wave's two record buffers in LDS (the tail build on the pruned plan): kChunkRecs slots each, slot 0 unused as in a
+// chunk, so a buffer is one round of the tail, two records per lane; slot 0 of a buffer that waits for the tail holds its
+// slots in use.  Addressed by 32-bit LDS byte addresses.
+typedef __attribute__((address_space(3))) uint64_t LdsRec;
+constexpr uint32_t kRecBufBytes = 8u * kChunkRecs;
+__device__ __forceinline__ uint32_t wave_recs()
+{
+    __shared__ __attribute__((aligned(2 * kRecBufBytes))) uint64_t recs[16][2u * kChunkRecs];
+    return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsRec *)recs[threadIdx.x >> 6])));
+}
+__device__ __forceinline__ LdsRec *lds_rec(uint32_t at) { return reinterpret_cast<LdsRec *>(static_cast<uintptr_t>(at)); }
 
 __device__ __forceinline__ void raw_retire(const RawWriter &w, uint32_t lane, const uint64_t *raw, uint32_t *raw_used)
 {
     if (lane == 0) raw_used[(w.chunk - raw) / kChunkRecs] = w.fill;
 }
 
+// LDS: the wave notes into LDS (note_candidates) and comes here for the chunk a buffer is copied to (lds_spill): `fill`
+// and the tail's flags are that buffer's business, and a reservation is listed only within the wave's budget.
+template <bool LDS = false>
 __device__ __forceinline__ void raw_acquire(RawWriter &w, uint64_t *raw, uint32_t max_chunks, Counters *counters,
                                             uint32_t lane)
 {
-    w.fill = 1;
-    if ((w.tail & kTailOn) != 0u) w.tail |= kTailPending | kTailLast;
+    if constexpr (!LDS) {
+        w.fill = 1;
+        if ((w.tail & kTailOn) != 0u) w.tail |= kTailPending | kTailLast;
+    }
     if (w.left != 0u) { // the next chunk of the reservation: its header was cleared with all the others (k_guide_hist)
         w.chunk += kChunkRecs;
         w.left -= 1u;
@@ -111,6 +147,11 @@ __device__ __forceinline__ void raw_acquire(RawWriter &w, uint64_t *raw, uint32_
     w.chunk = raw + static_cast<uint64_t>(idx) * kChunkRecs;
     w.left = take - 1u;
     if (take < 16u) w.reserve = take * 2u;
+    if constexpr (LDS) {
+        if ((w.tail & kTailOn) == 0u) return;
+        if (w.budget < take) return;
+        w.budget -= take; // (a list that is full has used the budget up: the reservations of a wave that drains nothing are 63 chunks)
+    }
     if ((w.tail & kTailOn) != 0u && lane == 0) {
         uint32_t *runs = wave_runs();
         const uint32_t listed = runs[0];
@@ -119,6 +160,57 @@ __device__ __forceinline__ void raw_acquire(RawWriter &w, uint64_t *raw, uint32_
             runs[0] = listed + 1u;
         }
     }
+}
+
+// A buffer of the wave's LDS records (`used` slots, slot 0 included) into the next chunk of the wave -- its own, then its
+// reservations, as the records went before there were buffers -- with two 8-byte stores per lane, and the chunk's fill
+// count.  From there the records go the way they always went: the read-back tail when the chunk is listed (`last`: also
+// when it is the first the wave retires), else k_verify.
+__device__ __forceinline__ void lds_spill(RawWriter &w, uint32_t buf, uint32_t used, bool last, uint32_t lane, uint64_t *raw,
+                                          uint32_t *raw_used, uint32_t max_chunks, Counters *counters)
+{
+    if ((w.tail & kTailHave) == 0u) raw_acquire<true>(w, raw, max_chunks, counters, lane);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint64_t r0 = lds_rec(buf)[lane], r1 = lds_rec(buf)[64u + lane];
+    if (lane != 0u && lane < used) w.chunk[lane] = r0;
+    if (64u + lane < used) w.chunk[64u + lane] = r1;
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t idx = static_cast<uint32_t>((w.chunk - raw) / kChunkRecs);
+    if (lane == 0) {
+        raw_used[idx] = used;
+        if (idx + 1u > wave_bufs()[kBufTop]) wave_bufs()[kBufTop] = idx + 1u;
+    }
+    w.tail &= ~kTailHave;
+    if ((w.tail & kTailOn) != 0u && (last || (w.tail & kTailLast) != 0u)) w.tail |= kTailPending | kTailLast;
+}
+
+// The buffer the wave is filling has no room for a pass's records.  A lean batch: it waits in LDS for the tail at the next
+// unit boundary and the wave goes on in the other buffer -- unless that one still waits (both filled inside one unit: a
+// hit-dense one), which then goes to a chunk first, or the wave's budget is used up.  Any other batch needs raw slots for its
+// grouping pass: every full buffer goes to a chunk at once.
+__device__ __forceinline__ void lds_buffer_full(RawWriter &w, uint32_t lane, uint64_t *raw, uint32_t *raw_used, uint32_t max_chunks,
+                                                Counters *counters)
+{
+    const bool waits = (w.tail & kTailLds) != 0u; // the other buffer: to a chunk, and this one waits in its place (its share of the budget too)
+    uint32_t used = w.fill;
+    w.fill = 1;
+    bool stays = waits;
+    if (!waits && (w.tail & kTailLean) != 0u) {
+        stays = w.budget != 0u;
+        if (stays) w.budget -= 1u;
+    }
+    if (stays) {
+        if (lane == 0) *lds_rec(w.lbuf) = used;
+        w.lbuf ^= kRecBufBytes;
+        w.tail |= kTailLds | kTailLast;
+        if (!waits) return;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        used = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(*lds_rec(w.lbuf)));
+    }
+    // (either way the buffer that goes to a chunk is the one the wave fills next: the copy's loads stand ahead of the next stores)
+    lds_spill(w, w.lbuf, used, true, lane, raw, raw_used, max_chunks, counters);
 }
 
 // ---- bit-sliced distance test -------------------------------------------------------------------
@@ -421,6 +513,7 @@ __device__ __forceinline__ RecLane rec_lane_at(uint32_t group_abs, uint32_t cand
     return {static_cast<uint32_t>(at), static_cast<uint32_t>(at >> 32)};
 }
 
+template <bool LDS = false>
 __device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, const uint32_t *pass_ids, uint32_t w_log, const RecLane &rl,
                                                 uint32_t lane, RawWriter &w, uint64_t *raw, uint32_t *raw_used,
                                                 uint32_t max_chunks, Counters *counters)
@@ -433,8 +526,12 @@ __device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, con
     do {
         const uint32_t n = static_cast<uint32_t>(__builtin_popcountll(who));
         if (__builtin_expect(w.fill + n > kChunkRecs, 0)) {
-            raw_retire(w, lane, raw, raw_used);
-            raw_acquire(w, raw, max_chunks, counters, lane);
+            if constexpr (LDS) {
+                lds_buffer_full(w, lane, raw, raw_used, max_chunks, counters);
+            } else {
+                raw_retire(w, lane, raw, raw_used);
+                raw_acquire(w, raw, max_chunks, counters, lane);
+            }
         }
         if (ok != 0u) {
             const uint32_t q = static_cast<uint32_t>(__builtin_ctz(ok));
@@ -444,7 +541,8 @@ __device__ __forceinline__ void note_candidates(uint32_t ok, uint32_t gslot, con
             // = raw_record(gslot + (q >> w_log), tile, off0 + (q & ((1u << w_log) - 1u))): off0 is a multiple of 1 << w_log
             const uint32_t slot = pass_ids ? pass_ids[q >> w_log] : gslot + (q >> w_log);
             const uint32_t lo = rl.lo | (q & ((1u << w_log) - 1u)), hi = rl.hi | (slot << 5);
-            w.chunk[w.fill + rank] = (static_cast<uint64_t>(hi) << 32) | lo;
+            if constexpr (LDS) *lds_rec(w.lbuf + 8u * (w.fill + rank)) = (static_cast<uint64_t>(hi) << 32) | lo; // (a 32-bit LDS address)
+            else w.chunk[w.fill + rank] = (static_cast<uint64_t>(hi) << 32) | lo;
         }
         w.fill += n;
         who = __ballot(ok != 0u);
@@ -499,6 +597,30 @@ __device__ __forceinline__ void scan_tail(uint32_t prune_mode, uint32_t lane, co
     if (lane == 0) { runs[kRunCursor] = k; runs[kRunCursor + 1u] = j; runs[kRunCursor + 2u] += verified; }
 }
 
+// The same round on a buffer of the wave's own LDS (`used` slots, slot 0 included), on a lean batch: the records never
+// left the wave, so there is no store to wait for, no fill count to read back and no mark to leave -- and no raw slot: on a
+// lean batch nothing reads a record's rank, terms or key by its slot (verify_finish<.., false>; a guide beyond its hit
+// slots makes the batch run again in full, k_replay).  The context was checked when the wave chose to keep buffers here
+// (kTailLean, scan_range).
+__device__ __forceinline__ void scan_tail_lds(uint32_t prune_mode, uint32_t lane, uint32_t buf)
+{
+    uint64_t kernarg = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr());
+    asm volatile("" : "+s"(kernarg));
+    KernargCtx &vc = *(KernargCtx *)kernarg;
+    asm volatile("" : "+v"(lane));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // the wave's own LDS stores (note_candidates), as in short_unit_masks
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t used = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(*lds_rec(buf))); // (slot 0: lds_buffer_full)
+    const uint32_t t0 = lane + 1u, t1 = lane + 65u;
+    const bool use0 = t0 < used, use1 = t1 < used && t1 < kChunkRecs;
+    const uint64_t rec0 = use0 ? lds_rec(buf)[t0] : 0ull;
+    const uint64_t rec1 = use1 ? lds_rec(buf)[t1] : 0ull;
+    __builtin_amdgcn_wave_barrier();
+    verify_record<true, false>(vc, prune_mode, rec0, use0, 0u, t0, lane);
+    verify_record<true, false>(vc, prune_mode, rec1, use1, 0u, t1, lane);
+    if (lane == 0) { wave_runs()[kRunCursor + 2u] += used - 1u; wave_bufs()[kBufDrained] += 1u; }
+}
+
 // Scan kernel.  A workgroup of 16 waves (two per CU = 8 waves per SIMD) owns one equal-cost range of the work
 // and its waves share the tiles of that range through a ticket counter in LDS: the hardware favours the older
 // waves of a SIMD, so waves with equal static shares finish anywhere between 30 % and 100 % of the kernel time
@@ -515,7 +637,7 @@ __device__ __forceinline__ void scan_tail(uint32_t prune_mode, uint32_t lane, co
 // The work of one scan workgroup.  FINE: the plan of the pruned scan (single-tile items numbered like the units).  A
 // function template instantiated once per plan inside k_scan, so that each copy reads its item list and guide words
 // through the kernel's own `__restrict__` arguments (a pointer chosen at run time loses the scalar loads).
-template <int THR, bool FINE, bool TAIL>
+template <int THR, bool FINE, bool TAIL, bool LEAN>
 __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_stream, const ScanItem *__restrict__ items,
                                            const PlanInfo *__restrict__ plan, const RangeStart *__restrict__ range_start,
                                            const std::conditional_t<FINE, FineSlot, uint32_t> *__restrict__ gword_stream, uint4 *wave_masks,
@@ -550,6 +672,18 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
         uint32_t *runs = wave_runs();
         runs[0] = 1u; runs[1] = wave_id; runs[kRunCursor] = 0u; runs[kRunCursor + 1u] = 0u; runs[kRunCursor + 2u] = 0u;
     }
+    w.lbuf = w.budget = 0u;
+    constexpr bool lds = FINE && TAIL && LEAN; // the build for a lean batch on the pruned plan (launch_scan_thr)
+    if constexpr (lds) {
+        // the records are noted into LDS; the first buffer that goes to a chunk goes to the wave's own.  A lean batch whose tail is
+        // armed keeps full buffers in LDS for it -- where the context in the kernel-argument segment is the kernel's own (scan_tail).
+        w.lbuf = wave_recs();
+        if (lane == 0) { wave_bufs()[kBufDrained] = 0u; wave_bufs()[kBufTop] = 0u; } // (the wave's own chunk is listed from the start)
+        w.budget = kListChunks - 1u;
+        w.tail |= kTailHave;
+        KernargCtx &kc = *(KernargCtx *)__builtin_amdgcn_kernarg_segment_ptr();
+        if (tail && vc.lean_tail != 0u && kc.raw == raw && kc.raw_used == raw_used) w.tail |= kTailLean;
+    }
     bool own_chunk = false;
     unsigned long long compared = 0ull; // (real candidate, real guide) pairs this wave has compared; wave-uniform
 
@@ -568,6 +702,12 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
     while (true) {
         if constexpr (FINE && TAIL) {
             // between two units: the chunks retired since; behind the last one: also the chunk the wave was writing
+            if constexpr (lds) {
+                if ((w.tail & kTailLds) != 0u) { // a full buffer of the wave's LDS
+                    scan_tail_lds(plan->fine, lane, w.lbuf ^ kRecBufBytes);
+                    w.tail &= ~kTailLds;
+                }
+            }
             if ((w.tail & kTailPending) != 0u) {
                 scan_tail(plan->fine, lane, raw, raw_used);
                 w.tail &= ~kTailPending;
@@ -578,7 +718,22 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
         if (lane == 0) u = atomicAdd(&next_unit, 1u);
         u = __builtin_amdgcn_readfirstlane(u);
         if (u >= n_units) {
-            if (own_chunk) {
+            if constexpr (lds) {
+                // the part-filled buffer: the tail's under the gate of a wave's last chunk (kTailLast) on a lean batch, else into
+                // the wave's next chunk -- its own, if no buffer went to one before -- for the read-back tail or k_verify
+                if (own_chunk && w.fill > 1u) {
+                    if ((w.tail & (kTailLean | kTailLast)) == (kTailLean | kTailLast) && w.budget != 0u) {
+                        if (lane == 0) *lds_rec(w.lbuf) = w.fill;
+                        w.lbuf ^= kRecBufBytes;
+                        w.tail |= kTailLds;
+                    } else {
+                        lds_spill(w, w.lbuf, w.fill, false, lane, raw, raw_used, max_chunks, counters);
+                    }
+                    w.fill = 1u;
+                }
+                if (own_chunk && no_own_chunk && lane == 0) counters->raw_overflow = 1u;
+                own_chunk = false; // (what follows asks whether a CHUNK is left for the read-back tail: lds_spill has said so)
+            } else if (own_chunk) {
                 raw_retire(w, lane, raw, raw_used);
                 if (no_own_chunk && lane == 0) counters->raw_overflow = 1u;
             }
@@ -657,7 +812,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                         PrevSlice prev;
                         const uint32_t ok = near_plane12_masks<THR>(c, wave_masks + i * 8u, thr, keep, prev);
                         if (__ballot(ok != 0u) != 0ull) {
-                            note_candidates(fine_dup(ok, prev, dup_filter), 0u, reinterpret_cast<const uint32_t *>(wave_masks + i * 8u) + kPassIds, w_log, rl, lane, w, raw,
+                            note_candidates<TAIL && LEAN>(fine_dup(ok, prev, dup_filter), 0u, reinterpret_cast<const uint32_t *>(wave_masks + i * 8u) + kPassIds, w_log, rl, lane, w, raw,
                                             raw_used, max_chunks, counters);
                             own_chunk = true;
                         }
@@ -703,7 +858,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                         PrevSlice prev;
                         const uint32_t ok = near_plane12<-1>(c, gg.s[uu].word, thr - cls, keep, prev);
                         if (__ballot(ok != 0u) != 0ull) {
-                            note_candidates(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
+                            note_candidates<TAIL && LEAN>(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                             own_chunk = true;
                         }
                     }
@@ -722,7 +877,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                             PrevSlice prev;
                             const uint32_t ok = near_plane12<(THR < 1 ? 0 : THR - 1)>(c, gg.s[uu].word, thr - 1u, keep, prev);
                             if (__ballot(ok != 0u) != 0ull) {
-                                note_candidates(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
+                                note_candidates<TAIL && LEAN>(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                                 own_chunk = true;
                             }
                         }
@@ -737,7 +892,7 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
                     PrevSlice prev;
                     const uint32_t ok = near_plane12<THR>(c, gg.s[uu].word, thr, keep, prev);
                     if (__ballot(ok != 0u) != 0ull) {
-                        note_candidates(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
+                        note_candidates<TAIL && LEAN>(fine_dup(ok, prev, dup_filter), gg.s[uu].id, nullptr, 5u, rl, lane, w, raw, raw_used, max_chunks, counters);
                         own_chunk = true;
                     }
                 }
@@ -792,6 +947,12 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
     if constexpr (FINE && TAIL) {
         if ((w.tail & kTailOn) != 0u && lane == 0 && wave_runs()[kRunCursor + 2u] != 0u) atomicAdd(&vc.counters->scan_verified, wave_runs()[kRunCursor + 2u]);
     }
+    if constexpr (lds) {
+        // what the host and k_verify have to know of the buffers: the chunks' worth of records that never took a chunk, and the
+        // last chunk that holds any
+        if (lane == 0 && wave_bufs()[kBufDrained] != 0u) atomicAdd(&counters->lds_chunks, wave_bufs()[kBufDrained]);
+        if (lane == 0 && wave_bufs()[kBufTop] != 0u) atomicMax(&counters->raw_top, wave_bufs()[kBufTop]);
+    }
     // the launch's own end: behind the tails, by the workgroup's last wave
     if (tail_launch && lane == 0 && atomicAdd(tails_done_p, 1u) == (blockDim.x >> 6) - 1u)
         atomicMax(span + 1, static_cast<unsigned long long>(__builtin_amdgcn_s_memrealtime()));
@@ -806,7 +967,9 @@ __device__ __forceinline__ void scan_range(const uint32_t *__restrict__ scan_str
 
 // INVARIANT: `vc` is the FIRST parameter.  scan_tail reads it at offset 0 of the kernel-argument segment (and checks what it
 // finds there against `raw` and `raw_used`).
-template <int THR, bool TAIL>
+// LEAN (with TAIL): the build for a lean batch (Workspace::lean_tail), whose waves on the pruned plan note into LDS and
+// verify from there; every other batch runs the build whose records go through the raw buffer, as they always did.
+template <int THR, bool TAIL, bool LEAN>
 __global__ __launch_bounds__(1024, 8) void k_scan(VerifyCtx vc,
                                                   const uint32_t *__restrict__ scan_stream,
                                                   const ScanItem *__restrict__ items_full,
@@ -836,10 +999,10 @@ __global__ __launch_bounds__(1024, 8) void k_scan(VerifyCtx vc,
     if (threadIdx.x == 0) atomicMin(span, t_start); // the launch's own span: first workgroup in, last one out
     // the plan of this batch: bucket-level items, or the successor-byte groups of the pruned scan (k_fine_plan)
     if (plan->fine != 0u)
-        scan_range<THR, true, TAIL>(scan_stream, items_fine, plan, range_start, gword_fine, tail_masks[threadIdx.x >> 6], raw, raw_used, max_chunks, counters, thr, stamps,
+        scan_range<THR, true, TAIL, LEAN>(scan_stream, items_fine, plan, range_start, gword_fine, tail_masks[threadIdx.x >> 6], raw, raw_used, max_chunks, counters, thr, stamps,
                               scan_count, &next_unit, &waves_done, &wg_compared, t_start, span, n_tiles, slice_bits, vc, &tails_done);
     else
-        scan_range<THR, false, TAIL>(scan_stream, items_full, plan, range_start, gword_full, tail_masks[threadIdx.x >> 6], raw, raw_used, max_chunks, counters, thr, stamps,
+        scan_range<THR, false, TAIL, LEAN>(scan_stream, items_full, plan, range_start, gword_full, tail_masks[threadIdx.x >> 6], raw, raw_used, max_chunks, counters, thr, stamps,
                                scan_count, &next_unit, &waves_done, &wg_compared, t_start, span, n_tiles, slice_bits, vc, &tails_done);
 }
 
@@ -848,13 +1011,18 @@ static void launch_scan_thr(const ImageView &v, const Workspace &ws, const Tunin
                             const VerifyCtx &vc, hipStream_t stream)
 {
     // pruned scan: the items and guide words grouped by (bucket, successor byte); the plan says which list counts
-    if (vc.scan_verify != 0u)
-        hipLaunchKernelGGL((k_scan<THR, true>), dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, vc, v.scan, ws.items,
+    if (vc.scan_verify != 0u && vc.lean_tail != 0u && prune_mode != 0u)
+        hipLaunchKernelGGL((k_scan<THR, true, true>), dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, vc, v.scan, ws.items,
+                           ws.fitems, ws.plan, ws.range_start, ws.gword, ws.fword,
+                           ws.raw, ws.raw_used, static_cast<uint32_t>(ws.cap_chunks), ws.counters, thr, ws.stamps, ws.scan_count,
+                           ws.scan_span + 2u * ws.span_slot, v.n_tiles, v.slice_width);
+    else if (vc.scan_verify != 0u)
+        hipLaunchKernelGGL((k_scan<THR, true, false>), dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, vc, v.scan, ws.items,
                            prune_mode ? ws.fitems : ws.items, ws.plan, ws.range_start, ws.gword, ws.fword,
                            ws.raw, ws.raw_used, static_cast<uint32_t>(ws.cap_chunks), ws.counters, thr, ws.stamps, ws.scan_count,
                            ws.scan_span + 2u * ws.span_slot, v.n_tiles, v.slice_width);
     else
-        hipLaunchKernelGGL((k_scan<THR, false>), dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, vc, v.scan, ws.items,
+        hipLaunchKernelGGL((k_scan<THR, false, false>), dim3(tn.scan_blocks), dim3(tn.scan_threads), 0, stream, vc, v.scan, ws.items,
                            prune_mode ? ws.fitems : ws.items, ws.plan, ws.range_start, ws.gword, ws.fword,
                            ws.raw, ws.raw_used, static_cast<uint32_t>(ws.cap_chunks), ws.counters, thr, ws.stamps, ws.scan_count,
                            ws.scan_span + 2u * ws.span_slot, v.n_tiles, v.slice_width);

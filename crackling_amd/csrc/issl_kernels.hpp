@@ -379,7 +379,10 @@ __device__ __forceinline__ VerifyRec verify_fetch(const Ctx &c, uint32_t prune_m
 }
 
 // `chunk`, `t`: the record's chunk and its slot there (1 .. kChunkRecs - 1 when in_use); lane: of the wave.
-template <bool SORTED_PRUNED, class Ctx>
+// SLOT = false: the record has no raw slot -- k_scan's tail on a buffer of its wave's LDS, a lean batch only: rank, terms
+// and key by raw slot are what the grouping pass reads, and a lean batch has none (a hit beyond its guide's slots is
+// counted in `overflowed`, and the batch runs again in full).
+template <bool SORTED_PRUNED, bool SLOT = true, class Ctx>
 __device__ __forceinline__ void verify_finish(const Ctx &c, uint32_t prune_mode, const VerifyRec &r, bool in_use,
                                               uint32_t chunk, uint32_t t, uint32_t lane)
 {
@@ -497,7 +500,7 @@ __device__ __forceinline__ void verify_finish(const Ctx &c, uint32_t prune_mode,
         s.pad = slot_pad(hit_occ, static_cast<uint32_t>(dist)); // (read by k_profile alone)
         c.slots[at] = s;
         key = kDeadKey;
-    } else if (live) {
+    } else if (SLOT && live) {
         const uint64_t slot = static_cast<uint64_t>(chunk) * (kChunkRecs - 1u) + (t - 1u); // < cap_chunks * 127 <= cap_hits
         c.rank[slot] = rank;
         // The terms (:392-460) -- unless the guide already has more hits than the replays that read them take
@@ -511,16 +514,16 @@ __device__ __forceinline__ void verify_finish(const Ctx &c, uint32_t prune_mode,
     }
     // (a lean batch has no grouping pass to read the keys back -- every hit went to its guide's slots, or the batch is run
     // again in full: 8 bytes per record that need not be written)
-    if (in_use && !c.lean_tail) c.raw[static_cast<uint64_t>(chunk) * kChunkRecs + t] = key;
+    if (SLOT && in_use && !c.lean_tail) c.raw[static_cast<uint64_t>(chunk) * kChunkRecs + t] = key;
 }
 
 // Both steps at once: one record per lane (k_verify).
-template <bool SORTED_PRUNED, class Ctx>
+template <bool SORTED_PRUNED, bool SLOT = true, class Ctx>
 __device__ __forceinline__ void verify_record(const Ctx &c, uint32_t prune_mode, uint64_t rec, bool in_use, uint32_t chunk,
                                               uint32_t t, uint32_t lane)
 {
     const VerifyRec r = verify_fetch<SORTED_PRUNED>(c, prune_mode, rec, in_use);
-    verify_finish<SORTED_PRUNED>(c, prune_mode, r, in_use, chunk, t, lane);
+    verify_finish<SORTED_PRUNED, SLOT>(c, prune_mode, r, in_use, chunk, t, lane);
 }
 
 } // namespace issl

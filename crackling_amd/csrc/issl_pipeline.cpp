@@ -428,7 +428,9 @@ int finish_batches(issl_index *ix, hipStream_t stream)
         // its hit slots (bit 2: one did; bit 1: and it had been enqueued lean -- once more, with the whole tail)
         lp->lean = (sticky[0] & 6u) == 0u && lp->ws.slot_hits >= kSlotHits;
         if (sticky[0] & 2u) retry = true;
-        if (sticky[0] & 1u) {
+        // (a lean batch's waves verify full buffers of records from their LDS, and those take no chunk: sticky[1] counts them in
+        // -- Counters::lds_chunks --, so the batch that is run again in full finds the chunks it needs)
+        if ((sticky[0] & 1u) || ((sticky[0] & 2u) && sticky[1] > lp->ws.cap_chunks)) {
             // sticky[1] = largest number of chunks any batch asked for
             int rc = ensure_raw_capacity(lp->ws, static_cast<size_t>(sticky[1]) + sticky[1] / 8 + 1024);
             if (rc) return rc;

@@ -26,10 +26,14 @@ __global__ __launch_bounds__(kChunkRecs, 8) void k_verify(VerifyCtx c, const Pla
     const bool none_marked = !MARKS || c.counters->scan_verified == 0u; // (a marked chunk has added its records to the counter)
     if (blockIdx.x == 0 && threadIdx.x == 0) { // what the host needs to know after any number of batches
         if (c.counters->raw_overflow) atomicOr(&sticky[0], 1u);
-        atomicMax(&sticky[1], n_chunks);
+        atomicMax(&sticky[1], n_chunks + (MARKS ? c.counters->lds_chunks : 0u)); // (what the batch would ask for, run in full; lds_chunks: 0 but behind k_scan's build for lean batches)
         if (plan->error) atomicOr(&sticky[2], plan->error);
     }
     if (n_chunks > cap_chunks) n_chunks = cap_chunks;
+    // a lean batch on the pruned plan (k_scan<THR, true, true>, launch_scan_thr): its waves note into LDS and say where the last
+    // chunk with records is; where they verified everything there, none -- the launch and the sticky words are all that is left
+    // of this kernel
+    if (MARKS && c.lean_tail != 0u && prune_mode != 0u && c.counters->raw_top < n_chunks) n_chunks = c.counters->raw_top;
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         // The passes behind the scan are chains of dependent loads at full occupancy: what they cost is the number of
         // links.  The chunk's header first: a chunk its scan wave has verified is left without asking for its records.
