@@ -188,6 +188,9 @@ static bool workspace_option(const issl_index *idx, const char *key, long long *
         {"ws_cap_fitems", static_cast<long long>(w.cap_fitems)},
         {"ws_lean", idx->lane.lean ? 1 : 0},
         {"ws_scan_verified", static_cast<long long>(idx->lane.scan_verified)},
+        {"ws_scan_lds_buffers", static_cast<long long>(idx->lane.scan_lds_buffers)},
+        {"ws_scan_raw_top", static_cast<long long>(idx->lane.scan_raw_top)},
+        {"ws_raw_chunks", static_cast<long long>(idx->lane.raw_chunks)},
     };
     for (const auto &k : keys)
         if (std::strcmp(k.key, key) == 0) {

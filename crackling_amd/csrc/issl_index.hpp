@@ -36,6 +36,7 @@ struct Lane {
     int last_max_dist = 0;
     uint32_t last_prune = 0;
     uint32_t scan_verified = 0; // Counters::scan_verified of the lane's last finished batch
+    uint32_t scan_lds_buffers = 0, scan_raw_top = 0, raw_chunks = 0; // ... its lds_chunks, raw_top and raw_chunks (ws_scan_lds_buffers, ws_scan_raw_top, ws_raw_chunks)
     bool lean = false;          // the lane's finished batches had no guide beyond its hit slots: the next ones are enqueued
                                 // without the grouping pass and the many-hit replays (Workspace::lean_tail)
 };

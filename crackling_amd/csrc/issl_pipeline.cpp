@@ -409,6 +409,11 @@ int finish_batches(issl_index *ix, hipStream_t stream)
         Counters c{};
         HIP_TRY(hipMemcpy(&c, lp->ws.counters, sizeof c, hipMemcpyDeviceToHost));
         lp->scan_verified = c.scan_verified; // (ws_scan_verified: the records of the lane's last batch that the scan's own waves verified)
+        // (ws_scan_lds_buffers, ws_scan_raw_top, ws_raw_chunks: which way that batch's records went -- buffers verified from LDS, one
+        // past the last chunk a buffer was copied to, chunks handed out)
+        lp->scan_lds_buffers = c.lds_chunks;
+        lp->scan_raw_top = c.raw_top;
+        lp->raw_chunks = c.raw_chunks;
         if (lp->ws.slots && lp->ws.slot_width == kSlotHits && ix->tuning.hit_slots && lp->last_n) {
             const size_t want = lp->ws.cap_slot_guides * size_t(kSlotHitsWide) * sizeof(SlotRec);
             size_t free_b = 0, total_b = 0;

@@ -299,7 +299,11 @@ int issl_index_set_option(issl_index *idx, const char *key, const char *value);
  * ws_fine_ways (placements per guide and bucket the pruned plan's arrays are sized for: 13 or 67), ws_cap_chunks (chunks of
  * the raw-record buffer), ws_cap_fitems (items of the pruned plan's list), ws_lean (1: the next batch is enqueued without
  * the grouping pass and the many-hit replays), ws_scan_verified (raw records of the lane's last finished batch that the scan's
- * own waves verified; the verify kernel took the others). */
+ * own waves verified; the verify kernel took the others), and of the same batch which way its records went:
+ * ws_scan_lds_buffers (buffers of records that the scan's waves verified from their LDS, which took no chunk: a lean batch on
+ * the pruned plan, else 0), ws_scan_raw_top (one past the last chunk that such a batch copied a buffer to, where the verify
+ * kernel stops; 0: no record left its wave) and ws_raw_chunks (chunks of the raw-record buffer handed out, the scan waves'
+ * own included). */
 int issl_index_get_option(const issl_index *idx, const char *key, long long *value);
 
 /* ---- guides (A2, isslScoreOfftargets.cpp:63-71,82-89,275-305) ---------------------------- */

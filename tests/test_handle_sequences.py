@@ -27,7 +27,8 @@ from test_offtarget_report import _check_csr, _cols, _profile_of, _scores_from
 pytestmark = pytest.mark.gpu
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 COMBOS = [(layout, width) for width in hs.WIDTHS for layout in hs.LAYOUTS]
-WS_KEYS = ("ws_cap_guides", "ws_slot_width", "ws_fine_ways", "ws_cap_chunks", "ws_cap_fitems", "ws_lean")
+WS_KEYS = ("ws_cap_guides", "ws_slot_width", "ws_fine_ways", "ws_cap_chunks", "ws_cap_fitems", "ws_lean",
+           "ws_scan_verified", "ws_scan_lds_buffers", "ws_scan_raw_top", "ws_raw_chunks")
 CAPACITIES = ("ws_cap_guides", "ws_fine_ways", "ws_cap_chunks", "ws_cap_fitems")
 
 

@@ -398,7 +398,8 @@ def test_every_documented_option_can_be_set_and_read_back(golden_uniform):
         ix.close()
 
 
-WORKSPACE_KEYS = ("ws_cap_guides", "ws_slot_width", "ws_fine_ways", "ws_cap_chunks", "ws_cap_fitems", "ws_lean")
+WORKSPACE_KEYS = ("ws_cap_guides", "ws_slot_width", "ws_fine_ways", "ws_cap_chunks", "ws_cap_fitems", "ws_lean",
+                  "ws_scan_verified", "ws_scan_lds_buffers", "ws_scan_raw_top", "ws_raw_chunks")
 
 
 def test_workspace_keys_are_read_only_and_zero_before_the_first_batch(golden_uniform):

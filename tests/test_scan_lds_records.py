@@ -12,13 +12,19 @@ always went (the read-back tail, k_verify).  A batch that is not lean runs the b
   lean to full two clean batches, then one with a guide of more than 512 hits: the batch runs again in full
   dump, lanes  issl_dump_hits, and lanes 2 and 3 with four batches in flight, on the second construction
 
+Which way a batch's records went is read from three keys of lane 0's last finished batch: ws_scan_lds_buffers (buffers
+verified from LDS), ws_scan_raw_top (one past the last chunk a buffer was copied to) and ws_raw_chunks (chunks handed out);
+tests/test_scan_lds_paths.py has the shipped default, the accounting of the buffers and a record buffer that is too small.
+
 The constructions are checked with the CPU oracle first (no guide beyond 512 hits where the lane has to stay lean)."""
+import re
+
 import numpy as np
 import pytest
 
 import oracle_util as ou
 from synth import random_sites, sigs_to_text, text_order_key
-from test_scan_verify import _cluster_world, _open, _same
+from test_scan_verify import ROOT, _cluster_world, _open, _same
 
 # (the cluster guide's 16 hits are noted in more than one slice each; with 16 .. 48 records for it, these prefixes cross the four sizes)
 PREFIXES = list(range(78, 117)) + list(range(205, 244))
@@ -100,12 +106,20 @@ def unit_case(tmp_path_factory):
     return path, all_guides, want, hits, per_guide
 
 
+def _pass_records(hits):
+    """The most records one pass can note in the boundary world: the cluster guide's largest hit count in one slice (a single
+    guide notes one record).  A buffer closes early only when a pass's records do not fit, so with this p a closed buffer
+    holds at least 127 - (p - 1) records."""
+    return int(np.bincount(hits[hits[:, 0] == 0][:, 1]).max())
+
+
 def test_the_constructions(boundary_case, unit_case):
     """The CPU oracle alone: the lane stays lean on both constructions (no guide beyond 512 hits), every single guide of the
     first has exactly one hit, and the added guide of the second has more than 512."""
     _, guides, _, _, per_guide = boundary_case
     assert per_guide.max() <= 512 and per_guide[0] == 16 and np.all(per_guide[1:] == 1), (per_guide[0], per_guide[1:].min(), per_guide[1:].max())
     assert len(guides) > max(PREFIXES)
+    assert _pass_records(boundary_case[3]) <= 16
     _, guides, _, _, per_guide = unit_case
     assert len(guides) == 121 and 256 <= per_guide[:-1].min() and per_guide[:-1].max() <= 512, (per_guide[:-1].min(), per_guide[:-1].max())
     assert per_guide[-1] > 512
@@ -115,23 +129,71 @@ def _prefix(want, k):
     return want[0][:k], want[1][:k]
 
 
+def _list_chunks():
+    """kListChunks of issl_kernels.hip (a wave's budget is one less), read as test_scan_verify._constant reads the header's."""
+    m = re.search(r"constexpr\s+uint32_t\s+kListChunks\s*=\s*(\d+)", (ROOT / "crackling_amd" / "csrc" / "issl_kernels.hip").read_text())
+    assert m
+    return int(m.group(1))
+
+
+def _paths(ix):
+    """Which way the last batch's records went: (buffers verified from LDS, one past the last chunk a buffer was copied to, chunks handed out)."""
+    return ix.get_option("ws_scan_lds_buffers"), ix.get_option("ws_scan_raw_top"), ix.get_option("ws_raw_chunks")
+
+
+def _first_batch_is_not_lean(ix):
+    """A handle's first batch runs k_scan<THR, true, false>: no buffer in LDS, and nothing writes raw_top."""
+    assert _paths(ix)[:2] == (0, 0), _paths(ix)
+
+
+@pytest.fixture(scope="module")
+def quiet_guide(boundary_case):
+    """A guide without a site within 4 mismatches in the boundary world: a batch of it notes nothing."""
+    path = boundary_case[0]
+    rng = np.random.default_rng(77)
+    oracle = ou.OracleIndex(path)
+    try:
+        for _ in range(64):
+            g = np.array([rng.integers(0, 1 << 40)], dtype=np.uint64)
+            if len(oracle.score(g, 4, 0.0, "and", want_hits=True)[2]) == 0:
+                return g, oracle.score(g, 4, 75.0, "and")
+    finally:
+        oracle.close()
+    raise AssertionError("no guide without hits")
+
+
 @pytest.mark.gpu
-def test_buffer_boundaries_one_wave_lean(boundary_case):
-    path, guides, want, _, per_guide = boundary_case
+def test_buffer_boundaries_one_wave_lean(boundary_case, quiet_guide):
+    path, guides, want, hits, per_guide = boundary_case
+    p = _pass_records(hits)
     ix = _open(path, "forced")
     ix.set_option("scan_blocks", 1).set_option("scan_threads", 64).set_option("prune", 1)
     ix.upload(0)
     try:
         assert _same(ix.score(guides[:8], 4, 75.0, "and"), _prefix(want, 8))   # (a clean batch: the lane's next ones are lean)
+        _first_batch_is_not_lean(ix)
+        # a batch that notes nothing: the chunks a launch hands out by itself (the waves' own)
+        assert _same(ix.score(quiet_guide[0], 4, 75.0, "and"), quiet_guide[1])
+        assert ix.stats()["hits"] == 0 and ix.get_option("ws_scan_verified") == 0 and _paths(ix)[:2] == (0, 0)
+        quiet_chunks = ix.get_option("ws_raw_chunks")
+        assert quiet_chunks > 0
         counts = []
         for k in PREFIXES:
             got = ix.score(guides[:k], 4, 75.0, "and")
             st = ix.stats()
             verified = ix.get_option("ws_scan_verified")
+            buffers, raw_top, raw_chunks = _paths(ix)
             print("prefix", k, "hits", st["hits"], "ws_scan_verified", verified, "raw_records", st["raw_records"])
+            if verified in (127, 128, 254, 255):
+                print("  ws_scan_verified", verified, "ws_scan_lds_buffers", buffers, "ws_scan_raw_top", raw_top, "ws_raw_chunks", raw_chunks)
             assert _same(got, _prefix(want, k)), k
             assert st["pruned"] == 2 and st["hits"] == per_guide[:k].sum(), k
             assert st["hits"] <= verified <= st["raw_records"], k
+            # fewer than 63 buffers: no record leaves the wave -- no chunk receives a buffer, none is handed out, and every
+            # verified record came from a buffer of at most 127; a buffer closes early only by what a pass notes (p records)
+            assert raw_top == 0 and raw_chunks == quiet_chunks, k
+            assert buffers >= -(-verified // 127), (k, buffers, verified)
+            assert (buffers - 1) * (127 - (p - 1)) < verified, (k, buffers, verified)
             counts.append(verified)
         # one wave with a forced tail verifies every record it notes: the prefixes take the wave across a buffer exactly full
         # (127 records), the first record of the second buffer, both full, and the first record behind them
@@ -156,6 +218,8 @@ def test_buffer_boundaries_one_wave_not_lean(boundary_case, slots):
             assert _same(got, _prefix(want, k)), k
             assert st["hits"] == per_guide[:k].sum(), k
             assert st["hits"] <= verified <= st["raw_records"], k
+            # lean_tail 0: the launch takes k_scan<THR, true, false>, the first batch as every other
+            assert _paths(ix)[:2] == (0, 0), (k, _paths(ix))
     finally:
         ix.close()
 
@@ -177,6 +241,14 @@ def test_both_buffers_inside_one_unit(unit_case, threads):
             assert _same(got, _prefix(want, n))
             assert st["pruned"] == 2 and st["hits"] == per_guide[:n].sum()
             assert 0 < verified <= st["raw_records"]
+            buffers, raw_top, raw_chunks = _paths(ix)
+            print("  ws_scan_lds_buffers", buffers, "ws_scan_raw_top", raw_top, "ws_raw_chunks", raw_chunks)
+            if call == 0:
+                _first_batch_is_not_lean(ix)
+            else:   # both buffers fill inside the cluster's unit: buffers verified from LDS AND buffers copied to chunks
+                assert buffers > 0 and 0 < raw_top <= raw_chunks, (call, buffers, raw_top, raw_chunks)
+                if threads == 64:   # (one wave's budget)
+                    assert buffers <= _list_chunks() - 1, (call, buffers)
     finally:
         ix.close()
 
@@ -189,8 +261,10 @@ def test_lean_to_full_and_back(unit_case):
     ix.set_option("scan_blocks", 1).set_option("prune", 1)
     ix.upload(0)
     try:
-        for _ in range(2):
+        for call in range(2):
             assert _same(ix.score(guides[:n], 4, 75.0, "and"), _prefix(want, n))
+            if call == 0:
+                _first_batch_is_not_lean(ix)
         # the lane is lean and the last guide outgrows its hit slots: the batch is run again with the whole tail
         assert _same(ix.score(guides, 4, 75.0, "and"), want)
         st = ix.stats()
@@ -210,6 +284,7 @@ def unit_forced(unit_case):
     ix.set_option("scan_blocks", 1).set_option("prune", 1)
     ix.upload(0)
     assert _same(ix.score(guides[:n], 4, 75.0, "and"), _prefix(want, n))
+    _first_batch_is_not_lean(ix)
     yield ix, guides[:n], _prefix(want, n), hits[hits[:, 0] < n]
     ix.close()
 
@@ -220,6 +295,7 @@ def test_dump_hits(unit_forced):
     got = ix.dump_hits(guides, 4, 0.0, "and")
     assert got.shape == hits.shape and np.array_equal(got, hits)
     assert ix.get_option("ws_scan_verified") > 0
+    assert ix.get_option("ws_scan_lds_buffers") == 0   # (a dump has no hit slots: the batch is not lean)
 
 
 @pytest.mark.gpu
